@@ -12,6 +12,12 @@ bulk_flux, set_vbc, lmd_vmix = KPP, wvelocity, diag with NINFO = 1) run on the d
 --no-physics holds their outputs fixed and times the section-8a hot path alone.
 
     python bench.py --gpus N --steps K --warmup W [--config BENCHMARK3 | BENCHMARK3_MPDATA | BENCHMARK1 ...]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W untimed steps, times K steps and prints the result line (value, ms_per_step, config).
+--dump-outputs DIR then writes what the last timed step left in the prognostic fields (dump_outputs below).
+--full adds what takes runs of its own: per-kernel hipEvent times (kernel_ms) and the step3d_t roofline
+(roofline), on one GPU BASELINE.json configuration 5 (config5) and the CPU baseline (cpu_baseline).
 
 For N > 1 the driver launches this file under torch.distributed.run, one rank
 per GPU; the grid is split into NtileI x NtileJ = N tiles (2x1, 4x1, 4x2) and the
@@ -45,6 +51,9 @@ BENCH_CONFIGS = {
     "BENCHMARK3_MPDATA": ("BENCHMARK3", 6, MPDATA),
     "BENCHMARK1_MPDATA": ("BENCHMARK1", 6, MPDATA),
 }
+# --dump-outputs: the prognostic fields of the step, at most DUMP_MAX_VALUES float64 values each (8 MB; 48 MB in all)
+DUMP_FIELDS = ("zeta", "ubar", "vbar", "u", "v", "t")
+DUMP_MAX_VALUES = 1 << 20
 
 
 def make_tile(config, **kw):
@@ -88,6 +97,24 @@ def kernel_source_sha(config):
         except OSError:
             return None
     return h.hexdigest()[:16]
+
+
+def dump_outputs(outdir, st, last_diag):
+    """--dump-outputs: DIR/<name>.npy (float64) for each of DUMP_FIELDS as the caller holds it after the last timed
+    step -- the whole array (every time level, halos included), or, where it has more than DUMP_MAX_VALUES values,
+    those at DUMP_MAX_VALUES positions of its Fortran-order flattening drawn without replacement by a generator
+    seeded with 0 (sorted; the same positions for the same arguments) -- and DIR/diag.npy, the 12-vector of the
+    last diag call, when the diagnostics ran."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    rng = np.random.default_rng(0)
+    for name in DUMP_FIELDS:
+        a = st[name]
+        if a.size > DUMP_MAX_VALUES:
+            a = a.reshape(-1, order="F")[np.sort(rng.choice(a.size, DUMP_MAX_VALUES, replace=False))]
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    if last_diag is not None:
+        np.save(os.path.join(outdir, "diag.npy"), np.asarray(last_diag, dtype=np.float64))
 
 
 # ----------------------------------------------------------------------------------------------
@@ -348,7 +375,12 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="BENCHMARK3")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run also measure kernel_ms + roofline and, on one GPU, config5 and "
+                         "cpu_baseline (each leg has a --no-... switch below)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the fields of the last timed step to DIR/<name>.npy (one GPU only; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-steps", type=int, default=10)
     ap.add_argument("--cpu-cores", type=int, default=0,
                     help="host cores of the CPU baseline (default: min(cores this process may use, 16 = the CPU share of a one-GPU box))")
@@ -363,12 +395,16 @@ def main():
                     help="several tiles over RCCL: replay LOOP_2D with its exchanges as one hipGraph (roms_hip_graph_exchanges); "
                          "auto = the library's default (off: measured slower in wall time on this stack)")
     ap.add_argument("--no-config5", action="store_true",
-                    help="skip the extra leg of the default run: BENCHMARK3_MPDATA (BASELINE.json configuration 5) timed "
+                    help="skip the extra leg of a --full run: BENCHMARK3_MPDATA (BASELINE.json configuration 5) timed "
                          "after the headline configuration and reported under the key config5")
     ap.add_argument("--no-physics", dest="physics", action="store_false",
                     help="keep the outputs of bulk_flux + set_vbc fixed instead of recomputing them on the "
                          "device every step (SURVEY 8f-1); default: recompute, as the reference's step does")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1")
 
     import torch
     import torch.distributed as dist
@@ -545,44 +581,45 @@ def main():
     torch.cuda.synchronize()
     barrier()
     wall = time.perf_counter() - t0
-    tick("kernel timing")
     if world > 1:
         tw = torch.tensor([wall], dtype=torch.float64)
         dist.all_reduce(tw, op=dist.ReduceOp.MAX)
         wall = float(tw.item())
 
-    # ---- roofline of the dominant graded kernel: step3d_t (live hipEvent timing) ----
-    be.timing(True)
-    per_kernel = {}
-    names = ["ana_srflux", "bulk_flux", "set_vbc", "lmd_vmix", "wvelocity", "diag", "set_massflux", "rho_eos", "omega", "set_zeta", "pre_step3d", "prsgrd", "t3dmix2", "rhs3d_tile",
-             "uv3dmix2", "step2d_loop", "set_depth", "step3d_uv", "step3d_t"]
-    acc = {n: [] for n in names}
-    for _ in range(5):
-        m.step()
-        tick()
-        for n in names:
-            v = be.last_ms(n)
-            if v >= 0:
-                acc[n].append(v)
-    for n in names:
-        if acc[n]:
-            per_kernel[n] = sum(acc[n]) / len(acc[n])
+    if args.dump_outputs:
+        be.to_host(list(DUMP_FIELDS))
+        dump_outputs(args.dump_outputs, st, m.last_diag)
+
     b = st.b
-    # achievable bandwidth next to the vendor peak: a streaming copy in the library's access
-    # pattern, 8 B read + 8 B written per double, on a working set of one 3-D field
-    ncal = (b.UBi - b.LBi + 1) * (b.UBj - b.LBj + 1) * b.N
-    cal = []
-    for _ in range(7):
-        be.calib_stream(ncal)
-        cal.append(be.last_ms("calib_stream"))
-    cal.sort()
-    measured_peak = 16.0 * ncal / (cal[len(cal) // 2] * 1e-3) / 1e9
-    be.timing(False)
+    per_kernel = {}
+    if args.full:
+        tick("kernel timing")
+        # ---- roofline of the dominant graded kernel: step3d_t (live hipEvent timing) ----
+        be.timing(True)
+        names = ["ana_srflux", "bulk_flux", "set_vbc", "lmd_vmix", "wvelocity", "diag", "set_massflux", "rho_eos", "omega", "set_zeta", "pre_step3d", "prsgrd", "t3dmix2", "rhs3d_tile",
+                 "uv3dmix2", "step2d_loop", "set_depth", "step3d_uv", "step3d_t"]
+        acc = {n: [] for n in names}
+        for _ in range(5):
+            m.step()
+            tick()
+            for n in names:
+                v = be.last_ms(n)
+                if v >= 0:
+                    acc[n].append(v)
+        for n in names:
+            if acc[n]:
+                per_kernel[n] = sum(acc[n]) / len(acc[n])
+        # achievable bandwidth next to the vendor peak: a streaming copy in the library's access
+        # pattern, 8 B read + 8 B written per double, on a working set of one 3-D field
+        ncal = (b.UBi - b.LBi + 1) * (b.UBj - b.LBj + 1) * b.N
+        cal = []
+        for _ in range(7):
+            be.calib_stream(ncal)
+            cal.append(be.last_ms("calib_stream"))
+        cal.sort()
+        measured_peak = 16.0 * ncal / (cal[len(cal) // 2] * 1e-3) / 1e9
+        be.timing(False)
     graph_state = be.graph_exchanges_state()      # 1: LOOP_2D ran as one hipGraph with its exchanges inside (loopback / opt-in)
-    tile_cells = (b.Iend - b.Istr + 1) * (b.Jend - b.Jstr + 1) * b.N
-    alg_bytes = 8.0 * (4 * b.NT + 4) * tile_cells          # SURVEY.md section 8d (compulsory traffic)
-    t_ms = per_kernel.get("step3d_t", float("nan"))
-    achieved = alg_bytes / (t_ms * 1e-3) / 1e9
     mpdata = any(st.p.Hadv[i] == 6 for i in range(b.NT))   # enum roms_adv: ADV_MPDATA
     # finite check: the timed run must not have blown up
     be.to_host(["zeta", "t"])
@@ -606,33 +643,40 @@ def main():
                if args.physics else "fixed inputs", "dt_s": dt, "ndtfast": st.p.ndtfast, "finite": ok}
         if notes:
             cfg["notes"] = notes
-        roof = {"kernel": ("k_mp_ta + k_mp_adiff + k_mp_update per tracer (step3d_t_tile, MPDATA)" if mpdata
-                           else "k_step3d_t_pipe (step3d_t_tile)"),
-                "bound": "hbm", "achieved": achieved,
-                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                "traffic": pmc_traffic(args.config, args.gpus)[0], "traffic_unit": "bytes/launch",
-                "traffic_source": pmc_traffic(args.config, args.gpus)[1],
-                "avg_ms": t_ms, "algorithmic_bytes": alg_bytes,
-                "measured_peak": measured_peak,
-                "measured_peak_note": "streaming copy k_calib_stream, 8 B read + 8 B written per double, one 3-D field"}
-        if mpdata:
-            multi = 8.0 * (12 * b.NT + 6) * tile_cells     # Ta, Ua, Va, Wa, beta_up/dn materialised
-            roof["multipass_bytes"] = multi
-            roof["multipass_frac"] = multi / (t_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
         out = {
             "metric": "simulated-days/wall-sec", "value": value, "unit": "simulated-days/s",
             "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * wall / args.steps, "higher_is_better": True,
             "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": cfg, "roofline": roof, "kernel_ms": per_kernel,
+            "config": cfg,
         }
-        if args.gpus == 1 and args.config == "BENCHMARK3" and not args.no_config5 and not args.loopback:
+        if args.full:
+            tile_cells = (b.Iend - b.Istr + 1) * (b.Jend - b.Jstr + 1) * b.N
+            alg_bytes = 8.0 * (4 * b.NT + 4) * tile_cells          # SURVEY.md section 8d (compulsory traffic)
+            t_ms = per_kernel.get("step3d_t", float("nan"))
+            achieved = alg_bytes / (t_ms * 1e-3) / 1e9
+            roof = {"kernel": ("k_mp_ta + k_mp_adiff + k_mp_update per tracer (step3d_t_tile, MPDATA)" if mpdata
+                               else "k_step3d_t_pipe (step3d_t_tile)"),
+                    "bound": "hbm", "achieved": achieved,
+                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                    "traffic": pmc_traffic(args.config, args.gpus)[0], "traffic_unit": "bytes/launch",
+                    "traffic_source": pmc_traffic(args.config, args.gpus)[1],
+                    "avg_ms": t_ms, "algorithmic_bytes": alg_bytes,
+                    "measured_peak": measured_peak,
+                    "measured_peak_note": "streaming copy k_calib_stream, 8 B read + 8 B written per double, one 3-D field"}
+            if mpdata:
+                multi = 8.0 * (12 * b.NT + 6) * tile_cells     # Ta, Ua, Va, Wa, beta_up/dn materialised
+                roof["multipass_bytes"] = multi
+                roof["multipass_frac"] = multi / (t_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
+            out["roofline"] = roof
+            out["kernel_ms"] = per_kernel
+        if args.full and args.gpus == 1 and args.config == "BENCHMARK3" and not args.no_config5 and not args.loopback:
             # BASELINE.json configuration 5 on the same box, after the headline run (its own state and context)
             try:
                 out["config5"] = run_config5(args, device)
             except Exception as e:            # the headline line must not depend on this leg
                 out["config5"] = {"error": repr(e)}
-        if not args.no_cpu_baseline and args.gpus == 1:
+        if args.full and not args.no_cpu_baseline and args.gpus == 1:
             # the GPU boxes of this pool report every core of the host (256) but give a one-GPU job a share of
             # 16 (their process guard and memory cap are sized for that): the baseline uses that share
             ncores = args.cpu_cores or min(len(os.sched_getaffinity(0)), CPU_SHARE)

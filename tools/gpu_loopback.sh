@@ -7,8 +7,8 @@ OUT=$R/gpurun_out/loopback_$CFG
 mkdir -p "$OUT"
 export TMPDIR=/tmp PYTHONPATH=$R
 cd "$R"
-python3 bench.py --config $CFG --steps 40 --warmup 5 --no-config5 --no-cpu-baseline > "$OUT/plain.json" 2> "$OUT/plain.err"
-python3 bench.py --config $CFG --steps 40 --warmup 5 --no-config5 --no-cpu-baseline --loopback > "$OUT/loop.json" 2> "$OUT/loop.err"
+python3 bench.py --config $CFG --steps 40 --warmup 5 --full --no-config5 --no-cpu-baseline > "$OUT/plain.json" 2> "$OUT/plain.err"
+python3 bench.py --config $CFG --steps 40 --warmup 5 --full --no-config5 --no-cpu-baseline --loopback > "$OUT/loop.json" 2> "$OUT/loop.err"
 python3 - "$OUT" <<'PY'
 import json, sys
 o = sys.argv[1]
