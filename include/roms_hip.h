@@ -52,27 +52,7 @@ typedef struct roms_fields {
 } roms_fields_t;
 
 /* ------------------------------------------------------------------ */
-/* Tile bounds: every integer of ROMS/Include/set_bounds.h:20-79 and   */
-/* ROMS/Include/tile.h:21-45, plus DOMAIN(ng)%*_Edge(tile)             */
-/* (ROMS/Modules/mod_param.F:286-323) and the grid sizes.             */
-/* ------------------------------------------------------------------ */
-typedef struct roms_bounds {
-  int Lm, Mm, N, NT, NAT;
-  int ntileI, ntileJ, tile, Itile, Jtile;
-  int NghostPoints, EWperiodic, NSperiodic;
-  int west_edge, east_edge, south_edge, north_edge;
-  int LBi, UBi, LBj, UBj;
-  int Istr, Iend, Jstr, Jend;
-  int IstrB, IendB, IstrM, IstrP, IendP, IstrR, IendR, IstrT, IendT, IstrU;
-  int JstrB, JendB, JstrM, JstrP, JendP, JstrR, JendR, JstrT, JendT, JstrV;
-  int Istrm3, Istrm2, Istrm1, IstrUm2, IstrUm1;
-  int Iendp1, Iendp2, Iendp2i, Iendp3;
-  int Jstrm3, Jstrm2, Jstrm1, JstrVm2, JstrVm1;
-  int Jendp1, Jendp2, Jendp2i, Jendp3;
-} roms_bounds_t;
-
-/* ------------------------------------------------------------------ */
-/* Run-time parameters (mod_scalars.F, mod_param.F)                    */
+/* Limits and codes of the run-time parameters (roms_params_t)         */
 /* ------------------------------------------------------------------ */
 #define ROMS_MAXN   64     /* max vertical levels held in the param block   */
 #define ROMS_MAXNT  16     /* max tracers                                   */
@@ -107,118 +87,41 @@ enum roms_lbc {
 /* rows of roms_params_t.lbc = the state variables of LBC(:, isFsur / isUbar / isVbar / isUvel / isVvel / isTvar, ng) */
 enum roms_lbc_var { LBV_ZETA = 0, LBV_UBAR, LBV_VBAR, LBV_U, LBV_V, LBV_T, LBV_COUNT };
 enum roms_lbc_side { LBS_WEST = 0, LBS_EAST, LBS_SOUTH, LBS_NORTH };
-
-typedef struct roms_params {
-  double dt, dtfast;                 /* mod_scalars.F dt(ng), dtfast(ng)     */
-  double g, rho0;                    /* mod_scalars.F:431-441                */
-  double gamma2;                     /* slipperiness, roms_*.in GAMMA2       */
-  double lambda;                     /* implicit weight, mod_scalars.F:724   */
-  int    ndtfast, nfast;             /* set_weights.F:3-244                  */
-  double weight1[ROMS_MAXFAST];      /* weight(1,1:2*ndtfast,ng)             */
-  double weight2[ROMS_MAXFAST];      /* weight(2,1:2*ndtfast,ng)             */
-  int    Vtransform;                 /* set_depth.F:82                       */
-  int    limit_bstress;              /* LIMIT_BSTRESS: the bottom stress may only slow the bottom velocity down to zero
-                                      * within a step, set_vbc.F:533-540, :562-567 (sits in the alignment gap before hc) */
-  double hc;
-  double sc_r[ROMS_MAXN + 1], Cs_r[ROMS_MAXN + 1];   /* index 1..N           */
-  double sc_w[ROMS_MAXN + 1], Cs_w[ROMS_MAXN + 1];   /* index 0..N           */
-  int    Hadv[ROMS_MAXNT], Vadv[ROMS_MAXNT];         /* enum roms_adv        */
-  int    lbc_west, lbc_east, lbc_south, lbc_north;   /* enum roms_lbc        */
-  /* equation of state */
-  int    nonlin_eos;                 /* 1 = NONLIN_EOS (rho_eos.F:111)       */
-  int    eminusp;                    /* EMINUSP: bulk_flux also sets evap = LHeat / Hlv and the surface salt flux
-                                      * stflux(isalt) = (evap - rain) / rhow, bulk_flux.F:883-899 (alignment gap before R0) */
-  double R0, T0, S0, Tcoef, Scoef;   /* linear EOS (rho_eos.F:576)           */
-  /* CPP-derived option switches of the application header */
-  int    uv_adv, uv_cor, uv_vis2, curvgrid, var_rho_2d;   /* uv_vis2: 0 = no UV_VIS2, 1 = MIX_S_UV (uv3dmix2_s.h:114),
-                                                          * 2 = MIX_GEO_UV (uv3dmix2_geo.h:116) */
-  int    ts_dif2, mix_geo_ts, mix_s_ts, salinity, lmd_nonlocal, solar_source;
-  int    splines_vdiff, splines_vvisc;
-  double Akt_bak[ROMS_MAXNT], Akv_bak;
-  /* Jerlov water type constants of lmd_swfrac.F:6 (mod_scalars.F:1502-1512), uniform WTYPE */
-  double swfrac_mu1, swfrac_mu2, swfrac_r1;
-  /* per-step physics between the hot kernels */
-  int    uv_drag;                    /* bottom stress law of set_vbc.F: 1 = UV_LDRAG, 2 = UV_QDRAG, 3 = UV_LOGDRAG */
-  int    mpdata_fast;                /* library switch (no reference counterpart): 1 = the anti-diffusive
-                                      * velocities of mpdata_adiff use refined reciprocals instead of IEEE
-                                      * divisions (results within the 1e-10 relative-RMS bound of the exact
-                                      * kernel, not bit-identical); 0 = exact */
-  double blk_ZQ, blk_ZT, blk_ZW;     /* measurement heights of bulk_flux.F (roms_*.in BLK_ZQ/ZT/ZW) */
-  int    masking;                    /* 1 = the application defines MASKING: rmask/umask/vmask/pmask are applied
-                                      * where the reference applies them (e.g. step2d_LF_AM3.h:778, step3d_t.F:603) */
-  int    pgf;                        /* enum roms_pgf: the pressure-gradient algorithm prsgrd.F:16-26 selects */
-  /* lbc[side][variable] (enum roms_lbc_side, roms_lbc_var; every tracer shares LBV_T): 0 = take the side's
-   * lbc_west / lbc_east / lbc_south / lbc_north above, otherwise an enum roms_lbc code */
-  int    lbc[4][LBV_COUNT];
-  /* LBC_RADIATION_NUDGING ("RadNud"): nudging coefficients (1/s) of the boundary point towards the boundary data,
-   * per side and variable -- FSobc_out/in (zeta), M2obc_out/in (ubar, vbar), M3obc_out/in (u, v), Tobc_out/in (t; one
-   * value for all tracers) of mod_scalars.F:1336-1365, i.e. 1/(xNUDG*86400) and OBCFAC times that */
-  double obc_out[4][LBV_COUNT], obc_in[4][LBV_COUNT];
-  /* biharmonic lateral mixing (TS_DIF4, UV_VIS4 of the application header; coefficients diff4, visc4_r, visc4_p =
-   * the square roots the reference stores, inp_par.F:986, read_phypar.F:6905).  Tracers: along s-surfaces (mix_s_ts,
-   * t3dmix4_s.h:23) or geopotentials (mix_geo_ts, t3dmix4_geo.h:23); momentum: along s-surfaces (uv3dmix4_s.h:23)
-   * and the 2-D operator of step2d_LF_AM3.h:1494-1740.  TS_DIF2 and TS_DIF4 (UV_VIS2 and UV_VIS4) may both be set. */
-  int    ts_dif4, uv_vis4;
-  /* MIX_ISO_TS: tracer mixing along isopycnals (t3dmix2_iso.h:23, t3dmix4_iso.h:23) -- reads pden of rho_eos; takes
-   * precedence over mix_geo_ts / mix_s_ts.  The default slope treatment (none of TS_MIX_MAX_SLOPE, TS_MIX_MIN_STRAT). */
-  int    mix_iso_ts;
-  /* RADIATION_2D: the radiation conditions (LBC_RADIATION, LBC_RADIATION_NUDGING; 2-D and 3-D variables) include the
-   * tangential phase speed Ce (e.g. zetabc.F:141-147, t3dbc_im.F:151-165) */
-  int    radiation_2d;
-  /* UV_LOGDRAG (uv_drag = 3): limits of the drag coefficient of the logarithmic bottom layer, roms_*.in Cdb_min /
-   * Cdb_max (mod_scalars.F:747-748); the roughness length is the field ZoBot */
-  double Cdb_min, Cdb_max;
-  /* GLS_MIXING: the generic length-scale closure of Umlauf and Burchard (2003) as gls_prestep.F / gls_corstep.F build
-   * it (main3d.F:564-567, :790-793); the parameter sets of roms_*.in (GLS_P ... GLS_SIGP: k-kl = Mellor-Yamada 2.5,
-   * k-epsilon, k-omega, gen) select the closure.  gls_stability: enum roms_gls_stab (the CPP choice GALPERIN (none),
-   * KANTHA_CLAYSON, CANUTO_A, CANUTO_B); gls_n2s2_horavg = N2S2_HORAVG; gls_ri_splines = RI_SPLINES (the shear from
-   * parabolic splines); the third-order upstream advection of tke / gls (neither K_C2ADVECTION nor K_C4ADVECTION).
-   * CRAIG_BANNER, CHARNOK, ZOS_HSIG, TKE_WAVEDISS are not built.  Akk_bak, Akp_bak: background diffusivities of
-   * tke and gls; Zos: surface roughness (m), mod_scalars.F.
-   * gls_mixing = 2: MY25_MIXING instead -- the same two entries are then my25_prestep (my25_prestep.F:23, the text of
-   * gls_prestep.F) and my25_corstep (my25_corstep.F:27; tke = q2, gls = q2l; Galperin et al. stability functions, Sm
-   * of Kantha and Clayson with gls_stability = GLS_KANTHA_CLAYSON; N2S2_HORAVG, RI_SPLINES as above).  Of the
-   * parameters only gls_Kmin, gls_Pmin (initial values) and Akk_bak are read; Akp and ZoBot are not used. */
-  int    gls_mixing, gls_stability, gls_n2s2_horavg, gls_ri_splines;
-  double gls_p, gls_m, gls_n, gls_cmu0, gls_c1, gls_c2, gls_c3m, gls_c3p, gls_sigk, gls_sigp, gls_Kmin, gls_Pmin;
-  double Akk_bak, Akp_bak, Zos;
-  /* WET_DRY (wetdry.F, step2d_LF_AM3.h:729-755, :863-866, :2123-2160 ...): cells whose total depth falls to Dcrit
-   * (roms_*.in DCRIT, m) are masked out of the barotropic and baroclinic stepping.  The wet/dry masks are fields
-   * (pmask_wet ... vmask_full); roms_hip_wetdry initialises them (initial.F:438-466), every step2d call updates
-   * them.  With wet_dry the barotropic step takes the general launch sequence (flux, free surface, masks,
-   * momentum). */
-  int    wet_dry;
-  /* Point sources / sinks of mod_sources.F (rivers): bit 0 = LuvSrc(ng) (transport through u- / v-faces, Dsrc = 0 / 1),
-   * bit 1 = LwSrc(ng) (volume influx at cell centres, Dsrc = 2).  With LuvSrc the table comes from roms_hip_set_sources;
-   * until it has been handed over every entry refuses to run (error text "point sources"), so that a river application
-   * cannot lose its sources silently.  LwSrc is not built: refused.  0 = the application has none. */
-  int    point_sources;
-  double Dcrit;
-  /* ATM_PRESS (prsgrd32.h:229-232, :264-266; prsgrd31.h:196-198, :213-215, :294-296; prsgrd40.h:187-196): the
-   * atmospheric surface pressure Pair (mb, FID_Pair) in the baroclinic pressure gradient (inverse barometer).
-   * press_compensate = PRESS_COMPENSATE (with ATM_PRESS): the same term in the Flather value of the normal barotropic
-   * velocity (u2dbc_im.F:264-272, :612-620; v2dbc_im.F:266, :615). */
-  int    atm_press, press_compensate;
-  /* TS_MIX_STABILITY (t3dmix2_s.h:212-218, t3dmix2_geo.h:236-239 / :268 / :301, t3dmix2_iso.h:239 / :271 / :321, the
-   * first operator of t3dmix4_s.h:262 / :308, t3dmix4_geo.h:279 / :311 / :345, t3dmix4_iso.h:287 / :319 / :369): every
-   * tracer difference of the lateral mixing operator is 3/4 of t(nrhs)'s plus 1/4 of t(nstp)'s. */
-  int    ts_mix_stability;
-  /* TS_MIX_MIN_STRAT (t3dmix2_iso.h:313-316, t3dmix4_iso.h:361-364, :679-682; with MIX_ISO_TS): the density difference
-   * that scales the isopycnal slopes is at least strat_min = 0.1 kg/m3 per metre times the layer distance, in the
-   * place of the constant eps = 0.5. */
-  int    ts_mix_min_strat;
-} roms_params_t;
+/* roms_params_t.gls_stability */
 enum roms_gls_stab { GLS_GALPERIN = 0, GLS_KANTHA_CLAYSON = 1, GLS_CANUTO_A = 2, GLS_CANUTO_B = 3 };
+
+/* ------------------------------------------------------------------ */
+/* The three structs of the boundary.  Each is declared once, as an    */
+/* X-macro table beside this header (roms_bounds.def, roms_params.def, */
+/* roms_step_idx.def: one entry per member, with the member's          */
+/* documentation); the ctypes mirror and the tests read the same       */
+/* tables.                                                             */
+/* ------------------------------------------------------------------ */
+#define ROMS_MEMBER(type, name)             type name;
+#define ROMS_MEMBER_A(type, name, n)        type name[n];
+#define ROMS_MEMBER_A2(type, name, n1, n2)  type name[n1][n2];
+
+/* Tile bounds: every integer of ROMS/Include/set_bounds.h:20-79 and ROMS/Include/tile.h:21-45, plus
+ * DOMAIN(ng)%*_Edge(tile) (ROMS/Modules/mod_param.F:286-323) and the grid sizes. */
+typedef struct roms_bounds {
+#include "roms_bounds.def"
+} roms_bounds_t;
+
+/* Run-time parameters (mod_scalars.F, mod_param.F) and option switches; every member is documented in the table. */
+typedef struct roms_params {
+#include "roms_params.def"
+} roms_params_t;
 
 /* Time-level indices = mod_stepping.F (nstp,nnew,nrhs,kstp,krhs,knew) and
  * mod_scalars.F (iic, iif, ntfirst, PREDICTOR_2D_STEP); see
  * main3d.F:189-191 and main3d.F:597-662.  All 1-based as in Fortran. */
 typedef struct roms_step_idx {
-  int iic, ntfirst;
-  int nstp, nnew, nrhs;
-  int kstp, krhs, knew;
-  int iif, predictor_2d_step;
+#include "roms_step_idx.def"
 } roms_step_idx_t;
+
+#undef ROMS_MEMBER
+#undef ROMS_MEMBER_A
+#undef ROMS_MEMBER_A2
 
 /* ------------------------------------------------------------------ */
 /* Library life cycle                                                  */
@@ -331,12 +234,14 @@ int roms_hip_gls_corstep(const roms_step_idx_t *s);
  * from zeta, ubar, vbar of time level Tindex = s->kstp (initial.F:438-466; WET_DRY applications).  The per-call
  * update wetdry_tile (:93) runs inside roms_hip_step2d. */
 int roms_hip_wetdry(const roms_step_idx_t *s);
-/* The source table SOURCES(ng) of mod_sources.F:56-80 with LuvSrc (roms_params_t.point_sources bit 0): Isrc, Jsrc (grid
- * indices of the u- or v-face), Dsrc (0.0 = u-face, 1.0 = v-face), Qbar(Nsrc) (m3/s), Qsrc(Nsrc,N) = Qbar * Qshape as
- * set_data.F:136-143 leaves it, Tsrc(Nsrc,N,NT) and LtracerSrc(NT); Fortran element order.  Call it after every
- * set_data that changes them (the arrays are copied; a few kB).  The entries that consume it: step2d
- * (step2d_LF_AM3.h:2484-2502), step3d_uv (step3d_uv.F:971-995), pre_step3d (pre_step3d.F:530-553), step3d_t
- * (step3d_t.F:734-799), wetdry (wetdry.F:307-320, :511-524).  A source with Dsrc = 2 (LwSrc) is refused. */
+/* The source table SOURCES(ng) of mod_sources.F:56-80 with LuvSrc or LwSrc (roms_params_t.point_sources bits 0, 1):
+ * Isrc, Jsrc (grid indices of the u- or v-face, or of the cell), Dsrc (0.0 = u-face, 1.0 = v-face, 2.0 = cell centre:
+ * LwSrc), Qbar(Nsrc) (m3/s), Qsrc(Nsrc,N) = Qbar * Qshape as set_data.F:136-143 leaves it, Tsrc(Nsrc,N,NT) and
+ * LtracerSrc(NT); Fortran element order.  Call it after every set_data that changes them (the arrays are copied; a
+ * few kB).  The entries that consume it: step2d (step2d_LF_AM3.h:2484-2502; LwSrc: the free surface of the source
+ * cells), step3d_uv (step3d_uv.F:971-995), pre_step3d (pre_step3d.F:530-553), step3d_t (step3d_t.F:734-799; LwSrc:
+ * :1136-1158, :1331-1360), omega (LwSrc: omega.F:165-190), wetdry (wetdry.F:307-320, :511-524).  A source of a kind
+ * whose bit of point_sources is off is not looked at. */
 int roms_hip_set_sources(int Nsrc, const int *Isrc, const int *Jsrc, const double *Dsrc, const double *Qbar,
                          const double *Qsrc, const double *Tsrc, const int *LtracerSrc);
 /* wvelocity(ng,tile,nstp)          ROMS/Nonlinear/wvelocity.F:27     (main3d.F:475; writes wvel) */

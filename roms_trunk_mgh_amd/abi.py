@@ -1,19 +1,42 @@
-"""ctypes mirror of include/roms_hip.h (the C ABI) and of include/roms_fields.def.
+"""ctypes mirror of include/roms_hip.h (the C ABI).
 
-The field table is parsed from the .def file so that the C side and the Python
-side cannot drift apart; the struct layouts are checked at load time against
-``roms_abi_sizeof`` exported by both shared libraries.
+The field table (roms_fields.def), the members of the three structs (roms_bounds.def, roms_params.def,
+roms_step_idx.def) and the limits ROMS_MAXN ... are parsed from the files the C side compiles, so that the C side
+and the Python side cannot drift apart; the struct sizes are checked at load time against ``roms_abi_sizeof``
+exported by both shared libraries, every member's offset by tests/test_abi.py.
 """
 import ctypes as C
+import keyword
 import os
 import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INCLUDE_DIR = os.path.join(ROOT, "include")
 
-ROMS_MAXN = 64
-ROMS_MAXNT = 16
-ROMS_MAXFAST = 256
+
+def _read(name):
+    """A file of include/ without its C comments."""
+    with open(os.path.join(INCLUDE_DIR, name)) as fh:
+        return re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
+
+
+def _constants():
+    """The integer constants of roms_hip.h: its `#define NAME integer` lines and the enumerators of its enums
+    (roms_field_id, which expands roms_fields.def, is FIELD_ID below)."""
+    txt = _read("roms_hip.h")
+    out = {n: int(v) for n, v in re.findall(r"^#define\s+(\w+)\s+(\d+)\s*$", txt, flags=re.M)}
+    for body in re.findall(r"\benum\s+\w+\s*\{([^{}#]*)\}", txt):
+        nxt = 0
+        for item in body.split(","):
+            name, _, val = (x.strip() for x in item.partition("="))
+            out[name] = nxt = int(val) if val else nxt
+            nxt += 1
+    return out
+
+
+CONSTANTS = _constants()
+ROMS_MAXN, ROMS_MAXNT, ROMS_MAXFAST = (CONSTANTS[n] for n in ("ROMS_MAXN", "ROMS_MAXNT", "ROMS_MAXFAST"))
+LBV_COUNT = CONSTANTS["LBV_COUNT"]
 
 KINDS = ["K_2D", "K_2D_T2", "K_2D_T3", "K_2D_NT", "K_3DR", "K_3DW",
          "K_3DR_T2", "K_3DW_T2", "K_3DW_NAT", "K_4DT", "K_3DR_NT", "K_3DW_T3"]
@@ -29,18 +52,7 @@ LBV = {"zeta": 0, "ubar": 1, "vbar": 2, "u": 3, "v": 4, "t": 5}
 LBS = {"west": 0, "east": 1, "south": 2, "north": 3}
 
 
-def _parse_fields():
-    out = []
-    pat = re.compile(r"^ROMS_FIELD\(\s*(\w+)\s*,\s*(\w+)\s*,\s*(\w+)\s*\)")
-    with open(os.path.join(INCLUDE_DIR, "roms_fields.def")) as fh:
-        for line in fh:
-            m = pat.match(line.strip())
-            if m:
-                out.append((m.group(1), m.group(2), m.group(3)))
-    return out
-
-
-FIELDS = _parse_fields()                      # [(name, kind, owner)]
+FIELDS = re.findall(r"\bROMS_FIELD\(\s*(\w+)\s*,\s*(\w+)\s*,\s*(\w+)\s*\)", _read("roms_fields.def"))   # [(name, kind, owner)]
 FIELD_ID = {n: i for i, (n, _, _) in enumerate(FIELDS)}
 FIELD_KIND = {n: k for n, k, _ in FIELDS}
 
@@ -55,19 +67,51 @@ def trailing_shape(kind, N, NT, NAT):
     }[kind]
 
 
+def _extent(text):
+    """An array extent of a member table: an integer, a constant of roms_hip.h, or a constant + an integer."""
+    m = re.fullmatch(r"(\w+)(?:\s*\+\s*(\d+))?", text.strip())
+    if not m:
+        raise ValueError(f"array extent {text!r}: expected INTEGER, NAME or NAME + INTEGER")
+    base = m.group(1)
+    return (int(base) if base.isdigit() else CONSTANTS[base]) + int(m.group(2) or 0)
+
+
+def _parse_members(def_file):
+    """[(C type, C name, extents)] of one struct from its X-macro table: ROMS_MEMBER(type, name),
+    ROMS_MEMBER_A(type, name, n), ROMS_MEMBER_A2(type, name, n1, n2)."""
+    out = []
+    for args in re.findall(r"\bROMS_MEMBER(?:_A2?)?\(([^()]*)\)", _read(def_file)):
+        ctype, name, *ext = (a.strip() for a in args.split(","))
+        out.append((ctype, name, tuple(_extent(e) for e in ext)))
+    return out
+
+
+# the three structs of the C ABI, member for member as include/roms_hip.h declares them
+STRUCTS = {"roms_bounds_t": _parse_members("roms_bounds.def"),
+           "roms_params_t": _parse_members("roms_params.def"),
+           "roms_step_idx_t": _parse_members("roms_step_idx.def")}
+_CTYPES = {"int": C.c_int, "double": C.c_double}
+
+
+def py_name(c_name):
+    """Python spelling of a C member name (`lambda` is a keyword: `lambda_`)."""
+    return c_name + "_" if keyword.iskeyword(c_name) else c_name
+
+
+def _ctypes_fields(members):
+    out = []
+    for ctype, name, ext in members:
+        t = _CTYPES[ctype]
+        for n in reversed(ext):                 # int lbc[4][6] = (c_int * 6) * 4
+            t = t * n
+        out.append((py_name(name), t))
+    return out
+
+
 class Bounds(C.Structure):
     """roms_bounds_t -- ROMS/Include/set_bounds.h:20-79, tile.h:21-45."""
-    _names = (
-        "Lm Mm N NT NAT ntileI ntileJ tile Itile Jtile "
-        "NghostPoints EWperiodic NSperiodic "
-        "west_edge east_edge south_edge north_edge "
-        "LBi UBi LBj UBj Istr Iend Jstr Jend "
-        "IstrB IendB IstrM IstrP IendP IstrR IendR IstrT IendT IstrU "
-        "JstrB JendB JstrM JstrP JendP JstrR JendR JstrT JendT JstrV "
-        "Istrm3 Istrm2 Istrm1 IstrUm2 IstrUm1 Iendp1 Iendp2 Iendp2i Iendp3 "
-        "Jstrm3 Jstrm2 Jstrm1 JstrVm2 JstrVm1 Jendp1 Jendp2 Jendp2i Jendp3"
-    ).split()
-    _fields_ = [(n, C.c_int) for n in _names]
+    _fields_ = _ctypes_fields(STRUCTS["roms_bounds_t"])
+    _names = [n for n, _ in _fields_]
 
     def as_dict(self):
         return {n: getattr(self, n) for n in self._names}
@@ -75,51 +119,12 @@ class Bounds(C.Structure):
 
 class Params(C.Structure):
     """roms_params_t -- scalars of mod_scalars.F / mod_param.F used on the path."""
-    _fields_ = [
-        ("dt", C.c_double), ("dtfast", C.c_double),
-        ("g", C.c_double), ("rho0", C.c_double),
-        ("gamma2", C.c_double), ("lambda_", C.c_double),
-        ("ndtfast", C.c_int), ("nfast", C.c_int),
-        ("weight1", C.c_double * ROMS_MAXFAST),
-        ("weight2", C.c_double * ROMS_MAXFAST),
-        ("Vtransform", C.c_int), ("limit_bstress", C.c_int),
-        ("hc", C.c_double),
-        ("sc_r", C.c_double * (ROMS_MAXN + 1)), ("Cs_r", C.c_double * (ROMS_MAXN + 1)),
-        ("sc_w", C.c_double * (ROMS_MAXN + 1)), ("Cs_w", C.c_double * (ROMS_MAXN + 1)),
-        ("Hadv", C.c_int * ROMS_MAXNT), ("Vadv", C.c_int * ROMS_MAXNT),
-        ("lbc_west", C.c_int), ("lbc_east", C.c_int),
-        ("lbc_south", C.c_int), ("lbc_north", C.c_int),
-        ("nonlin_eos", C.c_int), ("eminusp", C.c_int),
-        ("R0", C.c_double), ("T0", C.c_double), ("S0", C.c_double),
-        ("Tcoef", C.c_double), ("Scoef", C.c_double),
-        ("uv_adv", C.c_int), ("uv_cor", C.c_int), ("uv_vis2", C.c_int),
-        ("curvgrid", C.c_int), ("var_rho_2d", C.c_int),
-        ("ts_dif2", C.c_int), ("mix_geo_ts", C.c_int), ("mix_s_ts", C.c_int),
-        ("salinity", C.c_int), ("lmd_nonlocal", C.c_int), ("solar_source", C.c_int),
-        ("splines_vdiff", C.c_int), ("splines_vvisc", C.c_int),
-        ("Akt_bak", C.c_double * ROMS_MAXNT), ("Akv_bak", C.c_double),
-        ("swfrac_mu1", C.c_double), ("swfrac_mu2", C.c_double), ("swfrac_r1", C.c_double),
-        ("uv_drag", C.c_int), ("mpdata_fast", C.c_int),
-        ("blk_ZQ", C.c_double), ("blk_ZT", C.c_double), ("blk_ZW", C.c_double),
-        ("masking", C.c_int), ("pgf", C.c_int),
-        ("lbc", (C.c_int * 6) * 4),
-        ("obc_out", (C.c_double * 6) * 4), ("obc_in", (C.c_double * 6) * 4),
-        ("ts_dif4", C.c_int), ("uv_vis4", C.c_int), ("mix_iso_ts", C.c_int), ("radiation_2d", C.c_int),
-        ("Cdb_min", C.c_double), ("Cdb_max", C.c_double),
-        ("gls_mixing", C.c_int), ("gls_stability", C.c_int), ("gls_n2s2_horavg", C.c_int), ("gls_ri_splines", C.c_int),
-        ("gls_p", C.c_double), ("gls_m", C.c_double), ("gls_n", C.c_double), ("gls_cmu0", C.c_double),
-        ("gls_c1", C.c_double), ("gls_c2", C.c_double), ("gls_c3m", C.c_double), ("gls_c3p", C.c_double),
-        ("gls_sigk", C.c_double), ("gls_sigp", C.c_double), ("gls_Kmin", C.c_double), ("gls_Pmin", C.c_double),
-        ("Akk_bak", C.c_double), ("Akp_bak", C.c_double), ("Zos", C.c_double),
-        ("wet_dry", C.c_int), ("point_sources", C.c_int), ("Dcrit", C.c_double),
-        ("atm_press", C.c_int), ("press_compensate", C.c_int), ("ts_mix_stability", C.c_int), ("ts_mix_min_strat", C.c_int),
-    ]
+    _fields_ = _ctypes_fields(STRUCTS["roms_params_t"])
 
 
 class StepIdx(C.Structure):
     """roms_step_idx_t -- mod_stepping.F indices, main3d.F:189-191,597-662."""
-    _fields_ = [(n, C.c_int) for n in
-                "iic ntfirst nstp nnew nrhs kstp krhs knew iif predictor_2d_step".split()]
+    _fields_ = _ctypes_fields(STRUCTS["roms_step_idx_t"])
 
 
 class Fields(C.Structure):

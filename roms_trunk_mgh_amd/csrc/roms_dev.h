@@ -14,9 +14,10 @@
 #include <string>
 #include "roms_hip.h"
 
-// The point-source table SOURCES(ng) (mod_sources.F:56-80) on the device, LuvSrc only (roms_hip_set_sources).  The two
-// face maps (nij ints: 1 + the index of the source at the u- / v-face of the point, 0 elsewhere; the last source of a
-// face wins, as the sequential loops of the reference leave it) let a kernel find "its" source without a search.
+// The point-source table SOURCES(ng) (mod_sources.F:56-80) on the device, LuvSrc and LwSrc (roms_hip_set_sources).  The
+// two face maps and the cell map (nij ints: 1 + the index of the source at the u- / v-face or the centre of the point,
+// 0 elsewhere; the last source of a place wins, as the sequential loops of the reference leave it) let a kernel find
+// "its" source without a search.
 #define ROMS_NWS3 10   // 3-D scratch arrays (the _tile routines' automatic arrays; MPDATA holds Ta of three tracers at a time)
 
 struct RomsSrc {

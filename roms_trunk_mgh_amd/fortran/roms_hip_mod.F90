@@ -25,7 +25,11 @@ MODULE roms_hip_mod
   IMPLICIT NONE
   PRIVATE
 
-  !  mirrors `roms_step_idx_t` of include/roms_hip.h
+  !  limits of the parameter block = ROMS_MAXN, ROMS_MAXNT, ROMS_MAXFAST of include/roms_hip.h (vertical levels,
+  !  tracers, 2*ndtfast): set-up code checks N(ng), NT(ng) and 2*ndtfast(ng) against them
+  INTEGER, PARAMETER, PUBLIC :: ROMS_MAXN = 64, ROMS_MAXNT = 16, ROMS_MAXFAST = 256
+
+  !  mirrors `roms_step_idx_t` of include/roms_hip.h (include/roms_step_idx.def)
   TYPE, BIND(C), PUBLIC :: roms_step_idx_t
     INTEGER(c_int) :: iic, ntfirst
     INTEGER(c_int) :: nstp, nnew, nrhs
@@ -33,9 +37,11 @@ MODULE roms_hip_mod
     INTEGER(c_int) :: iif, predictor_2d_step
   END TYPE roms_step_idx_t
 
-  !  mirror `roms_bounds_t` and `roms_params_t` of include/roms_hip.h field for field (sizes checked against
-  !  roms_abi_sizeof in tests/test_fortran_shim.py): fill one of each from BOUNDS(ng)%...(tile), DOMAIN(ng)%*_Edge(tile)
-  !  and mod_scalars, declare it TARGET and hand c_loc of it to roms_hip_set_bounds / roms_hip_set_params
+  !  mirror `roms_bounds_t` and `roms_params_t` of include/roms_hip.h member for member (include/roms_bounds.def,
+  !  include/roms_params.def, where every member is documented; kind, name and extents of each member are checked
+  !  against those tables, the sizes against roms_abi_sizeof, in tests/test_fortran_shim.py): fill one of each from
+  !  BOUNDS(ng)%...(tile), DOMAIN(ng)%*_Edge(tile) and mod_scalars, declare it TARGET and hand c_loc of it to
+  !  roms_hip_set_bounds / roms_hip_set_params
   TYPE, BIND(C), PUBLIC :: roms_bounds_t
     INTEGER(c_int) :: Lm, Mm, N, NT, NAT
     INTEGER(c_int) :: ntileI, ntileJ, tile, Itile, Jtile
@@ -53,18 +59,18 @@ MODULE roms_hip_mod
   TYPE, BIND(C), PUBLIC :: roms_params_t
     REAL(c_double) :: dt, dtfast, g, rho0, gamma2, lambda
     INTEGER(c_int) :: ndtfast, nfast
-    REAL(c_double) :: weight1(256), weight2(256)
+    REAL(c_double) :: weight1(ROMS_MAXFAST), weight2(ROMS_MAXFAST)
     INTEGER(c_int) :: Vtransform, limit_bstress
     REAL(c_double) :: hc
-    REAL(c_double) :: sc_r(65), Cs_r(65), sc_w(65), Cs_w(65)
-    INTEGER(c_int) :: Hadv(16), Vadv(16)
+    REAL(c_double) :: sc_r(ROMS_MAXN + 1), Cs_r(ROMS_MAXN + 1), sc_w(ROMS_MAXN + 1), Cs_w(ROMS_MAXN + 1)
+    INTEGER(c_int) :: Hadv(ROMS_MAXNT), Vadv(ROMS_MAXNT)
     INTEGER(c_int) :: lbc_west, lbc_east, lbc_south, lbc_north
     INTEGER(c_int) :: nonlin_eos, eminusp
     REAL(c_double) :: R0, T0, S0, Tcoef, Scoef
     INTEGER(c_int) :: uv_adv, uv_cor, uv_vis2, curvgrid, var_rho_2d
     INTEGER(c_int) :: ts_dif2, mix_geo_ts, mix_s_ts, salinity, lmd_nonlocal, solar_source
     INTEGER(c_int) :: splines_vdiff, splines_vvisc
-    REAL(c_double) :: Akt_bak(16), Akv_bak
+    REAL(c_double) :: Akt_bak(ROMS_MAXNT), Akv_bak
     REAL(c_double) :: swfrac_mu1, swfrac_mu2, swfrac_r1
     INTEGER(c_int) :: uv_drag, mpdata_fast
     REAL(c_double) :: blk_ZQ, blk_ZT, blk_ZW
@@ -79,7 +85,10 @@ MODULE roms_hip_mod
     INTEGER(c_int) :: gls_mixing, gls_stability, gls_n2s2_horavg, gls_ri_splines
     REAL(c_double) :: gls_p, gls_m, gls_n, gls_cmu0, gls_c1, gls_c2, gls_c3m, gls_c3p, gls_sigk, gls_sigp, gls_Kmin, gls_Pmin
     REAL(c_double) :: Akk_bak, Akp_bak, Zos
-    !  WET_DRY: switch and the critical depth Dcrit (m); point_sources: LuvSrc.or.LwSrc (refused when non-zero)
+    !  WET_DRY: switch and the critical depth Dcrit (m); point_sources = MERGE(1, 0, LuvSrc(ng)) + MERGE(2, 0, LwSrc(ng))
+    !  (bit 0: transport through u- / v-faces, Dsrc = 0 / 1; bit 1: volume influx at cell centres, Dsrc = 2 -- the free
+    !  surface in step2d, omega, the tracer in step3d_t); with either bit the entries need the table of
+    !  roms_hip_set_sources
     INTEGER(c_int) :: wet_dry, point_sources
     REAL(c_double) :: Dcrit
     !  ATM_PRESS: Pair (mb) in the baroclinic pressure gradient
@@ -279,8 +288,8 @@ MODULE roms_hip_mod
       IMPORT :: c_int, roms_step_idx_t
       TYPE(roms_step_idx_t), INTENT(in) :: s
     END FUNCTION
-    !  LuvSrc: SOURCES(ng) of mod_sources.F (Isrc, Jsrc, Dsrc, Qbar, Qsrc, Tsrc) and LtracerSrc(:,ng) as 0 / 1;
-    !  after every set_data that changes them
+    !  LuvSrc, LwSrc: SOURCES(ng) of mod_sources.F (Isrc, Jsrc, Dsrc = 0 / 1 / 2, Qbar, Qsrc, Tsrc) and LtracerSrc(:,ng)
+    !  as 0 / 1; after every set_data that changes them
     INTEGER(c_int) FUNCTION roms_hip_set_sources (Nsrc, Isrc, Jsrc, Dsrc, Qbar, Qsrc, Tsrc, LtracerSrc)            &
    &                        BIND(C, name='roms_hip_set_sources')
       IMPORT :: c_int, c_double

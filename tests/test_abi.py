@@ -1,9 +1,11 @@
 """CPU: the C-ABI library loads without a GPU and exports every symbol
 include/roms_hip.h declares; struct layouts match the ctypes mirror; the HIP
-path fails loudly (no fallback) when no device is present."""
+path fails loudly (no fallback) when no device is present.  The three structs of the boundary are compared member
+for member (offset, size, type) and the enum mirrors value for value with what a C compiler makes of the header."""
 import ctypes
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -34,6 +36,85 @@ def test_struct_layouts_match():
     import oracle
     abi.check_abi(oracle.lib())
     assert len(abi.FIELDS) == len(set(n for n, _, _ in abi.FIELDS))
+
+
+_STRUCTS = [("roms_bounds_t", "roms_bounds.def", abi.Bounds), ("roms_params_t", "roms_params.def", abi.Params),
+            ("roms_step_idx_t", "roms_step_idx.def", abi.StepIdx)]
+
+
+def test_member_offsets_match_the_c_compiler(tmp_path):
+    """A C program that includes roms_hip.h expands the member tables into offsetof / sizeof of every member of the
+    three structs; name, offset, size and element type equal those of the ctypes classes, in order.  The sizes are
+    asserted literally: a layout change cannot pass by changing both sides at once.  The same program prints every
+    constant abi.py parsed out of the header (limits, enumerators)."""
+    sections = "".join(f"""
+  printf("struct {s} %zu\\n", sizeof({s}));
+#define S {s}
+#include "{d}"
+#undef S""" for s, d, _ in _STRUCTS)
+    consts = "".join(f'  printf("const {n} %d\\n", (int){n});\n' for n in abi.CONSTANTS)
+    (tmp_path / "off.c").write_text(f"""#include <stddef.h>
+#include <stdio.h>
+#include "roms_hip.h"
+#define ROMS_MEMBER(type, name) printf(#type " " #name " %zu %zu\\n", offsetof(S, name), sizeof(((S *)0)->name));
+#define ROMS_MEMBER_A(type, name, n) ROMS_MEMBER(type, name)
+#define ROMS_MEMBER_A2(type, name, n1, n2) ROMS_MEMBER(type, name)
+int main(void)
+{{{sections}
+{consts}  return 0;
+}}
+""")
+    r = subprocess.run(["cc", "-std=c11", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), "off.c", "-o", "off"],
+                       cwd=tmp_path, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    out = subprocess.run([str(tmp_path / "off")], capture_output=True, text=True, check=True).stdout.splitlines()
+    got, sizes, consts = {}, {}, {}
+    for line in out:
+        w = line.split()
+        if w[0] == "struct":
+            cur = got.setdefault(w[1], [])
+            sizes[w[1]] = int(w[2])
+        elif w[0] == "const":
+            consts[w[1]] = int(w[2])
+        else:
+            cur.append((w[0], w[1], int(w[2]), int(w[3])))
+    assert consts == abi.CONSTANTS and len(consts) >= 50
+    assert sizes == {"roms_bounds_t": 252, "roms_params_t": 7376, "roms_step_idx_t": 40}
+    n_members = 0
+    for s, _, cls in _STRUCTS:
+        want = []
+        for name, t in cls._fields_:
+            f = getattr(cls, name)
+            while hasattr(t, "_length_"):
+                t = t._type_
+            want.append(({ctypes.c_int: "int", ctypes.c_double: "double"}[t], name, f.offset, f.size))
+        assert [(t, abi.py_name(n), o, z) for t, n, o, z in got[s]] == want, s
+        assert ctypes.sizeof(cls) == sizes[s]
+        n_members += len(want)
+    print(f"{n_members} members, sizeof = {sizes}")
+    assert n_members == 163
+    assert abi.Bounds._names == [n for _, n, _ in abi.STRUCTS["roms_bounds_t"]] and "lambda_" in dict(abi.Params._fields_)
+
+
+def test_enum_mirrors_equal_the_header():
+    """abi.ADV, PGF, GLS_STAB, KINDS, LBV, LBS and the LBC_* constants carry the values of the enumerators of
+    roms_hip.h (abi.CONSTANTS, which test_member_offsets_match_the_c_compiler checks against the C compiler), and
+    no enumerator is left without its mirror."""
+    def enum(prefix):
+        return {n[len(prefix):]: v for n, v in abi.CONSTANTS.items() if n.startswith(prefix)}
+    assert {k.upper(): v for k, v in abi.ADV.items()} == enum("ADV_") and len(abi.ADV) == 8
+    assert abi.PGF == enum("PGF_") and len(abi.PGF) == 4
+    assert abi.GLS_STAB == enum("GLS_") and len(abi.GLS_STAB) == 4
+    assert {k: i for i, k in enumerate(abi.KINDS)} == {"K_" + k: v for k, v in enum("K_").items()} and len(abi.KINDS) == 12
+    lbv = enum("LBV_")
+    assert lbv.pop("COUNT") == abi.LBV_COUNT == len(abi.LBV) == 6
+    assert {k.upper(): v for k, v in abi.LBV.items()} == lbv
+    assert {k.upper(): v for k, v in abi.LBS.items()} == enum("LBS_") and len(abi.LBS) == 4
+    lbc = enum("LBC_")
+    for name in ("PERIODIC", "CLOSED", "GRADIENT", "CLAMPED", "CHAPMAN_IMPLICIT", "FLATHER", "RADIATION"):
+        assert getattr(abi, "LBC_" + name) == lbc[name], name
+    assert sorted(abi.LBC.values()) == sorted(lbc.values()) == list(range(11))
+    assert (abi.ROMS_MAXN, abi.ROMS_MAXNT, abi.ROMS_MAXFAST) == (64, 16, 256)
 
 
 @pytest.mark.skipif(torch.cuda.is_available(), reason="needs a box WITHOUT a GPU")
