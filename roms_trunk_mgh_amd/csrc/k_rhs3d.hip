@@ -17,8 +17,6 @@
 
 namespace {
 
-#define TP (BLK_X + 4)
-#define TJ (BLK_Y + 4)
 #define Gadv (-0.25)
 
 struct T3 {
@@ -28,9 +26,6 @@ struct T3 {
   bool s_edge, n_edge, w_edge, e_edge;
   __device__ __forceinline__ int at(int i, int j) const { return (i - i0) + (j - j0) * TP; }
 };
-
-__device__ __forceinline__ double d2x(const double *f, int a) { return f[a - 1] - 2.0 * f[a] + f[a + 1]; }
-__device__ __forceinline__ double d2y(const double *f, int a) { return f[a - TP] - 2.0 * f[a] + f[a + TP]; }
 
 __device__ __forceinline__ int ex_uxx(const T3 &L, int i) {           // rhs3d.F:668-685
   if (L.w_edge && i == L.Istr) return L.Istr + 1;

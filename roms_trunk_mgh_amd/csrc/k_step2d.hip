@@ -2,70 +2,42 @@
 // (ROMS/Nonlinear/step2d_LF_AM3.h:137-2528: leap-frog predictor / Adams-Moulton
 // corrector) and the LOOP_2D sequencing of main3d.F:592-700.
 //
-// Inside LOOP_2D a step2d call is ONE launch of k2d_mom_lds<true> (k_step2d_mom.hip:
-// free surface, fast-time averages and momentum together) plus, on several tiles, one
-// batched halo exchange.  The kernels of this file serve the calls that cannot take that
-// route -- a stand-alone roms_hip_step2d on several tiles, and the last predictor of the
-// loop, which only finishes the averages:
-//   k2d_flux   Drhs, DUon, DVom two points into the halo (:509-544)
-//   k2d_zeta   fast-time averaging (:614-682) and the free-surface step
-//              (:770-868): zeta(knew), rzeta(krhs); zeta_new and zwrk go to
-//              device scratch on the extended range so the momentum kernel can
-//              use them at i-1 / j-1 without another exchange
-// followed by k2d_mom_lds<false> with the reference's boundary-condition and halo calls
-// in between.  The reference's ~25 private (IminS:ImaxS,JminS:JmaxS) work arrays become
-// registers / LDS; only DUon, DVom, zeta_new, zwrk live in device scratch.
-#include "roms_dev.h"
+// Inside LOOP_2D, with closed or periodic edges and none of UV_VIS4, WET_DRY and point sources, a step2d call is ONE
+// launch of the fused k2d_mom_lds<true> (k_step2d_mom.hip: free surface, fast-time averages and momentum together,
+// zeta_new and zwrk kept in LDS) plus, on several tiles, one batched halo exchange.  The kernels of this file serve
+// the other calls:
+//   k2d_avg_last  the last predictor of the loop on one E-W periodic tile, which only finishes the fast-time averages
+//   k2d_flux      DUon, DVom two points into the halo (:509-544)
+//   k2d_zeta      fast-time averaging (:614-682) and the free-surface step (:770-868): zeta(knew), rzeta(krhs);
+//                 zeta_new and zwrk go to device scratch on the extended range so that the momentum kernel can use
+//                 them at i-1 / j-1 without another exchange
+// the last two followed by k2d_mom_lds<false>, with the reference's boundary-condition and halo calls in between
+// (step2d_impl).  The point formulas shared with the fused kernel are in step2d_common.h.  The reference's ~25 private
+// (IminS:ImaxS,JminS:JmaxS) work arrays become registers / LDS; only DUon, DVom, zeta_new, zwrk live in device scratch.
+#include "step2d_common.h"
 #include <cstdlib>
 #include <map>
 
 int roms_entry_check(const char *name);
 int roms_launch_step2d_visc4(int krhs);      // k_uv3dmix2.hip
-int roms_launch_k2d_mom_lds(const int *s10, const double *DUon, const double *DVom, const double *zeta_new,
-                            const double *zwrk, double *DUnext = nullptr, double *DVnext = nullptr);   // k_step2d_mom.hip
 
 namespace {
-
-struct S2 {
-  int krhs, kstp, knew, nstp, nnew, iif, iic, ntfirst, predictor;
-  int sm;   // 1 = single tile, E-W periodic: kernels cover the whole allocated tile and every
-            // ghost point is computed from its SOURCE point (periodic image in i, wall mirror in
-            // j), which reproduces "compute interior, apply zetabc/u2dbc/v2dbc, periodic copy"
-            // bit for bit without the extra launches of exchange_*2d_tile and the 2-D BCs.
-};
-
-__device__ __forceinline__ int wrap_i(const roms_bounds_t &b, int i)
-{
-  return (i < 1) ? i + b.Lm : ((i > b.Lm) ? i - b.Lm : i);
-}
-
-__device__ __forceinline__ void zeta_point(const RomsDev *__restrict__ c, const S2 &s, const double rhs,
-                                           double *__restrict__ zeta_new, double *__restrict__ zwrk, long a, long o,
-                                           bool write_scratch, bool write_zeta, bool write_rzeta, long nij, long ni);
 
 __global__ void __launch_bounds__(BLK_X *BLK_Y)
 k2d_flux(const RomsDev *__restrict__ c, S2 s, double *__restrict__ DUon, double *__restrict__ DVom)
 {
   DEV_PROLOGUE(c)
-  const int i0 = s.sm ? b.LBi : b.IstrU - 2, i1 = s.sm ? (b.Lm + b.NghostPoints) : b.Iendp2;
-  const int i = i0 + blockIdx.x * BLK_X + threadIdx.x;
+  const int i = b.IstrU - 2 + blockIdx.x * BLK_X + threadIdx.x;
   const int j = b.JstrV - 2 + blockIdx.y * BLK_Y + threadIdx.y;
-  if (i > i1 || j > b.Jendp2) return;
-  const int is = s.sm ? wrap_i(b, i) : i;
+  if (i > b.Iendp2 || j > b.Jendp2) return;
   const gcd_t zeta = (gcd_t)(c->F.zeta + (long)(s.krhs - 1) * nij);
   const gcd_t h = (gcd_t)(c->F.h);
-  const long a = I2(is, j), o = I2(i, j);
+  const long a = I2(i, j);
   const double Drhs = zeta[a] + h[a];
-  if (s.sm || i >= b.IstrU - 1) {
-    const double cff = 0.5 * GF(on_u)[a];
-    const double cff1 = cff * (Drhs + (zeta[a - 1] + h[a - 1]));
-    DUon[o] = GF(ubar)[a + (long)(s.krhs - 1) * nij] * cff1;
-  }
-  if (j >= b.JstrV - 1) {
-    const double cff = 0.5 * GF(om_v)[a];
-    const double cff1 = cff * (Drhs + (zeta[a - ni] + h[a - ni]));
-    DVom[o] = GF(vbar)[a + (long)(s.krhs - 1) * nij] * cff1;
-  }
+  if (i >= b.IstrU - 1)
+    DUon[a] = flux_u(GF(ubar)[a + (long)(s.krhs - 1) * nij], GF(on_u)[a], Drhs, zeta[a - 1] + h[a - 1]);
+  if (j >= b.JstrV - 1)
+    DVom[a] = flux_v(GF(vbar)[a + (long)(s.krhs - 1) * nij], GF(om_v)[a], Drhs, zeta[a - ni] + h[a - ni]);
 }
 
 __global__ void __launch_bounds__(BLK_X *BLK_Y)
@@ -81,165 +53,48 @@ k2d_zeta(const RomsDev *__restrict__ c, S2 s, const double *__restrict__ DUon, c
   if (i > b.IendR || j > b.JendR) return;
   const roms_params_t &p = c->p;
   const long a = I2(i, j);
-  const int iif = s.iif, nfast = p.nfast;
-  const gcd_t zk = (gcd_t)(c->F.zeta + (long)(s.krhs - 1) * nij);
   // ---- fast-time averaging, :614-682 ----
-  const bool inR = i >= b.IstrR && j >= b.JstrR;
-  if (inR) {
+  if (i >= b.IstrR && j >= b.JstrR) {
     const bool inU = i >= b.Istr, inV = j >= b.Jstr;
-    if (s.predictor) {
-      if (iif == 1) {
-        const double cff2 = (-1.0 / 12.0) * p.weight2[iif];
-        GF(Zt_avg1)[a] = 0.0;
-        if (inU) { GF(DU_avg1)[a] = 0.0; GF(DU_avg2)[a] = cff2 * DUon[a]; }
-        if (inV) { GF(DV_avg1)[a] = 0.0; GF(DV_avg2)[a] = cff2 * DVom[a]; }
-      } else {
-        const double cff1 = p.weight1[iif - 2];
-        const double cff2 = (8.0 / 12.0) * p.weight2[iif - 1] - (1.0 / 12.0) * p.weight2[iif];
-        GF(Zt_avg1)[a] = GF(Zt_avg1)[a] + cff1 * zk[a];
-        if (inU) {
-          GF(DU_avg1)[a] = GF(DU_avg1)[a] + cff1 * DUon[a];
-          GF(DU_avg2)[a] = GF(DU_avg2)[a] + cff2 * DUon[a];
-        }
-        if (inV) {
-          GF(DV_avg1)[a] = GF(DV_avg1)[a] + cff1 * DVom[a];
-          GF(DV_avg2)[a] = GF(DV_avg2)[a] + cff2 * DVom[a];
-        }
-      }
-    } else {
-      const double cff2 = (iif == 1) ? p.weight2[iif - 1] : (5.0 / 12.0) * p.weight2[iif - 1];
-      if (inU) GF(DU_avg2)[a] = GF(DU_avg2)[a] + cff2 * DUon[a];
-      if (inV) GF(DV_avg2)[a] = GF(DV_avg2)[a] + cff2 * DVom[a];
-    }
+    average_point(c, s, a, inU, inV, inU ? DUon[a] : 0.0, inV ? DVom[a] : 0.0, nij);
   }
-  if (iif > nfast) return;
+  if (s.iif > p.nfast) return;
   // ---- free surface, :770-868 ----
+  // on the extended range: the low-side ghost values of zeta(knew) computed here are, bit for bit, what the exchange
+  // delivers later; rzeta(krhs) on the owned points only
   if (i < b.IstrU - 1 || i > b.Iend || j < b.JstrV - 1 || j > b.Jend) return;
-  const bool own = i >= b.Istr && j >= b.Jstr;
+  const bool masking = p.masking != 0, am3z = !(s.iif == 1 || s.predictor);
   const double rhs = (DUon[a] - DUon[a + 1]) + (DVom[a] - DVom[a + ni]);
-  // zeta(knew) is stored on the extended range too: the low-side ghost value computed here is, bit
-  // for bit, what the exchange delivers later
-  zeta_point(c, s, rhs, zeta_new, zwrk, a, a, true, true, own, nij, ni);
+  const double rm = masking ? (double)GF(rmask)[a] : 1.0;
+  double zn, zw;
+  zeta_step(p, s, rhs, GF(pm)[a], GF(pn)[a], GF(zeta)[a + (long)(s.kstp - 1) * nij], GF(zeta)[a + (long)(s.krhs - 1) * nij],
+            am3z ? (double)GF(rzeta)[a + (long)(s.kstp - 1) * nij] : 0.0,
+            am3z ? (double)GF(rzeta)[a + (long)(3 - s.kstp - 1) * nij] : 0.0, rm, masking, zn, zw);
+  zeta_new[a] = zn;
+  zwrk[a] = zw;
+  // WET_DRY && MASKING, :863-866: the shared array (not zeta_new) keeps the total depth of a land cell at Dcrit
+  GF(zeta)[a + (long)(s.knew - 1) * nij] = (p.wet_dry && masking) ? zn + (p.Dcrit - GF(h)[a]) * (1.0 - rm) : zn;
+  if (s.predictor && i >= b.Istr && j >= b.Jstr) GF(rzeta)[a + (long)(s.krhs - 1) * nij] = rhs;
 }
 
-// Source-mapped variant (single tile, E-W periodic, closed N-S walls): one
-// thread per ALLOCATED point.  Thread (i,j) evaluates the free-surface step at
-// its source point (periodic image in i; wall row -> adjacent interior row =
-// the zero-gradient zetabc) and stores at (i,j): zeta(knew), rzeta(krhs),
-// zeta_new and zwrk come out with their ghost points already filled.
+// The last predictor of LOOP_2D (iif = nfast+1) on one E-W periodic tile: it only finishes the fast-time averages,
+// with DUon / DVom evaluated in place.  (Not merged with the averaging half of k2d_zeta: that one reads exchanged
+// fluxes from scratch, and choosing between the two sources would be a new branch per point in both.)
 __global__ void __launch_bounds__(BLK_X *BLK_Y)
-k2d_zeta_sm(const RomsDev *__restrict__ c, S2 s, const double *__restrict__ DUon, const double *__restrict__ DVom,
-            double *__restrict__ zeta_new, double *__restrict__ zwrk)
+k2d_avg_last(const RomsDev *__restrict__ c, S2 s)
 {
   DEV_PROLOGUE(c)
   const int i = b.LBi + blockIdx.x * BLK_X + threadIdx.x;
   const int j = b.LBj + blockIdx.y * BLK_Y + threadIdx.y;
-  if (i > b.Lm + b.NghostPoints || j > b.UBj) return;
-  const roms_params_t &p = c->p;
-  const int iif = s.iif, nfast = p.nfast;
-  const long o = I2(i, j);
-  // DUon / DVom (:509-544): from scratch, or -- when k2d_flux was not launched (DUon == nullptr) --
-  // evaluated in place with the same expression, so no separate flux kernel is needed
-  const gcd_t zkq = (gcd_t)(c->F.zeta + (long)(s.krhs - 1) * nij);
-  const gcd_t hq = (gcd_t)(c->F.h);
-  const gcd_t ubq = (gcd_t)(c->F.ubar + (long)(s.krhs - 1) * nij);
-  const gcd_t vbq = (gcd_t)(c->F.vbar + (long)(s.krhs - 1) * nij);
-  auto du = [&](long q) -> double {
-    if (DUon) return DUon[q];
-    const double cff = 0.5 * GF(on_u)[q];
-    const double cff1 = cff * ((zkq[q] + hq[q]) + (zkq[q - 1] + hq[q - 1]));
-    return ubq[q] * cff1;
-  };
-  auto dv = [&](long q) -> double {
-    if (DVom) return DVom[q];
-    const double cff = 0.5 * GF(om_v)[q];
-    const double cff1 = cff * ((zkq[q] + hq[q]) + (zkq[q - ni] + hq[q - ni]));
-    return vbq[q] * cff1;
-  };
-  // ---- fast-time averaging on the owned ranges only, :614-682 ----
-  if (i >= b.IstrR && i <= b.IendR && j >= b.JstrR && j <= b.JendR) {
-    const gcd_t zk = (gcd_t)(c->F.zeta + (long)(s.krhs - 1) * nij);
-    const bool inU = i >= b.Istr, inV = j >= b.Jstr;
-    if (s.predictor) {
-      if (iif == 1) {
-        const double cff2 = (-1.0 / 12.0) * p.weight2[iif];
-        GF(Zt_avg1)[o] = 0.0;
-        if (inU) { GF(DU_avg1)[o] = 0.0; GF(DU_avg2)[o] = cff2 * du(o); }
-        if (inV) { GF(DV_avg1)[o] = 0.0; GF(DV_avg2)[o] = cff2 * dv(o); }
-      } else {
-        const double cff1 = p.weight1[iif - 2];
-        const double cff2 = (8.0 / 12.0) * p.weight2[iif - 1] - (1.0 / 12.0) * p.weight2[iif];
-        GF(Zt_avg1)[o] = GF(Zt_avg1)[o] + cff1 * zk[o];
-        if (inU) {
-          GF(DU_avg1)[o] = GF(DU_avg1)[o] + cff1 * du(o);
-          GF(DU_avg2)[o] = GF(DU_avg2)[o] + cff2 * du(o);
-        }
-        if (inV) {
-          GF(DV_avg1)[o] = GF(DV_avg1)[o] + cff1 * dv(o);
-          GF(DV_avg2)[o] = GF(DV_avg2)[o] + cff2 * dv(o);
-        }
-      }
-    } else {
-      const double cff2 = (iif == 1) ? p.weight2[iif - 1] : (5.0 / 12.0) * p.weight2[iif - 1];
-      if (inU) GF(DU_avg2)[o] = GF(DU_avg2)[o] + cff2 * du(o);
-      if (inV) GF(DV_avg2)[o] = GF(DV_avg2)[o] + cff2 * dv(o);
-    }
-  }
-  if (iif > nfast) return;
-  // ---- free surface at the source point ----
-  const int is = wrap_i(b, i);
-  int js = j;
-  if (b.south_edge && j == b.Jstr - 1) js = b.Jstr;       // zetabc closed: zero gradient
-  if (b.north_edge && j == b.Jend + 1) js = b.Jend;
-  if (js < b.Jstr || js > b.Jend) return;
-  const long a = I2(is, js);
-  const bool own_row = (js == j);
-  const double rhs = (du(a) - du(a + 1)) + (dv(a) - dv(a + ni));
-  zeta_point(c, s, rhs, zeta_new, zwrk, a, o, own_row, true, own_row, nij, ni);
-}
-
-// One free-surface point: evaluate at index a, store at index o.
-__device__ __forceinline__ void zeta_point(const RomsDev *__restrict__ c, const S2 &s, const double rhs,
-                                           double *__restrict__ zeta_new, double *__restrict__ zwrk, long a, long o,
-                                           bool write_scratch, bool write_zeta, bool write_rzeta, long nij, long ni)
-{
-  const roms_params_t &p = c->p;
-  const int iif = s.iif;
+  if (i < b.IstrR || i > b.IendR || j < b.JstrR || j > b.JendR) return;
+  const long a = I2(i, j);
   const gcd_t zk = (gcd_t)(c->F.zeta + (long)(s.krhs - 1) * nij);
-  const double dtfast = p.dtfast;
-  const gcd_t zs = (gcd_t)(c->F.zeta + (long)(s.kstp - 1) * nij);
-  const double pmn_a = GF(pm)[a], pn_a = GF(pn)[a];
-  double zn, zw;
-  if (iif == 1) {
-    const double cff1 = dtfast;
-    zn = zs[a] + pmn_a * pn_a * cff1 * rhs;
-    if (p.masking) zn = zn * GF(rmask)[a];                      // MASKING, step2d_LF_AM3.h:778
-    zw = 0.5 * (zs[a] + zn);
-  } else if (s.predictor) {
-    const double cff1 = 2.0 * dtfast;
-    const double cff4 = 4.0 / 25.0;
-    const double cff5 = 1.0 - 2.0 * cff4;
-    zn = zs[a] + pmn_a * pn_a * cff1 * rhs;
-    if (p.masking) zn = zn * GF(rmask)[a];                      // :804
-    zw = cff5 * zk[a] + cff4 * (zs[a] + zn);
-  } else {
-    const int ptsk = 3 - s.kstp;
-    const double cff1 = dtfast * 5.0 / 12.0;
-    const double cff2 = dtfast * 8.0 / 12.0;
-    const double cff3 = dtfast * 1.0 / 12.0;
-    const double cff4 = 2.0 / 5.0;
-    const double cff5 = 1.0 - cff4;
-    const double cff = cff1 * rhs;
-    zn = zs[a] + pmn_a * pn_a * (cff + cff2 * GF(rzeta)[a + (long)(s.kstp - 1) * nij] -
-                                 cff3 * GF(rzeta)[a + (long)(ptsk - 1) * nij]);
-    if (p.masking) zn = zn * GF(rmask)[a];                      // :835
-    zw = cff5 * zn + cff4 * zk[a];
-  }
-  if (write_scratch) { zeta_new[o] = zn; zwrk[o] = zw; }
-  // WET_DRY && MASKING, :863-866: the shared array (not zeta_new) keeps the total depth of a land cell at Dcrit
-  if (write_zeta)
-    GF(zeta)[o + (long)(s.knew - 1) * nij] = (p.wet_dry && p.masking) ? zn + (p.Dcrit - GF(h)[a]) * (1.0 - GF(rmask)[a]) : zn;
-  if (write_rzeta && s.predictor) GF(rzeta)[o + (long)(s.krhs - 1) * nij] = rhs;
+  const gcd_t h = (gcd_t)(c->F.h);
+  const bool inU = i >= b.Istr, inV = j >= b.Jstr;
+  const double Drhs = zk[a] + h[a];
+  const double du = inU ? flux_u(GF(ubar)[a + (long)(s.krhs - 1) * nij], GF(on_u)[a], Drhs, zk[a - 1] + h[a - 1]) : 0.0;
+  const double dv = inV ? flux_v(GF(vbar)[a + (long)(s.krhs - 1) * nij], GF(om_v)[a], Drhs, zk[a - ni] + h[a - ni]) : 0.0;
+  average_point(c, s, a, inU, inV, du, dv, nij);
 }
 
 // ---------------------------------------------------------------------------
@@ -403,30 +258,24 @@ int step2d_impl(const roms_step_idx_t *si, bool in_loop)
   double *DUon = g_ctx.hostc.ws2[0], *DVom = g_ctx.hostc.ws2[1];
   double *zeta_new = g_ctx.hostc.ws2[2], *zwrk = g_ctx.hostc.ws2[3];
   const long nij = (long)(b.UBi - b.LBi + 1) * (b.UBj - b.LBj + 1);
-  // Source-mapped fast path: one tile, E-W periodic, closed N-S walls.  Not used on
-  // the first predictor of a step: there the momentum kernel read-modify-writes
-  // rufrc and ru(:,:,0,nstp) at the source points (:1884-2037), which ghost-point
-  // threads would race with.
-  // (the fused kernels apply the closed-wall conditions themselves; open S/N edges take the general path below,
-  // whose boundary conditions are separate launches)
+  // The fused kernel (k2d_mom_lds<true>) applies the closed-wall conditions itself; open S/N edges take the split
+  // path below, whose boundary conditions are separate launches.  So do
+  //   UV_VIS4: the biharmonic term is a pass of its own in front of the momentum kernel
+  //   WET_DRY: the masks are a pass of their own between the averages and the free surface
+  //   LuvSrc / LwSrc: the source faces and cells are launches of their own
   const bool walls = lbc2d_all_closed();
-  // (UV_VIS4: the biharmonic term is a pass of its own in front of the momentum kernel -- general path only)
-  // (WET_DRY: the masks are a pass of their own between the averages and the free surface -- general path only)
-  // (LuvSrc / LwSrc: the source faces and cells are launches of their own -- general path only)
   const bool srcs = (p.point_sources & 3) != 0;
-  const bool sm = b.ntileI * b.ntileJ == 1 && b.EWperiodic && !b.NSperiodic && !g_ctx.loopback && walls && !p.uv_vis4 && !p.wet_dry && !srcs;
-  if (sm) {
-    if (s.iif <= p.nfast) {
-      // ONE launch: free surface, fast-time averages and momentum (k2d_mom_lds<true>)
-      s.sm = 2;
-      return roms_launch_k2d_mom_lds((const int *)&s, nullptr, nullptr, nullptr, nullptr);
-    }
-    // the last predictor of the loop (iif = nfast+1) only finishes the fast-time averages (:614-682);
-    // DUon/DVom are evaluated in place
-    s.sm = 1;
-    hipLaunchKernelGGL(k2d_zeta_sm, grid2d(b.UBi - b.LBi + 1, b.UBj - b.LBj + 1), block2d(), 0, g_ctx.stream,
-                       g_ctx.devc, s, (const double *)nullptr, (const double *)nullptr, zeta_new, zwrk);
-    KERNEL_CHECK("k2d_zeta_sm");
+  const bool fusable = walls && !p.uv_vis4 && !p.wet_dry && !srcs;
+  // One tile, E-W periodic, closed N-S walls: the kernels store the periodic images and the wall rows themselves, so
+  // that no boundary-condition, exchange or flux launch is needed
+  if (fusable && b.ntileI * b.ntileJ == 1 && b.EWperiodic && !b.NSperiodic && !g_ctx.loopback) {
+    s.ew_images = 1;
+    if (s.iif <= p.nfast)     // ONE launch: free surface, fast-time averages and momentum
+      return roms_launch_k2d_mom_lds(s, K2dLaunch::FusedOneTile, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    // the last predictor of the loop (iif = nfast+1) only finishes the fast-time averages (:614-682)
+    hipLaunchKernelGGL(k2d_avg_last, grid2d(b.UBi - b.LBi + 1, b.UBj - b.LBj + 1), block2d(), 0, g_ctx.stream,
+                       g_ctx.devc, s);
+    KERNEL_CHECK("k2d_avg_last");
     if (s.predictor) {
       if ((rc = halo_exchange2d(GT_R, g_ctx.dev[FID_Zt_avg1]))) return rc;
       if ((rc = halo_exchange2d(GT_U, g_ctx.dev[FID_DU_avg1]))) return rc;
@@ -434,9 +283,9 @@ int step2d_impl(const roms_step_idx_t *si, bool in_loop)
     }
     return 0;
   }
-  // General path (several tiles; first predictor of a step on one tile).  Messages per call: inside
-  // LOOP_2D ONE fused exchange at the end (rzeta, zeta, ubar, vbar of this call + DUon, DVom of the
-  // next one, whose krhs is this call's knew); a stand-alone call exchanges its own fluxes first.
+  // Every other configuration.  Messages per call: inside LOOP_2D on several tiles ONE fused exchange at the end
+  // (rzeta, zeta, ubar, vbar of this call + DUon, DVom of the next one, whose krhs is this call's knew); any other
+  // call exchanges its own fluxes first.
   const bool multi = b.ntileI * b.ntileJ > 1 || g_ctx.loopback;
   // DUon/DVom live in two scratch pairs: the fused kernel reads one (exchanged fluxes of this level)
   // while it writes the other (own-point fluxes of the next level)
@@ -453,10 +302,9 @@ int step2d_impl(const roms_step_idx_t *si, bool in_loop)
     if ((rc = halo_batch_end())) return rc;
   }
   g_flux_ready = false;
-  if (in_loop && multi && walls && s.iif <= p.nfast && !p.uv_vis4 && !p.wet_dry && !srcs) {
+  if (in_loop && multi && fusable && s.iif <= p.nfast) {
     // ONE compute launch + ONE exchange per call
-    s.sm = 3;
-    if ((rc = roms_launch_k2d_mom_lds((const int *)&s, DUon, DVom, nullptr, nullptr, DUnext, DVnext))) return rc;
+    if ((rc = roms_launch_k2d_mom_lds(s, K2dLaunch::FusedTiles, DUon, DVom, nullptr, nullptr, DUnext, DVnext))) return rc;
     halo_batch_begin();
     if (s.predictor) halo_exchange2d(GT_R, g_ctx.dev[FID_rzeta] + (long)(s.krhs - 1) * nij);
     halo_exchange2d(GT_R, g_ctx.dev[FID_zeta] + (long)(s.knew - 1) * nij);
@@ -490,7 +338,7 @@ int step2d_impl(const roms_step_idx_t *si, bool in_loop)
   }
   if ((rc = bc_zeta(s.knew, si))) return rc;
   if (p.uv_vis4 && (rc = roms_launch_step2d_visc4(s.krhs))) return rc;
-  if ((rc = roms_launch_k2d_mom_lds((const int *)&s, DUon, DVom, zeta_new, zwrk))) return rc;
+  if ((rc = roms_launch_k2d_mom_lds(s, K2dLaunch::Split, DUon, DVom, zeta_new, zwrk, nullptr, nullptr))) return rc;
   if ((rc = bc_u2d(s.knew, si))) return rc;
   if ((rc = bc_v2d(s.knew, si))) return rc;
   if ((p.point_sources & 1) && g_ctx.hostc.src.n > 0) {        // LuvSrc, step2d_LF_AM3.h:2484-2502

@@ -3,25 +3,21 @@
 // (:939-1019), 4th-order centred advection (:1079-1283), Coriolis (:1291-1325),
 // curvilinear terms (:1333-1382), harmonic viscosity (:1394-1471), 2D<->3D coupling
 // (:1884-2065) and the ubar/vbar step (:2098-2255).  The five fields the wide
-// stencils read -- ubar(krhs),
-// vbar(krhs), DUon, DVom and the total depth Drhs = zeta(krhs)+h -- are staged
-// once per workgroup into LDS with their 2-point C-grid halo (68 x 8 doubles
-// per field for a 64 x 4 workgroup, 21.8 KB).  The 4th-order advection,
-// Coriolis, curvilinear and viscous terms then read LDS instead of issuing
-// ~100 L2 requests per point.
+// stencils read -- ubar(krhs), vbar(krhs), DUon, DVom and the total depth
+// Drhs = zeta(krhs)+h -- are staged once per workgroup into LDS with their 2-point
+// C-grid halo (68 x 8 doubles per field for a 64 x 4 workgroup, 21.8 KB).  The
+// 4th-order advection, Coriolis, curvilinear and viscous terms then read LDS
+// instead of issuing ~100 L2 requests per point.
 //
-// Source mapping (single tile, E-W periodic, closed N-S walls): threads cover
-// i = LBi:UBi; ghost columns evaluate at their periodic image (the tile is
-// loaded through the same wrap, so neighbour relations are preserved), and the
-// wall-adjacent rows also store the u2dbc / v2dbc closed-wall values, so no
-// boundary-condition or periodic-copy launch follows.
-#include "roms_dev.h"
+// One thread per interior point (Istr:Iend, Jstr:Jend).  FUSED, the kernel is a whole
+// step2d call: it also does the free-surface step and the fast-time averaging
+// (formulas of step2d_common.h), stores the closed-wall values of zetabc / u2dbc /
+// v2dbc on the wall rows and -- on one E-W periodic tile, whose LDS tiles are loaded
+// through the periodic wrap -- the periodic images of the columns next to the seam,
+// so that no boundary-condition or periodic-copy launch follows.
+#include "step2d_common.h"
 
 namespace {
-
-struct S2 {
-  int krhs, kstp, knew, nstp, nnew, iif, iic, ntfirst, predictor, sm;
-};
 
 // Row-uniform metrics.  On a zonally uniform grid (a Cartesian channel, a longitude-latitude grid: every
 // configuration of BASELINE.json) the fifteen metric arrays below do not depend on i.  roms_rowm_prepare() checks
@@ -55,20 +51,15 @@ struct Met {
 #define MT(name, q, jr) met.get((gcd_t)c->F.name, RM_##name, (q), (jr))
 #define HT(name, q, jr) meth.get((gcd_t)c->F.name, RM_##name, (q), (jr))
 
-#define TP (BLK_X + 4)       // tile pitch (i)
-#define TJ (BLK_Y + 4)       // tile rows  (j)
 #define C6 (1.0 / 6.0)
 
-struct T2 {                  // LDS tiles, addressed with TARGET coordinates
+struct T2 {                  // LDS tiles, addressed with grid coordinates
   const double *ub, *vb, *DU, *DV, *D;
-  int i0, j0;                // target coordinates of tile element (0,0)
+  int i0, j0;                // grid coordinates of tile element (0,0)
   int Istr, Iend, Jstr, Jend;
   bool s_edge, n_edge, w_edge, e_edge;
   __device__ __forceinline__ int at(int i, int j) const { return (i - i0) + (j - j0) * TP; }
 };
-
-__device__ __forceinline__ double d2x(const double *f, int a) { return f[a - 1] - 2.0 * f[a] + f[a + 1]; }
-__device__ __forceinline__ double d2y(const double *f, int a) { return f[a - TP] - 2.0 * f[a] + f[a + TP]; }
 
 __device__ __forceinline__ double UFx2(const T2 &m, int i, int j)      // :1079-1125
 {
@@ -107,85 +98,11 @@ __device__ __forceinline__ double VFe2(const T2 &m, int i, int j)      // :1207-
          (m.DV[a] + m.DV[a + TP] - C6 * (d2y(m.DV, m.at(i, ja)) + d2y(m.DV, m.at(i, jb))));
 }
 
-__device__ __forceinline__ int wrap_i(const roms_bounds_t &b, int i)
-{
-  return (i < 1) ? i + b.Lm : ((i > b.Lm) ? i - b.Lm : i);
-}
-
-// One free-surface point (step2d_LF_AM3.h:770-868) evaluated at source index a: the new free surface zn
-// and the time-weighted zw the pressure gradient uses.  Same expressions as zeta_point (k_step2d.hip).
-__device__ __forceinline__ void zeta_eval(const RomsDev *__restrict__ c, const S2 &s, const double rhs, long a, long nij,
-                                          const double pmn_a, const double pn_a, double &zn, double &zw)
-{
-  const roms_params_t &p = c->p;
-  const gcd_t zk = (gcd_t)(c->F.zeta + (long)(s.krhs - 1) * nij);
-  const gcd_t zs = (gcd_t)(c->F.zeta + (long)(s.kstp - 1) * nij);
-  const double dtfast = p.dtfast;
-  if (s.iif == 1) {
-    const double cff1 = dtfast;
-    zn = zs[a] + pmn_a * pn_a * cff1 * rhs;
-    if (p.masking) zn = zn * GF(rmask)[a];                      // MASKING, step2d_LF_AM3.h:778
-    zw = 0.5 * (zs[a] + zn);
-  } else if (s.predictor) {
-    const double cff1 = 2.0 * dtfast;
-    const double cff4 = 4.0 / 25.0;
-    const double cff5 = 1.0 - 2.0 * cff4;
-    zn = zs[a] + pmn_a * pn_a * cff1 * rhs;
-    if (p.masking) zn = zn * GF(rmask)[a];                      // :804
-    zw = cff5 * zk[a] + cff4 * (zs[a] + zn);
-  } else {
-    const int ptsk = 3 - s.kstp;
-    const double cff1 = dtfast * 5.0 / 12.0;
-    const double cff2 = dtfast * 8.0 / 12.0;
-    const double cff3 = dtfast * 1.0 / 12.0;
-    const double cff4 = 2.0 / 5.0;
-    const double cff5 = 1.0 - cff4;
-    const double cff = cff1 * rhs;
-    zn = zs[a] + pmn_a * pn_a * (cff + cff2 * GF(rzeta)[a + (long)(s.kstp - 1) * nij] -
-                                 cff3 * GF(rzeta)[a + (long)(ptsk - 1) * nij]);
-    if (p.masking) zn = zn * GF(rmask)[a];                      // :835
-    zw = cff5 * zn + cff4 * zk[a];
-  }
-}
-
-// The same with the point's inputs already in registers (the fused kernel issues these loads before its first barrier):
-// zs_a = zeta(kstp), zk_a = zeta(krhs), rz_k / rz_p = rzeta(kstp) / rzeta(ptsk), rm = rmask (1 without MASKING)
-__device__ __forceinline__ void zeta_eval_pre(const roms_params_t &p, const S2 &s, const double rhs, const double pmn_a,
-                                              const double pn_a, const double zs_a, const double zk_a, const double rz_k,
-                                              const double rz_p, const double rm, const bool masking, double &zn,
-                                              double &zw)
-{
-  const double dtfast = p.dtfast;
-  if (s.iif == 1) {
-    const double cff1 = dtfast;
-    zn = zs_a + pmn_a * pn_a * cff1 * rhs;
-    if (masking) zn = zn * rm;
-    zw = 0.5 * (zs_a + zn);
-  } else if (s.predictor) {
-    const double cff1 = 2.0 * dtfast;
-    const double cff4 = 4.0 / 25.0;
-    const double cff5 = 1.0 - 2.0 * cff4;
-    zn = zs_a + pmn_a * pn_a * cff1 * rhs;
-    if (masking) zn = zn * rm;
-    zw = cff5 * zk_a + cff4 * (zs_a + zn);
-  } else {
-    const double cff1 = dtfast * 5.0 / 12.0;
-    const double cff2 = dtfast * 8.0 / 12.0;
-    const double cff3 = dtfast * 1.0 / 12.0;
-    const double cff4 = 2.0 / 5.0;
-    const double cff5 = 1.0 - cff4;
-    const double cff = cff1 * rhs;
-    zn = zs_a + pmn_a * pn_a * (cff + cff2 * rz_k - cff3 * rz_p);
-    if (masking) zn = zn * rm;
-    zw = cff5 * zn + cff4 * zk_a;
-  }
-}
-
-// FUSED (single tile, source-mapped calls only): the free-surface step and the fast-time averaging
-// of k2d_zeta_sm are done here as well -- zeta_new and zwrk are evaluated from the staged DUon/DVom
-// tiles for the (65 x 5) points this workgroup's momentum stencil touches and kept in LDS, so one
-// step2d call is ONE launch and the zeta_new/zwrk scratch round trip disappears.
-// WET (general path only): the WET_DRY blocks -- pmask_wet in the viscous stress (:1436-1438), the wet/dry factor of
+// FUSED: the free-surface step and the fast-time averaging are done here as well -- zeta_new and zwrk are evaluated
+// from the staged DUon/DVom tiles for the (65 x 5) points this workgroup's momentum stencil touches and kept in LDS,
+// so one step2d call is ONE launch and the zeta_new/zwrk scratch round trip disappears.  On one E-W periodic tile
+// (S2::ew_images) DUon/DVom are evaluated in place while staging; on several tiles they arrive exchanged.
+// WET (split path only): the WET_DRY blocks -- pmask_wet in the viscous stress (:1436-1438), the wet/dry factor of
 // the new velocity, of the right-hand side and, in the first predictor, of rufrc / ru(:,:,0,nstp) (:2123-2135 ...).
 template <bool FUSED, bool ROWM = false, bool ROWH = false, bool WET = false>
 __global__ void __launch_bounds__(BLK_X *BLK_Y)
@@ -197,26 +114,21 @@ k2d_mom_lds(const RomsDev *__restrict__ c, S2 s, const double *__restrict__ DUon
   const roms_params_t &p = c->p;
   const Met<ROWM> met{(ccd_t)c->rowm, (int)nj, LBj};
   const Met<ROWH> meth{(ccd_t)c->rowm, (int)nj, LBj};
-  // DUnext != nullptr (FUSED on several tiles, inside LOOP_2D): the closed-wall conditions are applied here
-  // and DUon/DVom of the NEXT call (level knew) are left in DUnext/DVnext on the points this tile owns,
+  // FUSED on one tile or (DUnext != nullptr) on several tiles inside LOOP_2D: the closed-wall conditions are applied
+  // here.  With DUnext, DUon/DVom of the NEXT call (level knew) are left in DUnext/DVnext on the points this tile owns,
   // so that one exchange per call moves everything the next call needs
-  const bool inline_bc = s.sm || DUnext != nullptr;
   __shared__ double sU[TJ * TP], sV[TJ * TP], sDU[TJ * TP], sDV[TJ * TP], sD[TJ * TP];
   __shared__ double sZn[FUSED ? TJ * TP : 1], sZw[FUSED ? TJ * TP : 1];
-  // FUSED on one tile: threads cover the interior only and the owner of a column also stores its
-  // periodic images (columns Lm+1.. and ..0), instead of ghost threads repeating the work of their
-  // source column -- no nearly empty 33rd workgroup column, and the first predictor of a step (it
-  // read-modify-writes rufrc and ru(:,:,0,nstp)) has no reader/writer race any more
-  const bool img = FUSED && s.sm;
-  const bool ghost_threads = s.sm && !img;
-  const int ibase = ghost_threads ? b.LBi : b.Istr;
-  const int ilast = ghost_threads ? (b.Lm + b.NghostPoints) : b.Iend;
+  // one tile, E-W periodic: the thread that owns a column next to the seam also stores its periodic images (columns
+  // Lm+1.. and ..0), so that no exchange follows
+  const bool img = FUSED && s.ew_images;
+  const bool inline_bc = img || DUnext != nullptr;
   const Blk XB = xcd_block();
-  const int it0 = ibase + XB.x * BLK_X, j0 = b.Jstr + XB.y * BLK_Y;
+  const int i0 = b.Istr + XB.x * BLK_X, j0 = b.Jstr + XB.y * BLK_Y;
   // a wave is one row of the tile (BLK_X = 64 = the wave size): its row index is a scalar, so that the row-table
   // metrics of the momentum phase (MT / HT with row j, j-1, j+1) are scalar loads, not 64 lanes reading one address
   static_assert(BLK_X == 64, "one wave per tile row");
-  const int it = it0 + threadIdx.x, j = j0 + __builtin_amdgcn_readfirstlane(threadIdx.y);
+  const int i = i0 + threadIdx.x, j = j0 + __builtin_amdgcn_readfirstlane(threadIdx.y);
   const gcd_t ubk = (gcd_t)(c->F.ubar + (long)(s.krhs - 1) * nij);
   const gcd_t vbk = (gcd_t)(c->F.vbar + (long)(s.krhs - 1) * nij);
   const gcd_t zk = (gcd_t)(c->F.zeta + (long)(s.krhs - 1) * nij);
@@ -240,8 +152,8 @@ k2d_mom_lds(const RomsDev *__restrict__ c, S2 s, const double *__restrict__ DUon
       z_zs[r] = 0.0; z_zk[r] = 0.0; z_rk[r] = 0.0; z_rp[r] = 0.0; z_rm[r] = 1.0;
       if (q < ZW * ZH) {
         const int li = 1 + q % ZW, lj = 1 + q / ZW;
-        int gi = it0 - 2 + li, gj = j0 - 2 + lj;
-        if (s.sm) gi = wrap_i(b, gi);
+        int gi = i0 - 2 + li, gj = j0 - 2 + lj;
+        if (img) gi = wrap_i(b, gi);
         else gi = gi < b.LBi ? b.LBi : (gi > b.UBi ? b.UBi : gi);
         gj = gj < b.LBj ? b.LBj : (gj > b.UBj ? b.UBj : gj);
         const long gq = I2(gi, gj);
@@ -254,9 +166,8 @@ k2d_mom_lds(const RomsDev *__restrict__ c, S2 s, const double *__restrict__ DUon
         if (p.masking) z_rm[r] = GF(rmask)[gq];
       }
     }
-    if (it <= ilast && j <= b.Jend) {
-      const int isrc = ghost_threads ? wrap_i(b, it) : it;
-      const long a = I2(isrc, j), o = I2(it, j);
+    if (i <= b.Iend && j <= b.Jend) {
+      const long a = I2(i, j);
       const gcd_t rhoA = (gcd_t)(c->F.rhoA), rhoS = (gcd_t)(c->F.rhoS);
       q_rhoA0 = rhoA[a]; q_rhoS0 = rhoS[a]; q_rhoAw = rhoA[a - 1]; q_rhoSw = rhoS[a - 1];
       q_rhoAs = rhoA[a - ni]; q_rhoSs = rhoS[a - ni];
@@ -267,19 +178,18 @@ k2d_mom_lds(const RomsDev *__restrict__ c, S2 s, const double *__restrict__ DUon
         q_rubk = GF(rubar)[a + (long)(s.kstp - 1) * nij]; q_rubp = GF(rubar)[a + (long)(3 - s.kstp - 1) * nij];
         q_rvbk = GF(rvbar)[a + (long)(s.kstp - 1) * nij]; q_rvbp = GF(rvbar)[a + (long)(3 - s.kstp - 1) * nij];
       }
-      if (!(s.predictor && s.iif == 1)) {              // the running sums of the fast-time averages (:614-682)
-        q_DU2 = GF(DU_avg2)[o]; q_DV2 = GF(DV_avg2)[o];
-        if (s.predictor) { q_Zt = GF(Zt_avg1)[o]; q_DU1 = GF(DU_avg1)[o]; q_DV1 = GF(DV_avg1)[o]; q_zkr = zk[o]; }
-      }
+      // the running sums of the fast-time averages (:614-682)
+      if (avg_reads_sums2(s)) { q_DU2 = GF(DU_avg2)[a]; q_DV2 = GF(DV_avg2)[a]; }
+      if (avg_reads_sums1(s)) { q_Zt = GF(Zt_avg1)[a]; q_DU1 = GF(DU_avg1)[a]; q_DV1 = GF(DV_avg1)[a]; q_zkr = zk[a]; }
     }
   }
-  // ---- stage the stencil fields (target coordinates it0-2.., j0-2..) ----
+  // ---- stage the stencil fields (grid coordinates i0-2.., j0-2..) ----
   {
     const int tid = threadIdx.y * BLK_X + threadIdx.x;
     for (int e = tid; e < TJ * TP; e += BLK_X * BLK_Y) {
       const int li = e % TP, lj = e / TP;
-      int gi = it0 - 2 + li, gj = j0 - 2 + lj;
-      if (s.sm) gi = wrap_i(b, gi);
+      int gi = i0 - 2 + li, gj = j0 - 2 + lj;
+      if (img) gi = wrap_i(b, gi);
       else gi = gi < b.LBi ? b.LBi : (gi > b.UBi ? b.UBi : gi);
       gj = gj < b.LBj ? b.LBj : (gj > b.UBj ? b.UBj : gj);
       const long g = I2(gi, gj);
@@ -291,20 +201,17 @@ k2d_mom_lds(const RomsDev *__restrict__ c, S2 s, const double *__restrict__ DUon
         sDU[e] = DUon[g];
         sDV[e] = DVom[g];
       } else {
-        // DUon, DVom evaluated in place (:509-544), identical expression to k2d_flux; the
-        // ghost columns/rows they reach hold exact copies, so no separate flux pass is needed
-        const double cu = 0.5 * MT(on_u, g, gj);
-        sDU[e] = ug * (cu * (Dg + (zk[g - 1] + HT(h, g - 1, gj))));
-        if (gj >= b.LBj + 1) {
-          const double cv = 0.5 * MT(om_v, g, gj);
-          sDV[e] = vg * (cv * (Dg + (zk[g - ni] + HT(h, g - ni, gj - 1))));
-        } else sDV[e] = 0.0;
+        // DUon, DVom evaluated in place (:509-544); the ghost columns/rows they reach hold exact copies, so no
+        // separate flux pass is needed
+        sDU[e] = flux_u(ug, MT(on_u, g, gj), Dg, zk[g - 1] + HT(h, g - 1, gj));
+        if (gj >= b.LBj + 1) sDV[e] = flux_v(vg, MT(om_v, g, gj), Dg, zk[g - ni] + HT(h, g - ni, gj - 1));
+        else sDV[e] = 0.0;
       }
     }
   }
   __syncthreads();
   if constexpr (FUSED) {
-    // free surface at tile points li = 1..BLK_X+1, lj = 1..BLK_Y+1 (targets it0-1.., j0-1..)
+    // free surface at tile points li = 1..BLK_X+1, lj = 1..BLK_Y+1 (points i0-1.., j0-1..)
     const int tid = threadIdx.y * BLK_X + threadIdx.x;
 #pragma unroll
     for (int r = 0; r < ZIT; r++) {
@@ -312,24 +219,23 @@ k2d_mom_lds(const RomsDev *__restrict__ c, S2 s, const double *__restrict__ DUon
       if (q < ZW * ZH) {
         const int li = 1 + q % ZW, lj = 1 + q / ZW;
         const int e = lj * TP + li;
-        int gi = it0 - 2 + li, gj = j0 - 2 + lj;
-        if (s.sm) gi = wrap_i(b, gi);
+        int gi = i0 - 2 + li, gj = j0 - 2 + lj;
+        if (img) gi = wrap_i(b, gi);
         else gi = gi < b.LBi ? b.LBi : (gi > b.UBi ? b.UBi : gi);
         gj = gj < b.LBj ? b.LBj : (gj > b.UBj ? b.UBj : gj);
         const double rhs = (sDU[e] - sDU[e + 1]) + (sDV[e] - sDV[e + TP]);
         double zn, zw;
         const long gq = I2(gi, gj);
-        zeta_eval_pre(p, s, rhs, MT(pm, gq, gj), MT(pn, gq, gj), z_zs[r], z_zk[r], z_rk[r], z_rp[r], z_rm[r],
-                      p.masking != 0, zn, zw);
+        zeta_step(p, s, rhs, MT(pm, gq, gj), MT(pn, gq, gj), z_zs[r], z_zk[r], z_rk[r], z_rp[r], z_rm[r],
+                  p.masking != 0, zn, zw);
         sZn[e] = zn;
         sZw[e] = zw;
       }
     }
     __syncthreads();
   }
-  if (it > ilast || j > b.Jend) return;
-  const int i = ghost_threads ? wrap_i(b, it) : it; // source column
-  // store at the target and, for an owner next to the periodic seam, at its image column(s)
+  if (i > b.Iend || j > b.Jend) return;
+  // store at the point and, for an owner next to the periodic seam, at its image column(s)
   auto put = [&](gd_t A, long idx, double val) {
     A[idx] = val;
     if (img) {
@@ -337,90 +243,44 @@ k2d_mom_lds(const RomsDev *__restrict__ c, S2 s, const double *__restrict__ DUon
       if (i >= b.Lm - 2) A[idx - b.Lm] = val;
     }
   };
-  const bool owner = (i == it);
-  const bool do_u = s.sm ? true : (i >= b.IstrU);
+  const bool do_u = img || i >= b.IstrU;
   const bool do_v = j >= b.JstrV;
-  const long a = I2(i, j);                          // source index in global arrays
-  const long o = I2(it, j);                         // target index
+  const long a = I2(i, j);
   const gcd_t rhoA = (gcd_t)(c->F.rhoA);
   const gcd_t rhoS = (gcd_t)(c->F.rhoS);
   const gcd_t zs = (gcd_t)(c->F.zeta + (long)(s.kstp - 1) * nij);
   T2 m;
   m.ub = sU; m.vb = sV; m.DU = sDU; m.DV = sDV; m.D = sD;
-  m.i0 = it0 - 2; m.j0 = j0 - 2;
+  m.i0 = i0 - 2; m.j0 = j0 - 2;
   m.Istr = b.Istr; m.Iend = b.Iend; m.Jstr = b.Jstr; m.Jend = b.Jend;
   m.s_edge = b.south_edge && !b.NSperiodic; m.n_edge = b.north_edge && !b.NSperiodic;
   m.w_edge = b.west_edge && !b.EWperiodic;  m.e_edge = b.east_edge && !b.EWperiodic;
-  const int t = m.at(it, j);                        // this point in the tiles
+  const int t = m.at(i, j);                        // this point in the tiles
   const double fac = 1000.0 / p.rho0;
   const bool masking = p.masking != 0;
   // closed-wall rows under MASKING: the boundary value times the mask of the boundary point (zetabc.F:540,
   // u2dbc_im.F:975); mk(M, q) = 1 without masks
   auto mk = [&](gd_t M, long q) { return masking ? (double)M[q] : 1.0; };
-  // ---- pressure gradient, :939-1019 ----
   if constexpr (FUSED) {
-    // ---- what k2d_zeta_sm did: fast-time averages on the owned ranges and zeta(knew), rzeta(krhs) ----
-    const int iif = s.iif;
-    const gcd_t zkr = (gcd_t)(c->F.zeta + (long)(s.krhs - 1) * nij);
-    auto average = [&](long oo, int tt, bool inU, bool inV) {       // step2d_LF_AM3.h:614-682 at target oo
-      if (s.predictor && iif == 1) {
-        const double cff2 = (-1.0 / 12.0) * p.weight2[iif];
-        GF(Zt_avg1)[oo] = 0.0;
-        if (inU) { GF(DU_avg1)[oo] = 0.0; GF(DU_avg2)[oo] = cff2 * sDU[tt]; }
-        if (inV) { GF(DV_avg1)[oo] = 0.0; GF(DV_avg2)[oo] = cff2 * sDV[tt]; }
-      } else if (s.predictor) {
-        const double cff1 = p.weight1[iif - 2];
-        const double cff2 = (8.0 / 12.0) * p.weight2[iif - 1] - (1.0 / 12.0) * p.weight2[iif];
-        GF(Zt_avg1)[oo] = GF(Zt_avg1)[oo] + cff1 * zkr[oo];
-        if (inU) {
-          GF(DU_avg1)[oo] = GF(DU_avg1)[oo] + cff1 * sDU[tt];
-          GF(DU_avg2)[oo] = GF(DU_avg2)[oo] + cff2 * sDU[tt];
-        }
-        if (inV) {
-          GF(DV_avg1)[oo] = GF(DV_avg1)[oo] + cff1 * sDV[tt];
-          GF(DV_avg2)[oo] = GF(DV_avg2)[oo] + cff2 * sDV[tt];
-        }
-      } else {
-        const double cff2 = (iif == 1) ? p.weight2[iif - 1] : (5.0 / 12.0) * p.weight2[iif - 1];
-        if (inU) GF(DU_avg2)[oo] = GF(DU_avg2)[oo] + cff2 * sDU[tt];
-        if (inV) GF(DV_avg2)[oo] = GF(DV_avg2)[oo] + cff2 * sDV[tt];
-      }
-    };
-    const bool in_i = it >= b.IstrR && it <= b.IendR;
-    if (in_i) {
-      const bool inU = it >= b.Istr;
-      // the thread's own point, with the running sums requested at the top of the kernel (same expressions as `average`)
-      if (s.predictor && iif == 1) {
-        const double cff2 = (-1.0 / 12.0) * p.weight2[iif];
-        GF(Zt_avg1)[o] = 0.0;
-        if (inU) { GF(DU_avg1)[o] = 0.0; GF(DU_avg2)[o] = cff2 * sDU[t]; }
-        GF(DV_avg1)[o] = 0.0; GF(DV_avg2)[o] = cff2 * sDV[t];
-      } else if (s.predictor) {
-        const double cff1 = p.weight1[iif - 2];
-        const double cff2 = (8.0 / 12.0) * p.weight2[iif - 1] - (1.0 / 12.0) * p.weight2[iif];
-        GF(Zt_avg1)[o] = q_Zt + cff1 * q_zkr;
-        if (inU) {
-          GF(DU_avg1)[o] = q_DU1 + cff1 * sDU[t];
-          GF(DU_avg2)[o] = q_DU2 + cff2 * sDU[t];
-        }
-        GF(DV_avg1)[o] = q_DV1 + cff1 * sDV[t];
-        GF(DV_avg2)[o] = q_DV2 + cff2 * sDV[t];
-      } else {
-        const double cff2 = (iif == 1) ? p.weight2[iif - 1] : (5.0 / 12.0) * p.weight2[iif - 1];
-        if (inU) GF(DU_avg2)[o] = q_DU2 + cff2 * sDU[t];
-        GF(DV_avg2)[o] = q_DV2 + cff2 * sDV[t];
-      }
-      if (j == b.Jstr && b.JstrR < b.Jstr) average(o - ni, t - TP, inU, false);   // row JstrR = Jstr-1
-      if (j == b.Jend && b.JendR > b.Jend) average(o + ni, t + TP, inU, true);    // row JendR = Jend+1
+    // ---- fast-time averages on the owned ranges (:614-682) and zeta(knew), rzeta(krhs) ----
+    if (i >= b.IstrR && i <= b.IendR) {
+      const bool inU = i >= b.Istr;
+      // the thread's own point, with the running sums requested at the top of the kernel
+      store_average(c, s, a, inU, true,
+                    fast_average(p, s, FastAvg{q_Zt, q_DU1, q_DU2, q_DV1, q_DV2}, sDU[t], sDV[t], q_zkr));
+      // the rows of the averaging range beyond the interior: JstrR = Jstr-1, JendR = Jend+1
+      if (j == b.Jstr && b.JstrR < b.Jstr) average_point(c, s, a - ni, inU, false, sDU[t - TP], sDV[t - TP], nij);
+      if (j == b.Jend && b.JendR > b.Jend) average_point(c, s, a + ni, inU, true, sDU[t + TP], sDV[t + TP], nij);
     }
     const double zn = sZn[t];
     const gd_t zout = (gd_t)(c->F.zeta + (long)(s.knew - 1) * nij);
-    put(zout, o, zn);
-    if (b.south_edge && j == b.Jstr) put(zout, o - ni, masking ? zn * GF(rmask)[a - ni] : zn);   // zetabc closed
-    if (b.north_edge && j == b.Jend) put(zout, o + ni, masking ? zn * GF(rmask)[a + ni] : zn);
-    if (s.predictor)      // at the target: ghost columns hold the periodic copy, as after the exchange
-      put((gd_t)(c->F.rzeta + (long)(s.krhs - 1) * nij), o, (sDU[t] - sDU[t + 1]) + (sDV[t] - sDV[t + TP]));
+    put(zout, a, zn);
+    if (b.south_edge && j == b.Jstr) put(zout, a - ni, masking ? zn * GF(rmask)[a - ni] : zn);   // zetabc closed
+    if (b.north_edge && j == b.Jend) put(zout, a + ni, masking ? zn * GF(rmask)[a + ni] : zn);
+    if (s.predictor)      // the image columns hold the periodic copy, as after the exchange
+      put((gd_t)(c->F.rzeta + (long)(s.krhs - 1) * nij), a, (sDU[t] - sDU[t + 1]) + (sDV[t] - sDV[t + TP]));
   }
+  // ---- pressure gradient, :939-1019 ----
   // resting depth at the point, its western and its southern neighbour (rows j, j, j-1: always inside the array)
   const double h0 = HT(h, a, j), hw = HT(h, a - 1, j), hs = HT(h, a - ni, j - 1);
   const double zw0 = FUSED ? sZw[t] : zwrk[a];
@@ -451,13 +311,13 @@ k2d_mom_lds(const RomsDev *__restrict__ c, S2 s, const double *__restrict__ DUon
   // ---- advection, :1079-1283 ----
   if (p.uv_adv) {
     if (do_u) {
-      const double cff1 = UFx2(m, it, j) - UFx2(m, it - 1, j);
-      const double cff2 = UFe2(m, it, j + 1) - UFe2(m, it, j);
+      const double cff1 = UFx2(m, i, j) - UFx2(m, i - 1, j);
+      const double cff2 = UFe2(m, i, j + 1) - UFe2(m, i, j);
       rhs_u = rhs_u - (cff1 + cff2);
     }
     if (do_v) {
-      const double cff1 = VFx2(m, it + 1, j) - VFx2(m, it, j);
-      const double cff2 = VFe2(m, it, j) - VFe2(m, it, j - 1);
+      const double cff1 = VFx2(m, i + 1, j) - VFx2(m, i, j);
+      const double cff2 = VFe2(m, i, j) - VFe2(m, i, j - 1);
       rhs_v = rhs_v - (cff1 + cff2);
     }
   }
@@ -531,7 +391,7 @@ k2d_mom_lds(const RomsDev *__restrict__ c, S2 s, const double *__restrict__ DUon
     }
   }
   // ---- biharmonic viscosity, :1474-1740: evaluated by the pass in front of this kernel (roms_launch_step2d_visc4,
-  // k_uv3dmix2.hip); UV_VIS4 runs take the general path, so `a` is this thread's own point ----
+  // k_uv3dmix2.hip; split path only) ----
   if (p.uv_vis4) {
     if (do_u) rhs_u = rhs_u - c->ws2[22][a];
     if (do_v) rhs_v = rhs_v - c->ws2[23][a];
@@ -539,7 +399,6 @@ k2d_mom_lds(const RomsDev *__restrict__ c, S2 s, const double *__restrict__ DUon
   // ---- coupling between 2-D and 3-D equations, :1884-2065 ----
   double rf_u = 0.0, rf_v = 0.0;                        // rufrc / rvfrc of the first predictor (WET: scaled below)
   if (s.iif == 1 && s.predictor) {
-    // never source-mapped (step2d_impl), so owner is always true here
     const gd_t ru_s = (gd_t)(c->F.ru + (long)(s.nstp - 1) * n3w);
     const gd_t rv_s = (gd_t)(c->F.rv + (long)(s.nstp - 1) * n3w);
     const gcd_t ru_n = (gcd_t)(c->F.ru + (long)(s.nnew - 1) * n3w);
@@ -597,25 +456,25 @@ k2d_mom_lds(const RomsDev *__restrict__ c, S2 s, const double *__restrict__ DUon
         ((gd_t)(c->F.ru + (long)(s.nstp - 1) * n3w))[a] = rf;
       }
     }
-    put(ubn, o, un);
-    if (s.predictor && owner) GF(rubar)[a + (long)(s.krhs - 1) * nij] = rhs_u;
+    put(ubn, a, un);
+    if (s.predictor) GF(rubar)[a + (long)(s.krhs - 1) * nij] = rhs_u;
     const double un_s = masking ? (p.gamma2 * un) * GF(umask)[a - ni] : p.gamma2 * un;   // wall rows (u2dbc)
     const double un_n = masking ? (p.gamma2 * un) * GF(umask)[a + ni] : p.gamma2 * un;
     if (inline_bc) {                                   // u2dbc closed walls, u2dbc_im.F:51
-      if (b.south_edge && j == b.Jstr) put(ubn, o - ni, un_s);
-      if (b.north_edge && j == b.Jend) put(ubn, o + ni, un_n);
+      if (b.south_edge && j == b.Jstr) put(ubn, a - ni, un_s);
+      if (b.north_edge && j == b.Jend) put(ubn, a + ni, un_n);
     }
     if constexpr (FUSED) {
       if (DUnext) {                                    // DUon of level knew, :509-525 (as k2d_flux)
         const double znw = sZn[t - 1];
-        DUnext[a] = un * ((0.5 * MT(on_u, a, j)) * (Dn0 + (znw + hw)));
+        DUnext[a] = flux_u(un, MT(on_u, a, j), Dn0, znw + hw);
         // wall rows: u = gamma2*u(adjacent row), zeta = zero-gradient copy (u2dbc_im.F:51, zetabc.F:48)
         if (b.south_edge && j == b.Jstr)
-          DUnext[a - ni] = un_s * ((0.5 * MT(on_u, a - ni, j - 1)) *
-                                   ((sZn[t] * mk(GF(rmask), a - ni) + hs) + (znw * mk(GF(rmask), q - ni) + HT(h, q - ni, j - 1))));
+          DUnext[a - ni] = flux_u(un_s, MT(on_u, a - ni, j - 1), sZn[t] * mk(GF(rmask), a - ni) + hs,
+                                  znw * mk(GF(rmask), q - ni) + HT(h, q - ni, j - 1));
         if (b.north_edge && j == b.Jend)
-          DUnext[a + ni] = un_n * ((0.5 * MT(on_u, a + ni, j + 1)) *
-                                   ((sZn[t] * mk(GF(rmask), a + ni) + HT(h, a + ni, j + 1)) + (znw * mk(GF(rmask), q + ni) + HT(h, q + ni, j + 1))));
+          DUnext[a + ni] = flux_u(un_n, MT(on_u, a + ni, j + 1), sZn[t] * mk(GF(rmask), a + ni) + HT(h, a + ni, j + 1),
+                                  znw * mk(GF(rmask), q + ni) + HT(h, q + ni, j + 1));
       }
     }
   }
@@ -641,23 +500,23 @@ k2d_mom_lds(const RomsDev *__restrict__ c, S2 s, const double *__restrict__ DUon
         ((gd_t)(c->F.rv + (long)(s.nstp - 1) * n3w))[a] = rf;
       }
     }
-    put(vbn, o, vn);
-    if (s.predictor && owner) GF(rvbar)[a + (long)(s.krhs - 1) * nij] = rhs_v;
+    put(vbn, a, vn);
+    if (s.predictor) GF(rvbar)[a + (long)(s.krhs - 1) * nij] = rhs_v;
     if constexpr (FUSED) {
-      if (DVnext) DVnext[a] = vn * ((0.5 * MT(om_v, a, j)) * (Dn0 + (sZn[t - TP] + hs)));   // :527-544
+      if (DVnext) DVnext[a] = flux_v(vn, MT(om_v, a, j), Dn0, sZn[t - TP] + hs);   // :527-544
     }
   }
   if (inline_bc) {                                     // v2dbc closed walls, v2dbc_im.F:52
-    if (b.south_edge && j == b.Jstr) put(vbn, o, 0.0);
-    if (b.north_edge && j == b.Jend) put(vbn, o + ni, 0.0);
+    if (b.south_edge && j == b.Jstr) put(vbn, a, 0.0);
+    if (b.north_edge && j == b.Jend) put(vbn, a + ni, 0.0);
   }
   if constexpr (FUSED) {
     if (DVnext) {                                      // wall rows: v = 0 there
       const double zn0 = sZn[t];
       if (b.south_edge && j == b.Jstr)
-        DVnext[a] = 0.0 * ((0.5 * MT(om_v, a, j)) * ((zn0 + h0) + (zn0 * mk(GF(rmask), a - ni) + hs)));
+        DVnext[a] = flux_v(0.0, MT(om_v, a, j), zn0 + h0, zn0 * mk(GF(rmask), a - ni) + hs);
       if (b.north_edge && j == b.Jend)
-        DVnext[a + ni] = 0.0 * ((0.5 * MT(om_v, a + ni, j + 1)) * ((zn0 * mk(GF(rmask), a + ni) + HT(h, a + ni, j + 1)) + (zn0 + h0)));
+        DVnext[a + ni] = flux_v(0.0, MT(om_v, a + ni, j + 1), zn0 * mk(GF(rmask), a + ni) + HT(h, a + ni, j + 1), zn0 + h0);
     }
   }
 }
@@ -749,44 +608,20 @@ int roms_rowm_prepare()
   return 0;
 }
 
-// Launcher used by step2d_impl (k_step2d.hip); s10 = the ten ints of its S2.
-int roms_launch_k2d_mom_lds(const int *s10, const double *DUon, const double *DVom, const double *zeta_new,
+// Launcher used by step2d_impl (k_step2d.hip)
+int roms_launch_k2d_mom_lds(const S2 &s, K2dLaunch mode, const double *DUon, const double *DVom, const double *zeta_new,
                             const double *zwrk, double *DUnext, double *DVnext)
 {
   const roms_bounds_t &b = g_ctx.b;
-  S2 s{s10[0], s10[1], s10[2], s10[3], s10[4], s10[5], s10[6], s10[7], s10[8], s10[9]};
-  const int nx = (s.sm == 1) ? (b.UBi - b.LBi + 1) : (b.Iend - b.Istr + 1);
-  if (s.sm == 2) {      // fused free-surface + momentum call (source-mapped, fluxes in place)
-    s.sm = 1;
-    if (g_ctx.rowm_state == 1 && g_ctx.rowh)   // ... and depth and viscosity coefficients as well
-      hipLaunchKernelGGL((k2d_mom_lds<true, true, true>), grid2d(nx, b.Jend - b.Jstr + 1), block2d(), 0, g_ctx.stream,
-                         g_ctx.devc, s, (const double *)nullptr, (const double *)nullptr, (const double *)nullptr,
-                         (const double *)nullptr, (double *)nullptr, (double *)nullptr);
-    else if (g_ctx.rowm_state == 1)   // metrics independent of i: row table instead of fifteen 2-D arrays
-      hipLaunchKernelGGL((k2d_mom_lds<true, true>), grid2d(nx, b.Jend - b.Jstr + 1), block2d(), 0, g_ctx.stream,
-                         g_ctx.devc, s, (const double *)nullptr, (const double *)nullptr, (const double *)nullptr,
-                         (const double *)nullptr, (double *)nullptr, (double *)nullptr);
-    else
-      hipLaunchKernelGGL((k2d_mom_lds<true, false>), grid2d(nx, b.Jend - b.Jstr + 1), block2d(), 0, g_ctx.stream,
-                         g_ctx.devc, s, (const double *)nullptr, (const double *)nullptr, (const double *)nullptr,
-                         (const double *)nullptr, (double *)nullptr, (double *)nullptr);
-  } else if (s.sm == 3) {   // fused call on several tiles: exchanged DUon/DVom in, next call's fluxes out
-    s.sm = 0;
-    if (g_ctx.rowm_state == 1 && g_ctx.rowh)
-      hipLaunchKernelGGL((k2d_mom_lds<true, true, true>), grid2d(nx, b.Jend - b.Jstr + 1), block2d(), 0, g_ctx.stream,
-                         g_ctx.devc, s, DUon, DVom, (const double *)nullptr, (const double *)nullptr, DUnext, DVnext);
-    else if (g_ctx.rowm_state == 1)
-      hipLaunchKernelGGL((k2d_mom_lds<true, true>), grid2d(nx, b.Jend - b.Jstr + 1), block2d(), 0, g_ctx.stream,
-                         g_ctx.devc, s, DUon, DVom, (const double *)nullptr, (const double *)nullptr, DUnext, DVnext);
-    else
-      hipLaunchKernelGGL((k2d_mom_lds<true, false>), grid2d(nx, b.Jend - b.Jstr + 1), block2d(), 0, g_ctx.stream,
-                         g_ctx.devc, s, DUon, DVom, (const double *)nullptr, (const double *)nullptr, DUnext, DVnext);
-  } else if (g_ctx.p.wet_dry)
-    hipLaunchKernelGGL((k2d_mom_lds<false, false, false, true>), grid2d(nx, b.Jend - b.Jstr + 1), block2d(), 0, g_ctx.stream,
-                       g_ctx.devc, s, DUon, DVom, zeta_new, zwrk, (double *)nullptr, (double *)nullptr);
-  else
-    hipLaunchKernelGGL((k2d_mom_lds<false, false>), grid2d(nx, b.Jend - b.Jstr + 1), block2d(), 0, g_ctx.stream, g_ctx.devc, s,
-                       DUon, DVom, zeta_new, zwrk, (double *)nullptr, (double *)nullptr);
+  // metrics independent of i: row table instead of fifteen 2-D arrays (... and depth and viscosity coefficients too)
+  const bool rowm = g_ctx.rowm_state == 1, rowh = rowm && g_ctx.rowh;
+  const auto kernel = mode == K2dLaunch::Split ? (g_ctx.p.wet_dry ? k2d_mom_lds<false, false, false, true>
+                                                                  : k2d_mom_lds<false, false, false, false>)
+                      : rowh ? k2d_mom_lds<true, true, true, false>
+                      : rowm ? k2d_mom_lds<true, true, false, false>
+                             : k2d_mom_lds<true, false, false, false>;
+  hipLaunchKernelGGL(kernel, grid2d(b.Iend - b.Istr + 1, b.Jend - b.Jstr + 1), block2d(), 0, g_ctx.stream, g_ctx.devc, s,
+                     DUon, DVom, zeta_new, zwrk, DUnext, DVnext);
   KERNEL_CHECK("k2d_mom_lds");
   return 0;
 }

@@ -245,6 +245,12 @@ static inline dim3 grid2d(int nx, int ny) {
   return dim3((unsigned)((nx + BLK_X - 1) / BLK_X), (unsigned)((ny + BLK_Y - 1) / BLK_Y), 1);
 }
 static inline dim3 block2d() { return dim3(BLK_X, BLK_Y, 1); }
+// LDS tile of a workgroup's points with their 2-point C-grid halo (k_rhs3d.hip, k_step2d_mom.hip), and the second
+// differences of the 3rd / 4th-order advection at tile element a
+#define TP (BLK_X + 4)       // tile pitch (i)
+#define TJ (BLK_Y + 4)       // tile rows  (j)
+__device__ __forceinline__ double d2x(const double *f, int a) { return f[a - 1] - 2.0 * f[a] + f[a + 1]; }
+__device__ __forceinline__ double d2y(const double *f, int a) { return f[a - TP] - 2.0 * f[a] + f[a + TP]; }
 // (tile, level) decode of a 1-D grid for kernels with one thread per cell: consecutive workgroups of an XCD take the
 // SAME horizontal tile at consecutive levels, so the planes k-1, k, k+1 a vertical stencil reads meet in one L2
 // (with the level in gridDim.z they are thousands of workgroups apart and on other XCDs); tiles are dealt to the
