@@ -244,6 +244,34 @@ int roms_hip_wetdry(const roms_step_idx_t *s);
  * whose bit of point_sources is off is not looked at. */
 int roms_hip_set_sources(int Nsrc, const int *Isrc, const int *Jsrc, const double *Dsrc, const double *Qbar,
                          const double *Qsrc, const double *Tsrc, const int *LtracerSrc);
+/* Nudging towards a climatology: the run-time switches LnudgeM2CLM, LnudgeM3CLM, LnudgeTCLM of a roms_*.in with the
+ * members of CLIMA(ng) (mod_clima.F:190-261) they read.  No CPP option; IMPLICIT_NUDGING is not built.
+ *   LnudgeTCLM[NT] = LtracerCLM(itrc,ng).and.LnudgeTCLM(itrc,ng) as 0 / 1; NTCLM = the number of set flags, and the
+ *   compact index ic of a nudged tracer counts them in the order of itrc (step3d_t.F:1551-1560).
+ *   Array extents are the host's: M2nudgcof, ubarclm, vbarclm (LBi:UBi,LBj:UBj); M3nudgcof, uclm, vclm
+ *   (LBi:UBi,LBj:UBj,N); Tnudgcof, tclm (LBi:UBi,LBj:UBj,N,NTCLM).  Coefficients in 1/s.  Ghost points (periodic images
+ *   and the points of neighbour tiles included) must be filled: the momentum terms average the coefficient over the
+ *   two rho-points of a face.
+ * The arrays are copied to device arrays of the library.  The entries that consume them:
+ *   step3d_t     t(nnew) += dt * Tnudgcof * (tclm - t(nnew)) on IstrR:IendR, JstrR:JendR, after t3dbc_tile and before
+ *                the land/sea mask and the exchange (step3d_t.F:1551-1584)
+ *   rhs3d_tile   ru, rv(nrhs) += 1/4 (c(i-1)+c(i)) om_u on_u (Hz(i-1)+Hz(i)) (uclm - u(nrhs)) and the v form, after
+ *                the Coriolis and curvilinear terms, before the advection (rhs3d.F:567-594)
+ *   step2d       the same with M2nudgcof, Drhs, ubarclm - ubar(krhs) into rhs_ubar / rhs_vbar, predictor and
+ *                corrector, before the coupling with rufrc (step2d_LF_AM3.h:1818-1845)
+ *   every RadNud edge of a variable whose switch is on: obc_out = the coefficient at the edge (tracers: at the
+ *                boundary point, t3dbc_im.F:119-126, :254, :388, :522; momentum: the mean of the two rho-points around
+ *                the velocity point, u3dbc_im.F:113, v3dbc_im.F:113, u2dbc_im.F:149-158, v2dbc_im.F:151-158 and the
+ *                other edges' blocks), obc_in = obcfac * obc_out, instead of roms_params_t.obc_out / obc_in; also in
+ *                pre_step3d (pre_step3d.F:1126-1135) and ini_fields (ini_fields.F:602-633).  zetabc.F has no such
+ *                branch.
+ * Call it after roms_hip_set_bounds and roms_hip_set_params, and again whenever set_data has moved the climatology:
+ * on a later call with the same switches a NULL array means "keep the copy you have".  A set switch whose arrays were
+ * never given, obcfac < 0 and a call before bounds / params are refused.  All switches zero releases everything.
+ * roms_hip_set_bounds drops the copies (new extents). */
+int roms_hip_set_clima(int LnudgeM2CLM, const double *M2nudgcof, const double *ubarclm, const double *vbarclm,
+                       int LnudgeM3CLM, const double *M3nudgcof, const double *uclm, const double *vclm,
+                       const int *LnudgeTCLM, const double *Tnudgcof, const double *tclm, double obcfac);
 /* wvelocity(ng,tile,nstp)          ROMS/Nonlinear/wvelocity.F:27     (main3d.F:475; writes wvel) */
 int roms_hip_wvelocity(const roms_step_idx_t *s);
 /* diag(ng,tile)                    ROMS/Nonlinear/diag.F:31          (main3d.F:314), the tile-local part

@@ -548,3 +548,55 @@ def make_tile(config, ntileI=1, ntileJ=1, tile=0, NT=None, overrides=None,
     elif mask is not None:
         raise ValueError(f"unknown mask {mask!r}")
     return st
+
+
+def analytic_clima(st, sides=("south", "north"), width=6.0, tnudg=None, m2=True, m3=True, tracers=None, obcfac=3.0):
+    """An analytic sponge and climatology for the tile (roms_trunk_mgh_amd/clima.py), the stand-in for an application's
+    ana_nudgcoef.h and its climatology file: the nudging coefficient rises linearly over `width` grid points towards
+    the chosen `sides` (from a tenth of its maximum, 1/tnudg, in the interior, on top of a gentle two-dimensional
+    modulation, so that it is non-zero and varies in i and j everywhere) and decreases with depth (half at the bottom
+    level); the climatology fields are smooth waves around the initial state.  Everything is a function of the GLOBAL
+    indices (of the periodic image in a periodic direction), so that any tile of any tiling fills its own arrays, ghost
+    points included, with the values its neighbours hold.  tnudg: the shortest time scale (s), default 10 dt;
+    tracers: LnudgeTCLM per tracer (default: all active tracers); m2, m3: LnudgeM2CLM, LnudgeM3CLM."""
+    from .clima import Clima
+    b, p = st.b, st.p
+    Lm, Mm, N, NT = b.Lm, b.Mm, b.N, b.NT
+    ii = np.arange(b.LBi, b.UBi + 1, dtype=np.float64)[:, None]
+    jj = np.arange(b.LBj, b.UBj + 1, dtype=np.float64)[None, :]
+    iw = np.mod(ii - 1.0, Lm) + 1.0 if b.EWperiodic else ii
+    dist = np.full((st.ni, st.nj), np.inf)
+    for sd in sides:
+        d = {"west": iw + 0.0 * jj, "east": (Lm + 1.0) - iw + 0.0 * jj, "south": jj + 0.0 * ii,
+             "north": (Mm + 1.0) - jj + 0.0 * ii}[sd]
+        dist = np.minimum(dist, d)
+    ramp = np.clip(1.0 - dist / float(width), 0.0, 1.0)
+
+    def wave(a, bq, ph):
+        return np.sin(2.0 * math.pi * a * (iw - 0.5) / Lm + ph) * np.cos(math.pi * bq * (jj - 0.5) / Mm)
+
+    cmax = 1.0 / (tnudg if tnudg is not None else 10.0 * p.dt)
+    c2 = cmax * (ramp + 0.1 * (1.0 + 0.5 * wave(1, 1, 0.4)))
+    kk = (np.arange(1, N + 1, dtype=np.float64) / N)[None, None, :]
+    c3 = c2[:, :, None] * (0.5 + 0.5 * kk)
+    kw = dict(obcfac=obcfac)
+    if m2:
+        kw.update(LnudgeM2CLM=True, M2nudgcof=c2, ubarclm=0.03 * wave(2, 1, 0.9), vbarclm=0.02 * wave(1, 2, 0.2))
+    if m3:
+        kw.update(LnudgeM3CLM=True, M3nudgcof=c3, uclm=0.05 * wave(2, 1, 0.9)[:, :, None] * (0.3 + kk),
+                  vclm=0.03 * wave(1, 2, 0.2)[:, :, None] * (0.3 + kk))
+    flags = np.zeros(NT, dtype=np.int32)
+    if tracers is None:
+        flags[:b.NAT] = 1
+    else:
+        flags[:] = np.asarray(tracers) != 0
+    if flags.any():
+        nc = int(flags.sum())
+        tn = np.zeros((st.ni, st.nj, N, nc), order="F")
+        tc = np.zeros((st.ni, st.nj, N, nc), order="F")
+        for ic, it in enumerate(np.flatnonzero(flags)):
+            tn[:, :, :, ic] = c3 * (1.0 + 0.25 * ic)
+            tc[:, :, :, ic] = st["t"][:, :, :, 0, it] + 0.3 * wave(1 + ic, 1, 0.6)[:, :, None] * kk
+        kw.update(LnudgeTCLM=flags, Tnudgcof=tn, tclm=tc)
+    st.clima = Clima(b, **kw)
+    return st.clima

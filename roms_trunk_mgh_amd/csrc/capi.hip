@@ -78,7 +78,7 @@ __global__ void __launch_bounds__(256) k_calib_stream(const double *__restrict__
   if (e < n) dst[e] = src[e];
 }
 int roms_entry_check(const char *where);
-namespace { void sources_release(); }
+namespace { void sources_release(); void clima_release(); }
 extern "C" int roms_hip_calib_stream(long n)
 {
   int rc = roms_entry_check("roms_hip_calib_stream");
@@ -130,6 +130,16 @@ static void guarded_free(double **user, double **base)
   *user = *base = nullptr;
 }
 
+// ---- climatology (mod_clima.F), roms_hip_set_clima: the eight device copies, each with its guard bands ----
+namespace {
+enum { CL_M2nudgcof = 0, CL_ubarclm, CL_vbarclm, CL_M3nudgcof, CL_uclm, CL_vclm, CL_Tnudgcof, CL_tclm, CL_COUNT };
+const char *const k_clima_name[CL_COUNT] = {"M2nudgcof", "ubarclm", "vbarclm", "M3nudgcof", "uclm", "vclm", "Tnudgcof", "tclm"};
+struct ClimaStore {
+  double *dev[CL_COUNT] = {nullptr}, *base[CL_COUNT] = {nullptr};
+  long count[CL_COUNT] = {0};
+} g_clima;
+}  // namespace
+
 // 0 = every guard band intact; otherwise an error naming the first damaged array (field name, or ws3[q] /
 // ws2[q] for scratch) and the distance of the first damaged word from the array.
 extern "C" int roms_hip_check_guards(void)
@@ -159,6 +169,8 @@ extern "C" int roms_hip_check_guards(void)
   int rc;
   for (int id = 0; id < FID_COUNT; id++)
     if ((rc = check(k_field_name[id], -1, g_ctx.dev_base[id], g_ctx.count[id]))) return rc;
+  for (int q = 0; q < CL_COUNT; q++)
+    if ((rc = check(k_clima_name[q], -1, g_clima.base[q], g_clima.count[q]))) return rc;
   for (int q = 0; q < ROMS_NWS3; q++)
     if ((rc = check("ws3", q, g_ctx.ws3_base[q], nij * (b.N + 1)))) return rc;
   for (int q = 0; q < 32; q++)
@@ -242,6 +254,7 @@ extern "C" int roms_hip_finalize(void)
   for (int q = 0; q < ROMS_NWS3; q++) guarded_free(&g_ctx.hostc.ws3[q], &g_ctx.ws3_base[q]);
   for (int q = 0; q < 32; q++) guarded_free(&g_ctx.hostc.ws2[q], &g_ctx.ws2_base[q]);
   sources_release();
+  clima_release();
   if (g_ctx.devc) (void)hipFree(g_ctx.devc);
   g_ctx.devc = nullptr;
   if (g_ctx.stream) (void)hipStreamDestroy(g_ctx.stream);
@@ -354,6 +367,82 @@ extern "C" int roms_hip_set_sources(int Nsrc, const int *Isrc, const int *Jsrc, 
   return 0;
 }
 
+// ---- climatology nudging (mod_clima.F:190-261), LnudgeM2CLM / LnudgeM3CLM / LnudgeTCLM ----
+namespace {
+void clima_release()
+{
+  for (int q = 0; q < CL_COUNT; q++) {
+    guarded_free(&g_clima.dev[q], &g_clima.base[q]);
+    g_clima.count[q] = 0;
+  }
+  g_ctx.hostc.clima = RomsClima{};
+  g_ctx.devc_dirty = true;
+}
+}  // namespace
+
+extern "C" int roms_hip_set_clima(int LnudgeM2CLM, const double *M2nudgcof, const double *ubarclm, const double *vbarclm,
+                                  int LnudgeM3CLM, const double *M3nudgcof, const double *uclm, const double *vclm,
+                                  const int *LnudgeTCLM, const double *Tnudgcof, const double *tclm, double obcfac)
+{
+  const char *me = "roms_hip_set_clima";
+  if (!g_ctx.inited || !g_ctx.have_bounds || !g_ctx.have_params)
+    return roms_fail(me, "roms_hip_init, roms_hip_set_bounds and roms_hip_set_params come first");
+  if (!(obcfac >= 0.0)) return roms_fail(me, "climatology: obcfac < 0");
+  const roms_bounds_t &b = g_ctx.b;
+  const long nij = (long)(b.UBi - b.LBi + 1) * (long)(b.UBj - b.LBj + 1);
+  RomsClima want{};
+  want.m2 = LnudgeM2CLM != 0;
+  want.m3 = LnudgeM3CLM != 0;
+  want.obcfac = obcfac;
+  for (int it = 0; it < b.NT; it++)
+    if (LnudgeTCLM && LnudgeTCLM[it]) {
+      want.itrc[want.nt] = it + 1;
+      want.ic[it] = ++want.nt;
+    }
+  const RomsClima &have = g_ctx.hostc.clima;
+  if (!want.m2 && !want.m3 && !want.nt) {              // all flags zero: release everything
+    if (have.m2 || have.m3 || have.nt) {
+      HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+      step2d_graphs_release();
+      clima_release();
+    }
+    return 0;
+  }
+  const bool same = want.m2 == have.m2 && want.m3 == have.m3 && std::equal(want.ic, want.ic + ROMS_MAXNT, have.ic);
+  const double *host[CL_COUNT] = {M2nudgcof, ubarclm, vbarclm, M3nudgcof, uclm, vclm, Tnudgcof, tclm};
+  const long n[CL_COUNT] = {nij, nij, nij, nij * b.N, nij * b.N, nij * b.N, nij * b.N * want.nt, nij * b.N * want.nt};
+  const bool on[CL_COUNT] = {want.m2 != 0, want.m2 != 0, want.m2 != 0, want.m3 != 0, want.m3 != 0, want.m3 != 0,
+                             want.nt != 0, want.nt != 0};
+  // a NULL array = "keep the copy you have": only with the flags of the call that gave it.  Nothing is touched
+  // before every argument has been looked at, so that a refused call leaves the library as it was.
+  for (int q = 0; q < CL_COUNT; q++)
+    if (on[q] && !host[q] && !(same && g_clima.dev[q])) {
+      const std::string m = std::string("climatology: the switch of ") + k_clima_name[q] + " is set but the array was never "
+                            "given (NULL keeps an earlier copy only after a call with the same switches that brought one)";
+      return roms_fail(me, m.c_str());
+    }
+  HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+  // the boundary-condition launches inside the captured LOOP_2D graphs hold the coefficient address and obcfac
+  if (!same || want.obcfac != have.obcfac) step2d_graphs_release();
+  if (!same) clima_release();
+  for (int q = 0; q < CL_COUNT; q++) {
+    if (!on[q] || !host[q]) continue;
+    if (!g_clima.dev[q]) {
+      int rc = guarded_alloc(&g_clima.dev[q], &g_clima.base[q], n[q]);
+      if (rc) { clima_release(); return rc; }
+      g_clima.count[q] = n[q];
+    }
+    HIP_TRY(hipMemcpyAsync(g_clima.dev[q], host[q], sizeof(double) * n[q], hipMemcpyHostToDevice, g_ctx.stream));
+  }
+  HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+  want.M2nudgcof = g_clima.dev[CL_M2nudgcof]; want.ubarclm = g_clima.dev[CL_ubarclm]; want.vbarclm = g_clima.dev[CL_vbarclm];
+  want.M3nudgcof = g_clima.dev[CL_M3nudgcof]; want.uclm = g_clima.dev[CL_uclm]; want.vclm = g_clima.dev[CL_vclm];
+  want.Tnudgcof = g_clima.dev[CL_Tnudgcof]; want.tclm = g_clima.dev[CL_tclm];
+  g_ctx.hostc.clima = want;
+  g_ctx.devc_dirty = true;
+  return 0;
+}
+
 extern "C" int roms_hip_set_bounds(const roms_bounds_t *b)
 {
   if (!g_ctx.inited) return roms_fail("roms_hip_set_bounds", "library not initialised");
@@ -363,6 +452,7 @@ extern "C" int roms_hip_set_bounds(const roms_bounds_t *b)
   step2d_graphs_release();
   roms_rowm_release();
   sources_release();                       // the face maps are in the old bounds' index space
+  clima_release();                         // ... and the climatology has the old extents
   g_ctx.b = *b;
   g_ctx.hostc.b = *b;
   g_ctx.have_bounds = true;

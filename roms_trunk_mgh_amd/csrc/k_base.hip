@@ -76,6 +76,10 @@ struct BcArgs {
   int code[4];           // enum roms_lbc on the western / eastern / southern / northern edge
   int nk, masked;
   double dt2d;
+  // climatology nudging switched on for this variable (LnudgeM2CLM / LnudgeM3CLM / LnudgeTCLM): the coefficient array
+  // a RadNud edge takes its time scale from (M2nudgcof, M3nudgcof, Tnudgcof of the tracer's ic), and obcfac; or nullptr
+  const double *C;
+  double obcfac;
 };
 
 __device__ __forceinline__ double bc_radiate(double xb_old, double x1_old, double x1, double x2, double gL, double gR,
@@ -155,7 +159,16 @@ __global__ void k_edge_bc(const RomsDev *__restrict__ c, BcArgs a)
     if (a.var == LBV_ZETA && side == LBS_SOUTH) { gLb = gL; gRb = gR; }
     x = bc_radiate(O[B], O[P1], X[P1], X[Q2], gL, gR, inward, p.radiation_2d != 0, gLb, gRb);
     if (code == LBC_RADIATION_NUDGING) {            // explicit nudging towards the boundary data, zetabc.F:162-166 ...
-      double tau = inward ? p.obc_in[side][a.var] : p.obc_out[side][a.var];
+      double obc_out = p.obc_out[side][a.var], obc_in = p.obc_in[side][a.var];
+      if (a.C) {
+        // the coefficient at the edge: tracers at the boundary point (t3dbc_im.F:119-126), momentum the mean of the two
+        // rho-points around the velocity point, lower index first (u2dbc_im.F:149-158, v2dbc_im.F:151-158, u3dbc_im.F:113,
+        // v3dbc_im.F:113 and the other edges' blocks)
+        const double *Ck = a.C + kb;
+        obc_out = utype ? 0.5 * (Ck[B - 1] + Ck[B]) : vtype ? 0.5 * (Ck[B - ni] + Ck[B]) : Ck[B];
+        obc_in = a.obcfac * obc_out;
+      }
+      double tau = inward ? obc_in : obc_out;
       tau = tau * (a.var <= LBV_VBAR ? a.dt2d : p.dt);
       x = x + tau * (a.D[B + kb] - O[B]);
     }
@@ -339,6 +352,10 @@ static BcArgs bc_args(int var, double *X, int nk)
   a.masked = g_ctx.p.masking != 0;
   for (int sd = 0; sd < 4; sd++) a.code[sd] = var >= 0 ? lbc_code(g_ctx.p, sd, var) : LBC_GRADIENT;
   if (var < 0) a.masked = 0;
+  const RomsClima &C = g_ctx.hostc.clima;
+  a.obcfac = C.obcfac;
+  if ((var == LBV_UBAR || var == LBV_VBAR) && C.m2) a.C = C.M2nudgcof;
+  if ((var == LBV_U || var == LBV_V) && C.m3) a.C = C.M3nudgcof;
   return a;
 }
 
@@ -453,6 +470,9 @@ int bc_t3d(int nout, int itrc, int nstp)
   BcArgs a = bc_args(LBV_T, g_ctx.dev[FID_t] + ((long)(nout - 1) + 3L * (itrc - 1)) * n3r, g_ctx.b.N);
   a.Xold = g_ctx.dev[FID_t] + ((long)(nstp - 1) + 3L * (itrc - 1)) * n3r;
   a.D = g_ctx.dev[FID_t_bry] + (long)(itrc - 1) * n3r;
+  // the compact index the callers of t3dbc_tile count (step3d_t.F:1551-1560, pre_step3d.F:1126-1130, ini_fields.F:602-607)
+  const int ic = g_ctx.hostc.clima.ic[itrc - 1];
+  if (ic > 0) a.C = g_ctx.hostc.clima.Tnudgcof + (long)(ic - 1) * n3r;
   return edge_bc(a);
 }
 int bc_w3d(double *A)

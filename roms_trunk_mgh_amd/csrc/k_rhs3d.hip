@@ -110,6 +110,7 @@ __device__ __forceinline__ void rhs3d_lds_body(const RomsDev *__restrict__ c, in
   L.s_edge = b.south_edge && !b.NSperiodic; L.n_edge = b.north_edge && !b.NSperiodic;
   L.w_edge = b.west_edge && !b.EWperiodic;  L.e_edge = b.east_edge && !b.EWperiodic;
   const bool cor = p.uv_cor != 0, curv = p.curvgrid != 0 && p.uv_adv != 0, adv = p.uv_adv != 0;
+  const bool nudge = c->clima.m3 != 0;                 // LnudgeM3CLM (uniform)
   const int t = L.at(i, j);
   const int tid = threadIdx.y * BLK_X + threadIdx.x;
   // per-thread constants of the cell terms
@@ -219,6 +220,18 @@ __device__ __forceinline__ void rhs3d_lds_body(const RomsDev *__restrict__ c, in
         cell(t, dndx0, dmde0, a0, b0);
         if (do_u) { cell(t - 1, dndxw, dmdew, a1, b1); ruv = ruv + 0.5 * (a0 + a1); }
         if (do_v) { cell(t - TP, dndxs, dmdes, a1, b1); rvv = rvv - 0.5 * (b0 + b1); }
+      }
+      if (nudge) {                                     // nudging of 3-D momentum climatology, rhs3d.F:571-594
+        const long ck = c0 + (long)(k - 1) * nij;
+        const gcd_t cof = (gcd_t)c->clima.M3nudgcof;
+        if (do_u) {
+          const double cff = 0.25 * (cof[ck - 1] + cof[ck]) * GF(om_u)[c0] * GF(on_u)[c0];
+          ruv = ruv + cff * (bHz[t - 1] + bHz[t]) * (((gcd_t)c->clima.uclm)[ck] - bU[t]);
+        }
+        if (do_v) {
+          const double cff = 0.25 * (cof[ck - ni] + cof[ck]) * GF(om_v)[c0] * GF(on_v)[c0];
+          rvv = rvv + cff * (bHz[t - TP] + bHz[t]) * (((gcd_t)c->clima.vclm)[ck] - bV[t]);
+        }
       }
       if (adv) {
         if (do_u) {

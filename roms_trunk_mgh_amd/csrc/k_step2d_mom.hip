@@ -396,6 +396,18 @@ k2d_mom_lds(const RomsDev *__restrict__ c, S2 s, const double *__restrict__ DUon
     if (do_u) rhs_u = rhs_u - c->ws2[22][a];
     if (do_v) rhs_v = rhs_v - c->ws2[23][a];
   }
+  // ---- nudging of 2-D momentum climatology, :1822-1845 (the coefficient is a full 2-D array, never a row value) ----
+  if (c->clima.m2) {
+    const gcd_t cof = (gcd_t)c->clima.M2nudgcof;
+    if (do_u) {
+      const double cff = 0.25 * (cof[a - 1] + cof[a]) * GF(om_u)[a] * MT(on_u, a, j);
+      rhs_u = rhs_u + cff * (Dw + D0) * (((gcd_t)c->clima.ubarclm)[a] - sU[t]);
+    }
+    if (do_v) {
+      const double cff = 0.25 * (cof[a - ni] + cof[a]) * MT(om_v, a, j) * GF(on_v)[a];
+      rhs_v = rhs_v + cff * (Ds + D0) * (((gcd_t)c->clima.vbarclm)[a] - sV[t]);
+    }
+  }
   // ---- coupling between 2-D and 3-D equations, :1884-2065 ----
   double rf_u = 0.0, rf_v = 0.0;                        // rufrc / rvfrc of the first predictor (WET: scaled below)
   if (s.iif == 1 && s.predictor) {

@@ -663,6 +663,30 @@ int launch_nmax(int nnew, int itrc0, int ntr)
   return 0;
 }
 
+// Nudging towards the tracer climatology, step3d_t.F:1572-1584, and the land/sea mask that follows it (:1590-1596):
+//   t(nnew) = t(nnew) + dt * Tnudgcof(ic) * (tclm(ic) - t(nnew))      on IstrR:IendR, JstrR:JendR
+// after t3dbc_tile (the radiation condition reads the un-nudged interior, and the boundary points are nudged too),
+// before the exchange.  One thread per point, all nudged tracers in one launch (blockIdx.z = level + N * (ic-1)),
+// consecutive lanes along i: three reads and one write of a double per point.  t(nnew) arrives masked (the advection
+// kernel and t3dbc_tile end with the mask), so a land point stays a zero of either sign.
+__global__ void __launch_bounds__(BLK_X *BLK_Y)
+k_t_nudge(const RomsDev *__restrict__ c, int nnew)
+{
+  DEV_PROLOGUE(c)
+  const RomsClima &C = c->clima;
+  const int i = b.IstrR + blockIdx.x * BLK_X + threadIdx.x, j = b.JstrR + blockIdx.y * BLK_Y + threadIdx.y;
+  if (i > b.IendR || j > b.JendR) return;
+  const int k = blockIdx.z % N + 1, ic = blockIdx.z / N + 1;
+  const int itrc = C.itrc[ic - 1];
+  const long q2 = I2(i, j), q = q2 + (long)(k - 1) * nij;
+  const gd_t t = (gd_t)(c->F.t + ((long)(nnew - 1) + 3L * (itrc - 1)) * n3r);
+  const long qc = q + (long)(ic - 1) * n3r;
+  const double t0 = t[q];
+  double tn = t0 + c->p.dt * ((gcd_t)C.Tnudgcof)[qc] * (((gcd_t)C.tclm)[qc] - t0);
+  if (c->p.masking) tn = tn * GF(rmask)[q2];
+  t[q] = tn;
+}
+
 }  // namespace
 
 extern "C" int roms_hip_step3d_t(const roms_step_idx_t *s)
@@ -729,6 +753,12 @@ extern "C" int roms_hip_step3d_t(const roms_step_idx_t *s)
   // t3dbc_tile + periodic wrap / mp_exchange4d, step3d_t.F:1564-1626
   for (int it = 1; it <= b.NT; it++)
     if ((rc = bc_t3d(s->nnew, it, s->nstp))) return rc;
+  if (g_ctx.hostc.clima.nt > 0) {
+    ScopedTimer tm("step3d_t_nudge");
+    const dim3 grid((b.IendR - b.IstrR + BLK_X) / BLK_X, (b.JendR - b.JstrR + BLK_Y) / BLK_Y, b.N * g_ctx.hostc.clima.nt);
+    hipLaunchKernelGGL(k_t_nudge, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nnew);
+    KERNEL_CHECK("k_t_nudge");
+  }
   const long n3r = (long)(b.UBi - b.LBi + 1) * (b.UBj - b.LBj + 1) * b.N;
   halo_batch_begin();
   for (int it = 1; it <= b.NT; it++)

@@ -36,6 +36,19 @@ struct RomsSrc {
   double *save;               // [n * N] the mass fluxes of the source faces across k_uv_column (k_step3d_uv.hip)
 };
 
+// The climatology CLIMA(ng) (mod_clima.F:190-261) with LnudgeM2CLM / LnudgeM3CLM / LnudgeTCLM (roms_hip_set_clima):
+// device copies of the nudging coefficients and of the fields they relax towards, host extents (LBi:UBi, LBj:UBj
+// [, N][, NTCLM]).  Every test of a flag is wave-uniform; with all flags zero no kernel reads a pointer.
+struct RomsClima {
+  int m2, m3, nt;             // LnudgeM2CLM, LnudgeM3CLM, NTCLM = number of nudged tracers
+  int ic[ROMS_MAXNT];         // compact index ic (1-based) of tracer itrc, 0 = not nudged (step3d_t.F:1551-1560)
+  int itrc[ROMS_MAXNT];       // tracer (1-based) of compact index ic
+  double obcfac;              // obc_in = obcfac * obc_out on a RadNud edge (t3dbc_im.F:119-126)
+  const double *M2nudgcof, *ubarclm, *vbarclm;   // [nij]
+  const double *M3nudgcof, *uclm, *vclm;         // [nij * N]
+  const double *Tnudgcof, *tclm;                 // [nij * N * nt]
+};
+
 struct RomsDev {
   roms_bounds_t b;
   roms_params_t p;
@@ -45,6 +58,7 @@ struct RomsDev {
   double *ws2[32];      // 2-D scratch, each nij doubles
   const double *rowm;   // row table of the i-uniform metric arrays (k_step2d_mom.hip), or nullptr
   RomsSrc src;          // point sources (LuvSrc), n = 0 without
+  RomsClima clima;      // climatology nudging, all flags zero without
 };
 
 struct RomsCtx {
@@ -330,7 +344,7 @@ int bc_u2d(int kout, const roms_step_idx_t *s);
 int bc_v2d(int kout, const roms_step_idx_t *s);
 int bc_u3d(int nout, int nstp);
 int bc_v3d(int nout, int nstp);
-int bc_t3d(int nout, int itrc, int nstp);
+int bc_t3d(int nout, int itrc, int nstp);   // the compact climatology index ic of itrc comes from the RomsClima block
 bool lbc2d_all_closed();
 int lbc_code(const roms_params_t &p, int sd, int v);   // effective enum roms_lbc of variable v on side sd
 int bc_w3d(double *A);

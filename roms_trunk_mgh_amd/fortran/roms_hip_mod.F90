@@ -297,6 +297,19 @@ MODULE roms_hip_mod
       INTEGER(c_int), INTENT(in) :: Isrc(*), Jsrc(*), LtracerSrc(*)
       REAL(c_double), INTENT(in) :: Dsrc(*), Qbar(*), Qsrc(*), Tsrc(*)
     END FUNCTION
+    !  LnudgeM2CLM, LnudgeM3CLM, LnudgeTCLM: the nudging coefficients and climatology fields of CLIMA(ng) (mod_clima.F);
+    !  LnudgeTCLM(NT) = MERGE(1, 0, LtracerCLM(itrc,ng).and.LnudgeTCLM(itrc,ng)); obcfac = obcfac(ng).  After
+    !  roms_hip_set_params, and after every set_data that moves the climatology (an array left out on a later call --
+    !  C_NULL_PTR -- keeps its copy)
+    INTEGER(c_int) FUNCTION roms_hip_set_clima (LnudgeM2CLM, M2nudgcof, ubarclm, vbarclm,                          &
+   &                        LnudgeM3CLM, M3nudgcof, uclm, vclm, LnudgeTCLM, Tnudgcof, tclm, obcfac)                &
+   &                        BIND(C, name='roms_hip_set_clima')
+      IMPORT :: c_int, c_double, c_ptr
+      INTEGER(c_int), VALUE :: LnudgeM2CLM, LnudgeM3CLM
+      TYPE(c_ptr), VALUE :: M2nudgcof, ubarclm, vbarclm, M3nudgcof, uclm, vclm, Tnudgcof, tclm
+      INTEGER(c_int), INTENT(in) :: LnudgeTCLM(*)
+      REAL(c_double), VALUE :: obcfac
+    END FUNCTION
     !  GLS_MIXING: gls_prestep (main3d.F:567) and gls_corstep (main3d.F:793)
     INTEGER(c_int) FUNCTION roms_hip_gls_prestep (s) BIND(C, name='roms_hip_gls_prestep')
       IMPORT :: c_int, roms_step_idx_t
@@ -324,7 +337,7 @@ MODULE roms_hip_mod
   PUBLIC :: roms_hip_step3d_uv, roms_hip_step3d_t, roms_hip_bulk_flux, roms_hip_set_vbc, roms_hip_lmd_vmix
   PUBLIC :: roms_hip_ana_srflux, roms_hip_wvelocity, roms_hip_diag, roms_hip_snapshot_begin, roms_hip_snapshot_end
   PUBLIC :: roms_hip_ini_zeta, roms_hip_ini_fields, roms_hip_gls_prestep, roms_hip_gls_corstep, roms_hip_wetdry
-  PUBLIC :: roms_hip_set_sources
+  PUBLIC :: roms_hip_set_sources, roms_hip_set_clima
   PUBLIC :: roms_hip_entry, roms_hip_make_idx, roms_hip_status
 
 CONTAINS
