@@ -1,8 +1,15 @@
-// advect.h -- tracer advective flux stencils shared by the predictor
-// (pre_step3d.F:342-915) and the corrector (step3d_t.F:363-1210): the
-// reference writes the same C2 / U3 / A4 / C4 flux formulas in both files.
+// advect.h -- the tracer column shared by the predictor k_pre_t (pre_step3d.F:342-915) and the correctors
+// k_step3d_t_pipe / k_step3d_t_hsimt (step3d_t.F:363-1455): the reference writes the same C2 / U3 / A4 / C4 flux
+// formulas, wall rules and whole-column reconstructions in both files; here each is stated once.
+//   flux formulas     hflux<>, vflux<>
+//   column frame      tile_column(), column_walls(), tracer_level(), column_fields(), tracer_akt()
+//   whole column      a4_slopes<>(), spline_w<>()
+//   one level         cell_faces<>(), vflux_level<>(), thomas_row()
+//   host              adv_pair(), adv_run_length(), kernel_for_n()
+// The device functions take loaded values: which load is issued when stays the kernel's business.
 #pragma once
-#include "roms_hip.h"
+#include <type_traits>
+#include "roms_dev.h"
 
 template <int HADV>
 __device__ __forceinline__ double hflux(double Hflx, double tm1, double t0, double dm1, double d0, double dp1)
@@ -60,3 +67,215 @@ __device__ __forceinline__ double vflux(int k, int N, double Wk, double tkm1, do
   }
 }
 
+// ---------------------------------------------------------------------------
+// Column frame
+// ---------------------------------------------------------------------------
+// (i, j, tracer) of the calling thread in a launch over grid_tile_tracer(); !valid: the thread has no column.
+// (Returned by value with the early exits of the kernels' former text: out-parameters cost two VGPRs here.)
+struct TileCol { int i, j, itrc; bool valid; };
+__device__ __forceinline__ TileCol tile_column(const roms_bounds_t &b, int itrc0, int ntr)
+{
+  const TileTr tt = decode_tile_tracer(b.Iend - b.Istr + 1, b.Jend - b.Jstr + 1, ntr);
+  TileCol r;
+  r.valid = false;
+  if (!tt.valid) return r;
+  r.i = b.Istr + tt.bx * BLK_X + threadIdx.x;
+  r.j = b.Jstr + tt.by * BLK_Y + threadIdx.y;
+  r.itrc = itrc0 + tt.itr;             // 1-based tracer index
+  if (r.i > b.Iend || r.j > b.Jend) return r;
+  r.valid = true;
+  return r;
+}
+// The cell lies on a physical (closed, non-periodic) edge: the first difference outside the wall face is a copy of
+// the wall face's, FX(Istr-1) = FX(Istr), FX(Iend+2) = FX(Iend+1) and likewise FE (step3d_t.F:700-715, :741-760;
+// pre_step3d.F:401-412), so the outer stencil point of a wall row is not used -- what the caller loads in its place
+// (a valid address, a literal 0) is the caller's business.
+struct Walls { bool s, n, w, e; };
+__device__ __forceinline__ Walls column_walls(const RomsDev *__restrict__ c, int i, int j)
+{
+  const roms_bounds_t &b = c->b;       // (through c, as the kernels read it: with a reference parameter the compiler
+  Walls wl;                            // loads every member up front instead of short-circuiting)
+  wl.s = b.south_edge && !b.NSperiodic && j == b.Jstr;
+  wl.n = b.north_edge && !b.NSperiodic && j == b.Jend;
+  wl.w = b.west_edge && !b.EWperiodic && i == b.Istr;
+  wl.e = b.east_edge && !b.EWperiodic && i == b.Iend;
+  return wl;
+}
+// t(:,:,:,lev,itrc), lev = nstp | 3 | nnew; n3r = points of a rho-array.  (Generic pointer: cast to gcd_t / gd_t.)
+__device__ __forceinline__ double *tracer_level(const RomsDev *__restrict__ c, int lev, int itrc, long n3r)
+{
+  return c->F.t + ((long)(lev - 1) + 3L * (itrc - 1)) * n3r;
+}
+// the tracer-independent fields of the column sweep
+struct ColFields { gcd_t Huon, Hvom, W, Hz; };
+__device__ __forceinline__ ColFields column_fields(const RomsDev *__restrict__ c)
+{
+  ColFields f;
+  f.Huon = (gcd_t)c->F.Huon;
+  f.Hvom = (gcd_t)c->F.Hvom;
+  f.W = (gcd_t)c->F.W;
+  f.Hz = (gcd_t)c->F.Hz;
+  return f;
+}
+// Akt(:,:,:,MIN(itrc,NAT)); n3w = points of a W-array
+__device__ __forceinline__ gcd_t tracer_akt(const RomsDev *__restrict__ c, int itrc, long n3w)
+{
+  const int ltrc = itrc < c->b.NAT ? itrc : c->b.NAT;
+  return (gcd_t)(c->F.Akt + (long)(ltrc - 1) * n3w);
+}
+
+// ---------------------------------------------------------------------------
+// Vertical schemes that need the whole column first (c0 = index of (i,j,1), nij = level stride)
+// ---------------------------------------------------------------------------
+// A4: harmonic-mean slopes a4cf[1..N] of the vertical differences FC(k) = t(k+1)-t(k), FC(N) = FC(N-1), FC(0) = FC(1)
+// (step3d_t.F:943-962, pre_step3d.F:671-690); t = t(nstp) in the predictor, t(3) in the corrector
+template <int NMAX>
+__device__ __forceinline__ void a4_slopes(gcd_t t, long c0, long nij, int N, double *a4cf)
+{
+  const double eps = 1.0E-16;
+  double dprev = 0.0, tk = t[c0];
+#pragma unroll
+  for (int k = 1; k <= NMAX; k++) {
+    if (k <= N) {
+      double dk;
+      if (k < N) { const double tk1 = t[c0 + (long)k * nij]; dk = tk1 - tk; tk = tk1; }
+      else dk = dprev;
+      if (k == 1) dprev = dk;
+      const double cff = 2.0 * dk * dprev;
+      a4cf[k] = (cff > eps) ? cff / (dk + dprev) : 0.0;
+      dprev = dk;
+    }
+  }
+}
+// SPLINES: parabolic-spline reconstruction of t at W-points times W, spl[0..N] with zeroed ends.  The two files
+// differ in the end conditions only: step3d_t.F:894-930 has 2 / 1 / 2 / 1 where pre_step3d.F:622-650 (PRED) has
+// 1.5 / 0.5 / 3 / 2.
+template <bool PRED, int NMAX>
+__device__ __forceinline__ void spline_w(gcd_t t, gcd_t Hz, gcd_t W, long c0, long nij, int N, double *spl)
+{
+  constexpr double bot_t = PRED ? 1.5 : 2.0, bot_cf = PRED ? 0.5 : 1.0, top_t = PRED ? 3.0 : 2.0, top_cf = PRED ? 2.0 : 1.0;
+  double cfs[NMAX + 1];
+  spl[0] = bot_t * t[c0];
+  cfs[1] = bot_cf;
+#pragma unroll
+  for (int k = 1; k < NMAX; k++) {
+    if (k <= N - 1) {
+      const double hk = Hz[c0 + (long)(k - 1) * nij], hk1 = Hz[c0 + (long)k * nij];
+      const double cff = 1.0 / (2.0 * hk + hk1 * (2.0 - cfs[k]));
+      cfs[k + 1] = cff * hk;
+      spl[k] = cff * (3.0 * (hk * t[c0 + (long)k * nij] + hk1 * t[c0 + (long)(k - 1) * nij]) - hk1 * spl[k - 1]);
+    }
+  }
+#pragma unroll
+  for (int k = 1; k <= NMAX; k++)
+    if (k == N) spl[k] = (top_t * t[c0 + (long)(N - 1) * nij] - spl[k - 1]) / (top_cf - cfs[k]);
+#pragma unroll
+  for (int k = NMAX - 1; k >= 0; k--) {
+    if (k <= N - 1) {
+      spl[k] = spl[k] - cfs[k + 1] * spl[k + 1];
+      spl[k + 1] = W[c0 + (long)(k + 1) * nij] * spl[k + 1];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k <= NMAX; k++) if (k == 0 || k == N) spl[k] = 0.0;
+}
+
+// ---------------------------------------------------------------------------
+// One level of the column
+// ---------------------------------------------------------------------------
+// the eight horizontal neighbours of a cell (x = along i, y = along j) and the transports of its four faces
+struct HStencil { double xm2, xm1, xp1, xp2, ym2, ym1, yp1, yp2, hu0, hu1, hv0, hv1; };
+struct Faces { double FXi, FXip1, FEj, FEjp1; };
+// Horizontal advective fluxes through the four faces of the cell with value tk (step3d_t.F:596-828 and the same
+// text of pre_step3d.F).  MASK (MASKING): the first differences are multiplied by umask / vmask of their face (step3d_t.F:603,
+// :667; pre_step3d.F:398, :463), the masks read per level at c0 (cache hits) rather than held in registers.
+template <int HADV, bool MASK>
+__device__ __forceinline__ Faces cell_faces(double tk, const HStencil &s, const Walls &wl, const RomsDev *__restrict__ c,
+                                            long c0, long ni)
+{
+  double dxm1 = s.xm1 - s.xm2, dx0 = tk - s.xm1, dxp1 = s.xp1 - tk, dxp2 = s.xp2 - s.xp1;
+  double dy0 = tk - s.ym1, dyp1 = s.yp1 - tk;
+  double dym1 = s.ym1 - s.ym2, dyp2 = s.yp2 - s.yp1;
+  if constexpr (MASK) {
+    const gcd_t um = (gcd_t)c->F.umask, vm = (gcd_t)c->F.vmask;
+    dxm1 = dxm1 * um[c0 + (wl.w ? 0 : -1)]; dx0 = dx0 * um[c0]; dxp1 = dxp1 * um[c0 + 1];
+    dxp2 = dxp2 * um[c0 + (wl.e ? 1 : 2)];
+    dy0 = dy0 * vm[c0]; dyp1 = dyp1 * vm[c0 + ni];
+    dym1 = dym1 * vm[c0 + (wl.s ? 0 : -ni)]; dyp2 = dyp2 * vm[c0 + (wl.n ? ni : 2 * ni)];
+  }
+  if (wl.s) dym1 = dy0;
+  if (wl.n) dyp2 = dyp1;
+  if (wl.w) dxm1 = dx0;
+  if (wl.e) dxp2 = dxp1;
+  Faces f;
+  f.FXi = hflux<HADV>(s.hu0, s.xm1, tk, dxm1, dx0, dxp1);
+  f.FXip1 = hflux<HADV>(s.hu1, tk, s.xp1, dx0, dxp1, dxp2);
+  f.FEj = hflux<HADV>(s.hv0, s.ym1, tk, dym1, dy0, dyp1);
+  f.FEjp1 = hflux<HADV>(s.hv1, tk, s.yp1, dy0, dyp1, dyp2);
+  return f;
+}
+// Vertical advective flux through the top face of level k = 1..N: zero at the surface, the spline value, or the
+// stencil of the scheme (with the A4 slopes of the two levels).  spl / a4cf: the column of the scheme, unused otherwise.
+template <int VADV>
+__device__ __forceinline__ double vflux_level(int k, int N, double Wk, double tkm1, double tk, double tkp1, double tkp2,
+                                              const double *spl, const double *a4cf)
+{
+  if (k == N) return 0.0;
+  if constexpr (VADV == ADV_SPLINES) return spl[k];
+  else {
+    double cfk = 0.0, cfk1 = 0.0;
+    if constexpr (VADV == ADV_A4) { cfk = a4cf[k]; cfk1 = a4cf[k + 1]; }
+    return vflux<VADV>(k, N, Wk, tkm1, tk, tkp1, tkp2, cfk, cfk1);
+  }
+}
+// Row k-1 of the forward elimination of the implicit vertical diffusion in spline form, step3d_t.F:1376-1410, formed
+// while the upward sweep is at level k: *_m1 = level k-1, akt_m2 / akt_m1 / akt_0 = Akt(k-2) / Akt(k-1) / Akt(k),
+// t_m1 / t_0 = the advected tracer of the two levels, CFm / DCm = CF(k-2) / DC(k-2); sets CF(k-1), DC(k-1).
+__device__ __forceinline__ void thomas_row(double dt, double hz_m1, double ohz_m1, double hz, double ohz, double akt_m2,
+                                           double akt_m1, double akt_0, double t_m1, double t_0, double CFm, double DCm,
+                                           double &CF, double &DC)
+{
+  const double cff6 = 1.0 / 6.0, cff3r = 1.0 / 3.0;
+  const double fc = cff6 * hz_m1 - dt * akt_m2 * ohz_m1;
+  const double cf = cff6 * hz - dt * akt_0 * ohz;
+  const double bc = cff3r * (hz_m1 + hz) + dt * akt_m1 * (ohz_m1 + ohz);
+  const double cff = 1.0 / (bc - fc * CFm);
+  CF = cff * cf;
+  DC = cff * (t_0 - t_m1 - fc * DCm);
+}
+
+// ---------------------------------------------------------------------------
+// Host side of the two entries (roms_hip_pre_step3d, roms_hip_step3d_t)
+// ---------------------------------------------------------------------------
+// Key Hadv * 16 + Vadv of a scheme pair for the switch over the built kernels.  SU3 runs the kernels of C4 (the
+// "C4 / SU3" arms above) in the three pairs with SU3 that are built.
+static inline int adv_pair(int ha, int va)
+{
+  const int hv = ha * 16 + va;
+  switch (hv) {
+  case ADV_U3 * 16 + ADV_SU3:    return ADV_U3 * 16 + ADV_C4;
+  case ADV_SU3 * 16 + ADV_SU3:   return ADV_C4 * 16 + ADV_C4;
+  case ADV_SU3 * 16 + ADV_HSIMT: return ADV_C4 * 16 + ADV_HSIMT;
+  default:                       return hv;
+  }
+}
+// length of the run of consecutive tracers it, it+1, ... (1-based, up to NT) that share tracer it's scheme pair: one
+// launch per run (run-time selection per tracer, step3d_t.F:596+: one kernel per scheme, host dispatch)
+static inline int adv_run_length(const roms_params_t &p, int NT, int it)
+{
+  const int ha = p.Hadv[it - 1], va = p.Vadv[it - 1];
+  int n = 1;
+  while (it + n <= NT && p.Hadv[it + n - 1] == ha && p.Vadv[it + n - 1] == va) n++;
+  return n;
+}
+// The instantiation of a kernel template for columns of N levels: pick(NMAX) returns the kernel whose unrolled
+// column arrays hold NMAX = 16 / 32 / (48, where the caller has that one) / ROMS_MAXN levels.
+template <bool WITH48 = false, class Pick>
+static inline auto kernel_for_n(int N, Pick pick)
+{
+  if (N <= 16) return pick(std::integral_constant<int, 16>{});
+  if (N <= 32) return pick(std::integral_constant<int, 32>{});
+  if constexpr (WITH48)
+    if (N <= 48) return pick(std::integral_constant<int, 48>{});
+  return pick(std::integral_constant<int, ROMS_MAXN>{});
+}

@@ -27,31 +27,20 @@ __global__ void __launch_bounds__(BLK_X *BLK_Y)
 k_pre_t(const RomsDev *__restrict__ c, int nstp, int nnew, int first_step, int itrc0, int ntr)
 {
   DEV_PROLOGUE(c)
-  const TileTr tt = decode_tile_tracer(b.Iend - b.Istr + 1, b.Jend - b.Jstr + 1, ntr);
-  if (!tt.valid) return;
-  const int i = b.Istr + tt.bx * BLK_X + threadIdx.x;
-  const int j = b.Jstr + tt.by * BLK_Y + threadIdx.y;
-  const int itrc = itrc0 + tt.itr;
-  if (i > b.Iend || j > b.Jend) return;
+  const TileCol tc = tile_column(b, itrc0, ntr);
+  if (!tc.valid) return;
+  const int i = tc.i, j = tc.j, itrc = tc.itrc;
   const roms_params_t &p = c->p;
-  const int ltrc = itrc < b.NAT ? itrc : b.NAT;
   const double dt = p.dt;
-  const gcd_t ts = (gcd_t)(c->F.t + ((long)(nstp - 1) + 3L * (itrc - 1)) * n3r);
-  const gd_t t3 = (gd_t)(c->F.t + (2L + 3L * (itrc - 1)) * n3r);
-  const gd_t tn = (gd_t)(c->F.t + ((long)(nnew - 1) + 3L * (itrc - 1)) * n3r);
-  const gcd_t Huon = (gcd_t)(c->F.Huon);
-  const gcd_t Hvom = (gcd_t)(c->F.Hvom);
-  const gcd_t Wv = (gcd_t)(c->F.W);
-  const gcd_t Hz = (gcd_t)(c->F.Hz);
+  const gcd_t ts = (gcd_t)tracer_level(c, nstp, itrc, n3r);
+  const gd_t t3 = (gd_t)tracer_level(c, 3, itrc, n3r);
+  const gd_t tn = (gd_t)tracer_level(c, nnew, itrc, n3r);
+  const ColFields f = column_fields(c);
   const gcd_t z_r = (gcd_t)(c->F.z_r);
   const gcd_t z_w = (gcd_t)(c->F.z_w);
-  const gcd_t Akt = (gcd_t)(c->F.Akt + (long)(ltrc - 1) * n3w);
+  const gcd_t Akt = tracer_akt(c, itrc, n3w);
   const long c0 = I2(i, j);
-  const bool s_wall = b.south_edge && !b.NSperiodic && j == b.Jstr;
-  const bool n_wall = b.north_edge && !b.NSperiodic && j == b.Jend;
-  // physical western / eastern edges (pre_step3d.F:401-412: FX(Istr-1) = FX(Istr), FX(Iend+2) = FX(Iend+1))
-  const bool w_wall = b.west_edge && !b.EWperiodic && i == b.Istr;
-  const bool e_wall = b.east_edge && !b.EWperiodic && i == b.Iend;
+  const Walls wl = column_walls(c, i, j);
   // time-stepping weights, pre_step3d.F:586-600
   // (upstream predictors -- MPDATA, HSIMT -- use Gamma = 1/2; the horizontal part takes the weight of the horizontal
   // scheme, :557-563, the vertical part that of the vertical scheme, :793-799: they differ for "HSIMT vertically with
@@ -78,103 +67,39 @@ k_pre_t(const RomsDev *__restrict__ c, int nstp, int nnew, int first_step, int i
   // vertical schemes that need the whole column first
   double a4cf[(VADV == ADV_A4) ? NMAX + 2 : 1];
   double spl[(VADV == ADV_SPLINES) ? NMAX + 1 : 1];
-  if constexpr (VADV == ADV_A4) {
-    const double eps = 1.0E-16;
-    double dprev = 0.0, tk = ts[c0];
-#pragma unroll
-    for (int k = 1; k <= NMAX; k++) {
-      if (k <= N) {
-        double dk;
-        if (k < N) { const double tk1 = ts[c0 + (long)k * nij]; dk = tk1 - tk; tk = tk1; }
-        else dk = dprev;
-        if (k == 1) dprev = dk;
-        const double cf = 2.0 * dk * dprev;
-        a4cf[k] = (cf > eps) ? cf / (dk + dprev) : 0.0;
-        dprev = dk;
-      }
-    }
-  }
-  if constexpr (VADV == ADV_SPLINES) {
-    // pre_step3d.F:622-650 (note 1.5/0.5/3/2 instead of step3d_t's 2/1/2/1)
-    double cfs[NMAX + 1];
-    spl[0] = 1.5 * ts[c0];
-    cfs[1] = 0.5;
-#pragma unroll
-    for (int k = 1; k < NMAX; k++) {
-      if (k <= N - 1) {
-        const double hk = Hz[c0 + (long)(k - 1) * nij], hk1 = Hz[c0 + (long)k * nij];
-        const double cf = 1.0 / (2.0 * hk + hk1 * (2.0 - cfs[k]));
-        cfs[k + 1] = cf * hk;
-        spl[k] = cf * (3.0 * (hk * ts[c0 + (long)k * nij] + hk1 * ts[c0 + (long)(k - 1) * nij]) - hk1 * spl[k - 1]);
-      }
-    }
-#pragma unroll
-    for (int k = 1; k <= NMAX; k++)
-      if (k == N) spl[k] = (3.0 * ts[c0 + (long)(N - 1) * nij] - spl[k - 1]) / (2.0 - cfs[k]);
-#pragma unroll
-    for (int k = NMAX - 1; k >= 0; k--) {
-      if (k <= N - 1) {
-        spl[k] = spl[k] - cfs[k + 1] * spl[k + 1];
-        spl[k + 1] = Wv[c0 + (long)(k + 1) * nij] * spl[k + 1];
-      }
-    }
-#pragma unroll
-    for (int k = 0; k <= NMAX; k++) if (k == 0 || k == N) spl[k] = 0.0;
-  }
+  if constexpr (VADV == ADV_A4) a4_slopes<NMAX>(ts, c0, nij, N, a4cf);
+  if constexpr (VADV == ADV_SPLINES) spline_w<true, NMAX>(ts, f.Hz, f.W, c0, nij, N, spl);
 
   const bool src_cell = c->src.n > 0 && src_cell_any(c, c0, ni);      // LuvSrc: a face of this cell is a source face
   double tkm1 = 0.0, tk = ts[c0], tkp1 = (N >= 2) ? ts[c0 + nij] : 0.0, tkp2;
   double FCprev = 0.0;                                        // advective FC(k-1)
   double FDprev = dt * GF(btflx)[c0 + (long)(itrc - 1) * nij]; // diffusive FC(0)
-  double w_km1 = Wv[c0];
+  double w_km1 = f.W[c0];
   double zr_k = (cff3 != 0.0) ? z_r[c0] : 0.0;
   for (int k = 1; k <= N; k++) {
     const long ck = c0 + (long)(k - 1) * nij;
     tkp2 = (k + 2 <= N) ? ts[ck + 2 * nij] : 0.0;
     // ---- horizontal fluxes of t(nstp) ----
-    const double xm1 = ts[ck - 1], xp1 = ts[ck + 1];
-    const double xm2 = w_wall ? 0.0 : ts[ck - 2];
-    const double xp2 = e_wall ? 0.0 : ts[ck + 2];
-    const double ym1 = ts[ck - ni], yp1 = ts[ck + ni];
-    const double ym2 = s_wall ? 0.0 : ts[ck - 2 * ni];
-    const double yp2 = n_wall ? 0.0 : ts[ck + 2 * ni];
-    const double hu0 = Huon[ck], hu1 = Huon[ck + 1];
-    const double hv0 = Hvom[ck], hv1 = Hvom[ck + ni];
-    double dxm1 = xm1 - xm2, dx0 = tk - xm1, dxp1 = xp1 - tk, dxp2 = xp2 - xp1;
-    double dy0 = tk - ym1, dyp1 = yp1 - tk;
-    double dym1 = ym1 - ym2, dyp2 = yp2 - yp1;
-    if constexpr (MASK) {
-      const gcd_t um = (gcd_t)c->F.umask, vm = (gcd_t)c->F.vmask;
-      dxm1 = dxm1 * um[c0 + (w_wall ? 0 : -1)]; dx0 = dx0 * um[c0]; dxp1 = dxp1 * um[c0 + 1];
-      dxp2 = dxp2 * um[c0 + (e_wall ? 1 : 2)];
-      dy0 = dy0 * vm[c0]; dyp1 = dyp1 * vm[c0 + ni];
-      dym1 = dym1 * vm[c0 + (s_wall ? 0 : -ni)]; dyp2 = dyp2 * vm[c0 + (n_wall ? ni : 2 * ni)];
-    }
-    if (s_wall) dym1 = dy0;
-    if (n_wall) dyp2 = dyp1;
-    if (w_wall) dxm1 = dx0;
-    if (e_wall) dxp2 = dxp1;
-    double FXi = hflux<HADV>(hu0, xm1, tk, dxm1, dx0, dxp1);
-    double FXip1 = hflux<HADV>(hu1, tk, xp1, dx0, dxp1, dxp2);
-    double FEj = hflux<HADV>(hv0, ym1, tk, dym1, dy0, dyp1);
-    double FEjp1 = hflux<HADV>(hv1, tk, yp1, dy0, dyp1, dyp2);
+    HStencil s;
+    s.xm1 = ts[ck - 1]; s.xp1 = ts[ck + 1];
+    s.xm2 = wl.w ? 0.0 : ts[ck - 2];
+    s.xp2 = wl.e ? 0.0 : ts[ck + 2];
+    s.ym1 = ts[ck - ni]; s.yp1 = ts[ck + ni];
+    s.ym2 = wl.s ? 0.0 : ts[ck - 2 * ni];
+    s.yp2 = wl.n ? 0.0 : ts[ck + 2 * ni];
+    s.hu0 = f.Huon[ck]; s.hu1 = f.Huon[ck + 1];
+    s.hv0 = f.Hvom[ck]; s.hv1 = f.Hvom[ck + ni];
+    Faces fx = cell_faces<HADV, MASK>(tk, s, wl, c, c0, ni);
     if (src_cell)                                    // LuvSrc, pre_step3d.F:530-553
-      src_cell_fluxes<true>(c, c0, ck, ni, k, itrc, nullptr, FXi, FXip1, FEj, FEjp1);
-    const double hz = Hz[ck];
+      src_cell_fluxes<true>(c, c0, ck, ni, k, itrc, nullptr, fx.FXi, fx.FXip1, fx.FEj, fx.FEjp1);
+    const double hz = f.Hz[ck];
     const double tnn = tn[ck];
-    double t3v = hz * (cff1 * tk + cff2 * tnn) - cpp * (FXip1 - FXi + FEjp1 - FEj);
+    double t3v = hz * (cff1 * tk + cff2 * tnn) - cpp * (fx.FXip1 - fx.FXi + fx.FEjp1 - fx.FEj);
     // ---- vertical advective flux through the top face ----
-    const double w_k = Wv[ck + nij];
-    double FCk;
-    if (k == N) FCk = 0.0;
-    else if constexpr (VADV == ADV_SPLINES) FCk = spl[k];
-    else {
-      double cfk = 0.0, cfk1 = 0.0;
-      if constexpr (VADV == ADV_A4) { cfk = a4cf[k]; cfk1 = a4cf[k + 1]; }
-      FCk = vflux<VADV>(k, N, w_k, tkm1, tk, tkp1, tkp2, cfk, cfk1);
-    }
+    const double w_k = f.W[ck + nij];
+    const double FCk = vflux_level<VADV>(k, N, w_k, tkm1, tk, tkp1, tkp2, spl, a4cf);
     // ---- artificial continuity, pre_step3d.F:893-915 ----
-    const double DCk = 1.0 / (hz - cppv * (hu1 - hu0 + hv1 - hv0 + (w_k - w_km1)));
+    const double DCk = 1.0 / (hz - cppv * (s.hu1 - s.hu0 + s.hv1 - s.hv0 + (w_k - w_km1)));
     t3v = DCk * (t3v - cppv * (FCk - FCprev));
     t3[ck] = t3v;
     // ---- start of the corrector: explicit vertical flux, pre_step3d.F:917-1010 ----
@@ -281,29 +206,16 @@ k_pre_uv(const RomsDev *__restrict__ c, int nstp, int nnew, int nrhs, int stage)
 template <int HADV, int VADV>
 int launch_pre_t(const roms_step_idx_t *s, int itrc0, int ntr)
 {
+  typedef void (*PreKernel)(const RomsDev *, int, int, int, int, int);
   const roms_bounds_t &b = g_ctx.b;
   const dim3 grid = grid_tile_tracer(b.Iend - b.Istr + 1, b.Jend - b.Jstr + 1, ntr);
   const int first = s->iic == s->ntfirst;
   if (b.N > ROMS_MAXN) return roms_fail("roms_hip_pre_step3d", "N > 64 not instantiated");
-  constexpr bool maskable = HADV != ADV_MPDATA;        // the upstream predictor of MPDATA / HSIMT has no mask
-  if constexpr (maskable) {
-    if (g_ctx.p.masking) {
-      if (b.N <= 16)
-        hipLaunchKernelGGL((k_pre_t<HADV, VADV, 16, true>), grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nstp, s->nnew, first, itrc0, ntr);
-      else if (b.N <= 32)
-        hipLaunchKernelGGL((k_pre_t<HADV, VADV, 32, true>), grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nstp, s->nnew, first, itrc0, ntr);
-      else
-        hipLaunchKernelGGL((k_pre_t<HADV, VADV, ROMS_MAXN, true>), grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nstp, s->nnew, first, itrc0, ntr);
-      KERNEL_CHECK("k_pre_t");
-      return 0;
-    }
-  }
-  if (b.N <= 16)
-    hipLaunchKernelGGL((k_pre_t<HADV, VADV, 16, false>), grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nstp, s->nnew, first, itrc0, ntr);
-  else if (b.N <= 32)
-    hipLaunchKernelGGL((k_pre_t<HADV, VADV, 32, false>), grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nstp, s->nnew, first, itrc0, ntr);
-  else
-    hipLaunchKernelGGL((k_pre_t<HADV, VADV, ROMS_MAXN, false>), grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nstp, s->nnew, first, itrc0, ntr);
+  PreKernel kernel = kernel_for_n(b.N, [](auto nm) -> PreKernel { return k_pre_t<HADV, VADV, nm.value, false>; });
+  if constexpr (HADV != ADV_MPDATA)                    // the upstream predictor of MPDATA / HSIMT has no mask
+    if (g_ctx.p.masking)
+      kernel = kernel_for_n(b.N, [](auto nm) -> PreKernel { return k_pre_t<HADV, VADV, nm.value, true>; });
+  hipLaunchKernelGGL(kernel, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nstp, s->nnew, first, itrc0, ntr);
   KERNEL_CHECK("k_pre_t");
   return 0;
 }
@@ -320,15 +232,11 @@ static int pre_step3d_tracers(const roms_step_idx_t *s)
   {
     int it = 1;
     while (it <= b.NT) {
-      const int ha = p.Hadv[it - 1], va = p.Vadv[it - 1];
-      int n = 1;
-      while (it + n <= b.NT && p.Hadv[it + n - 1] == ha && p.Vadv[it + n - 1] == va) n++;
-      switch (ha * 16 + va) {
-      case ADV_U3 * 16 + ADV_C4:
-      case ADV_U3 * 16 + ADV_SU3:  rc = launch_pre_t<ADV_U3, ADV_C4>(s, it, n); break;
+      const int n = adv_run_length(p, b.NT, it);
+      switch (adv_pair(p.Hadv[it - 1], p.Vadv[it - 1])) {
+      case ADV_U3 * 16 + ADV_C4:   rc = launch_pre_t<ADV_U3, ADV_C4>(s, it, n); break;
       case ADV_A4 * 16 + ADV_A4:   rc = launch_pre_t<ADV_A4, ADV_A4>(s, it, n); break;
-      case ADV_C4 * 16 + ADV_C4:
-      case ADV_SU3 * 16 + ADV_SU3: rc = launch_pre_t<ADV_C4, ADV_C4>(s, it, n); break;
+      case ADV_C4 * 16 + ADV_C4:   rc = launch_pre_t<ADV_C4, ADV_C4>(s, it, n); break;
       case ADV_C2 * 16 + ADV_C2:   rc = launch_pre_t<ADV_C2, ADV_C2>(s, it, n); break;
       case ADV_U3 * 16 + ADV_SPLINES: rc = launch_pre_t<ADV_U3, ADV_SPLINES>(s, it, n); break;
       case ADV_C4 * 16 + ADV_SPLINES: rc = launch_pre_t<ADV_C4, ADV_SPLINES>(s, it, n); break;
@@ -340,7 +248,6 @@ static int pre_step3d_tracers(const roms_step_idx_t *s)
       // vertical predictor is the upstream step (:729-748, Gamma = 1/2 :793-799), the horizontal one the scheme's own
       case ADV_U3 * 16 + ADV_HSIMT: rc = launch_pre_t<ADV_U3, ADV_MPDATA>(s, it, n); break;
       case ADV_C4 * 16 + ADV_HSIMT: rc = launch_pre_t<ADV_C4, ADV_MPDATA>(s, it, n); break;
-      case ADV_SU3 * 16 + ADV_HSIMT: rc = launch_pre_t<ADV_C4, ADV_MPDATA>(s, it, n); break;
       case ADV_A4 * 16 + ADV_HSIMT: rc = launch_pre_t<ADV_A4, ADV_MPDATA>(s, it, n); break;
       case ADV_C2 * 16 + ADV_HSIMT: rc = launch_pre_t<ADV_C2, ADV_MPDATA>(s, it, n); break;
       default:

@@ -70,6 +70,60 @@ def test_step3d_t_schemes(hadv, vadv):
     assert all(v <= TOL for v in diffs.values()), diffs
 
 
+SCHEME_PAIRS = [("C2", "C2"), ("C4", "C4"), ("A4", "A4"), ("U3", "SPLINES"), ("A4", "SPLINES"), ("C4", "SPLINES")]
+
+
+@pytest.mark.parametrize("iic", [1, 5])
+@pytest.mark.parametrize("hadv,vadv", SCHEME_PAIRS)
+def test_pre_step3d_schemes(hadv, vadv, iic):
+    """The predictor's own vertical-scheme columns (A4 slopes of t(nstp), the spline with the predictor's end
+    conditions) and every horizontal stencil, with both time weightings (iic = 1: first step, iic = 5: LF-AM3)."""
+    ov = {"Hadv": hadv, "Vadv": vadv}
+    st_h, st_o, st0 = _run_pair("UPWELLING", "pre_step3d", util.step_idx(iic=iic), overrides=ov)
+    diffs = util.compare_states(st_h, st_o)
+    assert all(v <= TOL for v in diffs.values()), diffs
+    assert util.max_rel_diff(st_o["t"], st0["t"]) > 1e-6
+
+
+def _run_tracer_kernel(kernel, overrides, mask=None):
+    """_run_pair for pre_step3d / step3d_t on UPWELLING, with a land mask if asked for"""
+    import oracle
+    st0 = util.prepared_state("UPWELLING", overrides=overrides, mask=mask)
+    if kernel == "step3d_t":
+        util.hz_weighted_tnew(st0)
+    st_o, st_h = st0.copy(), st0.copy()
+    oracle.Oracle(st_o).call(kernel, util.step_idx())
+    h = hip.RomsHip(st_h)
+    try:
+        h.call(kernel, util.step_idx())
+        h.to_host()
+    finally:
+        h.close()
+    return st_h, st_o, st0
+
+
+@pytest.mark.parametrize("hadv,vadv", [("A4", "A4"), ("U3", "SPLINES")])
+@pytest.mark.parametrize("kernel", ["pre_step3d", "step3d_t"])
+def test_tracer_schemes_masked(kernel, hadv, vadv):
+    """MASKING through the masked face differences and the two whole-column vertical schemes, predictor and corrector"""
+    st_h, st_o, st0 = _run_tracer_kernel(kernel, {"Hadv": hadv, "Vadv": vadv}, mask="island")
+    assert st0.p.masking == 1 and (st0["rmask"] == 0).any()
+    diffs = util.compare_states(st_h, st_o)
+    assert all(v <= TOL for v in diffs.values()), diffs
+    assert util.max_rel_diff(st_o["t"], st0["t"]) > 1e-6
+
+
+@pytest.mark.parametrize("hadv,vadv", [("A4", "A4"), ("U3", "SPLINES")])
+@pytest.mark.parametrize("kernel", ["pre_step3d", "step3d_t"])
+def test_tracer_schemes_n52(kernel, hadv, vadv):
+    """N = 52 runs the largest instantiation (columns of up to 64 levels) with the whole-column arrays in use"""
+    st_h, st_o, st0 = _run_tracer_kernel(kernel, {"Hadv": hadv, "Vadv": vadv, "N": 52})
+    assert st0.b.N == 52
+    diffs = util.compare_states(st_h, st_o)
+    assert all(v <= TOL for v in diffs.values()), diffs
+    assert util.max_rel_diff(st_o["t"], st0["t"]) > 1e-6
+
+
 @pytest.mark.parametrize("config", CONFIGS)
 def test_prsgrd(config):
     st_h, st_o, st0 = _run_pair(config, "prsgrd", util.step_idx())
