@@ -194,6 +194,10 @@ int roms_hip_ini_fields(const roms_step_idx_t *s);
  * under its switch ts_dif2 / ts_dif4 / uv_vis2 / uv_vis4)
  *                                  ROMS/Nonlinear/rhs3d.F:25         */
 int roms_hip_rhs3d(const roms_step_idx_t *s);
+/* Fewest levels: roms_hip_pre_step3d, roms_hip_rhs3d_tile (so roms_hip_rhs3d) and roms_hip_step3d_t refuse N < 4
+ * ("needs N >= 4 levels"): their columns are walked with the levels k-1 .. k+2 held in registers, which the
+ * fourth-order vertical stencils need from N = 4 on.  roms_hip_prsgrd, roms_hip_wvelocity and the two GLS entries
+ * refuse N < 3.  Every other entry runs from N = 3 on (tests/test_gpu_wide.py, shape "thin"). */
 /* the pieces of rhs3d, exported for per-kernel parity tests */
 int roms_hip_pre_step3d(const roms_step_idx_t *s);  /* pre_step3d.F:39   */
 int roms_hip_prsgrd(const roms_step_idx_t *s);      /* prsgrd32.h:40     */

@@ -282,7 +282,7 @@ extern "C" int roms_hip_pre_step3d(const roms_step_idx_t *s)
   int rc = roms_entry_check("roms_hip_pre_step3d");
   if (rc) return rc;
   if ((rc = check_lbc())) return rc;
-  if (g_ctx.b.N < 4) return roms_fail("roms_hip_pre_step3d", "N < 4");
+  if (g_ctx.b.N < 4) return roms_fail("roms_hip_pre_step3d", "needs N >= 4 levels (the vertical stencils of the column read k-1 .. k+2)");
   ScopedTimer tm("pre_step3d");
   // (the reference does the tracers first; the two halves share no output)
   if ((rc = pre_step3d_uv(s))) return rc;

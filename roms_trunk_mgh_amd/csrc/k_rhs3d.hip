@@ -297,7 +297,7 @@ extern "C" int roms_hip_rhs3d_tile(const roms_step_idx_t *s)
   if ((rc = check_lbc())) return rc;
   ScopedTimer tm("rhs3d_tile");
   const roms_bounds_t &b = g_ctx.b;
-  if (b.N < 4) return roms_fail("roms_hip_rhs3d_tile", "N < 4");
+  if (b.N < 4) return roms_fail("roms_hip_rhs3d_tile", "needs N >= 4 levels (the vertical stencils of the column read k-1 .. k+2)");
   hipLaunchKernelGGL(k_rhs3d_lds, grid2d(b.Iend - b.Istr + 1, b.Jend - b.Jstr + 1), block2d(), 0, g_ctx.stream,
                      g_ctx.devc, s->nrhs);
   KERNEL_CHECK("k_rhs3d_lds");

@@ -500,7 +500,7 @@ extern "C" int roms_hip_step3d_t(const roms_step_idx_t *s)
   if ((rc = check_lbc())) return rc;
   const roms_bounds_t &b = g_ctx.b;
   const roms_params_t &p = g_ctx.p;
-  if (b.N < 4) return roms_fail("roms_hip_step3d_t", "N < 4");
+  if (b.N < 4) return roms_fail("roms_hip_step3d_t", "needs N >= 4 levels (the vertical stencils of the column read k-1 .. k+2)");
   if (!p.splines_vdiff)
     for (int it = 1; it <= b.NT; it++)
       if (p.Hadv[it - 1] == ADV_HSIMT || p.Vadv[it - 1] == ADV_HSIMT)

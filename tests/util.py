@@ -19,9 +19,34 @@ def step_idx(iic=3, ntfirst=1, nstp=1, nnew=2, nrhs=1, kstp=1, krhs=1, knew=2, i
 WET = False
 
 
-def synthetic_wet_masks(st, seed=5):
+def _cells(st, cells):
+    """Array indices of the global (i, j) rho points `cells` and of their periodic images among the ghost columns."""
+    b = st.b
+    out = []
+    for i, j in cells:
+        for ig in ((i - b.Lm, i, i + b.Lm) if b.EWperiodic else (i,)):
+            if b.LBi <= ig <= b.UBi and b.LBj <= j <= b.UBj:
+                out.append((ig - b.LBi, j - b.LBj))
+    return out
+
+
+def add_land(st, cells):
+    """Turn the rho points `cells` (global (i, j)) into land on top of the state's mask and rebuild umask / vmask / pmask
+    (ana.set_masks); the free surface is masked as ana.make_tile leaves it.  For coasts where a test needs them (across
+    a workgroup seam, tests/test_gpu_wide.py) -- ana.island_mask places its own by the grid's proportions."""
+    rm = st["rmask"].copy()
+    for q in _cells(st, cells):
+        rm[q] = 0.0
+    ana.set_masks(st, rm)
+    st["zeta"] *= st["rmask"][:, :, None]
+    st["Zt_avg1"] *= st["rmask"]
+    return st
+
+
+def synthetic_wet_masks(st, seed=5, dry=()):
     """Wet/dry masks from a seeded rho-point flag (dry blobs, single dry cells, dry stretches along the edges) by the
-    rules of wetdry.F:563-716 restated on whole arrays; independent of the oracle's loops."""
+    rules of wetdry.F:563-716 restated on whole arrays; independent of the oracle's loops.  dry: further dry rho points,
+    global (i, j)."""
     b = st.b
     rng = np.random.default_rng(seed)
     ii = np.arange(b.LBi, b.UBi + 1, dtype=np.float64)[:, None]
@@ -33,6 +58,8 @@ def synthetic_wet_masks(st, seed=5):
         wd[(iw - ic) ** 2 + (jj - jc) ** 2 <= r * r] = 0.0
     glob = rng.random((b.Lm + 8, b.Mm + 8)) < 0.03            # lone dry cells: a function of the global indices
     wd[glob[(iw.astype(int) + 3) % (b.Lm + 8), (jj.astype(int) + 3) % (b.Mm + 8)]] = 0.0
+    for q in _cells(st, dry):
+        wd[q] = 0.0
     wd *= st["rmask"]
     m, s = slice(0, -1), slice(1, None)
     um = np.zeros_like(wd)
@@ -57,17 +84,21 @@ def synthetic_wet_masks(st, seed=5):
     return wd
 
 
-def prepared_state(config, seed=1, NT=None, overrides=None, oracle_backend=None, mask=None, wet=None):
+def prepared_state(config, seed=1, NT=None, overrides=None, oracle_backend=None, mask=None, wet=None, land=(), dry=()):
     """A tile state with non-trivial velocities, fluxes, RHS terms and tracers at
     all time levels.  Deterministic (seeded).  mask = "island": a MASKING grid (ana.island_mask); the
-    prognostic fields are then zero on land, as the reference keeps them."""
+    prognostic fields are then zero on land, as the reference keeps them.  land / dry: further land cells (add_land;
+    needs a mask) and dry cells (needs wet), global (i, j)."""
     import oracle
     wet = WET if wet is None else wet
     if wet:
         overrides = dict(overrides or {}, wet_dry=1)
     st = ana.make_tile(config, perturb=1.0, NT=NT, overrides=overrides, mask=mask)
+    if land:
+        assert mask is not None
+        add_land(st, land)
     if wet:
-        synthetic_wet_masks(st)
+        synthetic_wet_masks(st, dry=dry)
     b = st.b
     rng = np.random.default_rng(seed)
     Lm, Mm, N = b.Lm, b.Mm, b.N
@@ -136,14 +167,14 @@ def prepared_state(config, seed=1, NT=None, overrides=None, oracle_backend=None,
     return st
 
 
-def kpp_state(config="BENCHMARK_TINY", mask=None):
+def kpp_state(config="BENCHMARK_TINY", mask=None, overrides=None, land=()):
     """prepared_state made into a meaningful input of KPP (lmd_vmix): density, buoyancy frequency, expansion
     coefficients from the (pinned) oracle rho_eos instead of the zeros prepared_state leaves; surface forcing that
     gives shallow boundary layers (ending inside the top layer: ksbl = N) in the western half of the domain and deep
     ones in the eastern half; surface / bottom diffusivities of salinity different from the temperature's (the routine
     leaves levels 0 and N alone and reads level N when ksbl = N)."""
     import oracle
-    st = prepared_state(config, mask=mask)
+    st = prepared_state(config, mask=mask, overrides=overrides, land=land)
     oracle.Oracle(st).call("rho_eos", step_idx())
     b = st.b
     st["stflux"][:, :, 0] += 1.0e-6
@@ -177,7 +208,7 @@ MY25_BUILDS = {  # ... and of the MY25_MIXING builds (upwelling_my25.h, benchmar
 }
 
 
-def gls_state(config, gls="k-epsilon", mask=None, basin=False, extra=None):
+def gls_state(config, gls="k-epsilon", mask=None, basin=False, extra=None, land=()):
     """prepared_state of a GLS_MIXING application with the CPP choices of the matching reference build, made into a
     meaningful input of gls_prestep / gls_corstep: bvf from the (pinned) oracle rho_eos with both signs of the
     stratification, energetic tke / gls at the three time levels, diffusivities above their backgrounds, W as omega
@@ -189,7 +220,7 @@ def gls_state(config, gls="k-epsilon", mask=None, basin=False, extra=None):
         ov["EWperiodic"] = False
     if extra:
         ov.update(extra)
-    st = prepared_state(config, mask=mask, overrides=ov)
+    st = prepared_state(config, mask=mask, overrides=ov, land=land)
     oracle.Oracle(st).call("rho_eos", step_idx())
     b, p = st.b, st.p
     ii = np.arange(b.LBi, b.UBi + 1, dtype=np.float64)[:, None, None]
@@ -291,7 +322,7 @@ def oracle_mpdata_adiff(st, oHz, Ta, t3):
     return Ta, Ua, Va, Wa
 
 
-def river_sources(st, kind="walls", same_tracer=False, seed=3):
+def river_sources(st, kind="walls", same_tracer=False, seed=3, at=()):
     """A point-source table for the state (LuvSrc; roms_trunk_mgh_amd/sources.py) and the switch in the parameters
     (a private copy of them).  kind = "walls": faces of the closed walls -- an inflow through the southern wall, and in a
     basin an inflow through the western wall and an outflow (a sink) through the eastern one; "coast": faces of the land
@@ -300,7 +331,8 @@ def river_sources(st, kind="walls", same_tracer=False, seed=3):
     both in the free surface and the tracers but only the later one in omega -- as written, omega.F:173-190; for the
     device-against-oracle tests); "all" = walls + wells (+ coast with a mask).  Qshape grows towards the surface;
     the first tracer comes with the river (LtracerSrc), the others do not -- unless same_tracer: then every tracer does,
-    with the value `same_tracer` (a river of ambient water)."""
+    with the value `same_tracer` (a river of ambient water).  at: further sources (I, J, Dsrc, fraction of the nominal
+    discharge), where a test needs them (tests/test_gpu_wide.py: beside a workgroup seam)."""
     from roms_trunk_mgh_amd import sources
     b = st.b
     N, NT = b.N, b.NT
@@ -331,6 +363,8 @@ def river_sources(st, kind="walls", same_tracer=False, seed=3):
                 elif not done_v and a == 0.0 and s == 1.0 and j > b.Mm // 2:
                     I.append(i); J.append(j); D.append(1.0); Q.append(-0.6 * q0); done_v = True     # southward, into the water
         assert done_u and done_v
+    for i, j, d, f in at:
+        I.append(i); J.append(j); D.append(float(d)); Q.append(f * q0)
     n = len(I)
     assert n > 0, kind
     w = np.linspace(1.0, 3.0, N)
