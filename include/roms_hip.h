@@ -87,6 +87,23 @@ enum roms_lbc {
 /* rows of roms_params_t.lbc = the state variables of LBC(:, isFsur / isUbar / isVbar / isUvel / isVvel / isTvar, ng) */
 enum roms_lbc_var { LBV_ZETA = 0, LBV_UBAR, LBV_VBAR, LBV_U, LBV_V, LBV_T, LBV_COUNT };
 enum roms_lbc_side { LBS_WEST = 0, LBS_EAST, LBS_SOUTH, LBS_NORTH };
+/* Momentum advection, roms_params_t.uv_adv: 0 = no UV_ADV; otherwise ROMS_UV_ADV(h, v) with the horizontal and the
+ * vertical scheme the application header selects.  1 = ROMS_UV_ADV(ROMS_UVH_U3, ROMS_UVV_C4W) is the reference's
+ * default: third-order upstream horizontally (rhs3d.F:706-730 ...), fourth-order centred vertical flux with the
+ * fourth-order averaged W (:1177-1256), fourth-order centred in step2d (step2d_LF_AM3.h:1077-1256).
+ *   ROMS_UVH_C2  UV_C2ADVECTION  second-order centred (rhs3d.F:605-656; in step2d step2d_LF_AM3.h:1026-1076)
+ *   ROMS_UVH_C4  UV_C4ADVECTION  fourth-order centred (rhs3d.F:685-705, :761-778, :829-849, :902-919)
+ *   ROMS_UVV_C2  UV_C2ADVECTION  (:1079-1107, :1330-1361)
+ *   ROMS_UVV_C4  UV_C4ADVECTION  weights 9/32, 1/32 on the velocity, the two-point sum of W (:1108-1176, :1362-1433)
+ *   ROMS_UVV_SPLINES  UV_SADVECTION  conservative parabolic splines (:1016-1078, :1267-1329)
+ * The six pairs the reference can be compiled to are accepted -- (U3, C4W), (U3, SPLINES), (C2, C2), (C2, SPLINES),
+ * (C4, C4), (C4, SPLINES) -- and every other value is refused by roms_hip_rhs3d_tile, roms_hip_rhs3d, roms_hip_step2d
+ * and roms_hip_step2d_loop (error text "uv_adv").  step2d takes the C2 form exactly when h = ROMS_UVH_C2. */
+enum roms_uv_hadv { ROMS_UVH_U3 = 0, ROMS_UVH_C2 = 1, ROMS_UVH_C4 = 2 };
+enum roms_uv_vadv { ROMS_UVV_C4W = 0, ROMS_UVV_C2 = 1, ROMS_UVV_C4 = 2, ROMS_UVV_SPLINES = 3 };
+#define ROMS_UV_ADV(h, v) (1 | ((h) << 4) | ((v) << 8))
+#define ROMS_UV_HADV(uv_adv) (((uv_adv) >> 4) & 15)      /* the two schemes of a valid non-zero uv_adv */
+#define ROMS_UV_VADV(uv_adv) (((uv_adv) >> 8) & 15)
 /* roms_params_t.gls_stability */
 enum roms_gls_stab { GLS_GALPERIN = 0, GLS_KANTHA_CLAYSON = 1, GLS_CANUTO_A = 2, GLS_CANUTO_B = 3 };
 

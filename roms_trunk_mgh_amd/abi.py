@@ -48,6 +48,18 @@ GLS_STAB = {"GALPERIN": 0, "KANTHA_CLAYSON": 1, "CANUTO_A": 2, "CANUTO_B": 3}   
 PGF = {"DJ_GRADPS": 0, "STANDARD": 1, "WJ_GRADP": 2, "PJ_GRADP": 3}         # enum roms_pgf (prsgrd.F:16-26)
 LBC_PERIODIC, LBC_CLOSED, LBC_GRADIENT, LBC_CLAMPED, LBC_CHAPMAN_IMPLICIT, LBC_FLATHER, LBC_RADIATION = range(7)
 LBC = {"Per": 0, "Clo": 1, "Gra": 2, "Cla": 3, "Cha": 4, "Fla": 5, "Rad": 6, "RadNud": 7, "Che": 8, "Shc": 9, "Red": 10}      # the keywords of roms_*.in
+UV_HADV = {"U3": 0, "C2": 1, "C4": 2}                     # enum roms_uv_hadv
+UV_VADV = {"C4W": 0, "C2": 1, "C4": 2, "SPLINES": 3}      # enum roms_uv_vadv
+# the pairs the reference can be compiled to (none; UV_SADVECTION; UV_C2ADVECTION [+ S]; UV_C4ADVECTION [+ S])
+UV_ADV_PAIRS = [("U3", "C4W"), ("U3", "SPLINES"), ("C2", "C2"), ("C2", "SPLINES"), ("C4", "C4"), ("C4", "SPLINES")]
+
+
+def uv_adv(h="U3", v="C4W"):
+    """ROMS_UV_ADV(h, v) of roms_hip.h: the value of roms_params_t.uv_adv for a horizontal and a vertical scheme
+    (names of UV_HADV / UV_VADV, or their codes); uv_adv() = 1 is the default pair."""
+    return 1 | (UV_HADV.get(h, h) << 4) | (UV_VADV.get(v, v) << 8)
+
+
 LBV = {"zeta": 0, "ubar": 1, "vbar": 2, "u": 3, "v": 4, "t": 5}
 LBS = {"west": 0, "east": 1, "south": 2, "north": 3}
 

@@ -191,7 +191,8 @@ def make_params(cfg, NT):
     p.Scoef = {"BENCHMARK": 7.6e-4, "UPWELLING": 0.0, "SEAMOUNT": 7.6e-4}[app]
     p.nonlin_eos = int(app == "BENCHMARK")
     # option switches of the application headers (ROMS/Include/{benchmark,upwelling,seamount}.h)
-    p.uv_adv, p.uv_cor = 1, 1
+    # momentum advection: uv_hadv = "U3" / "C2" / "C4", uv_vadv = "C4W" / "C2" / "C4" / "SPLINES" (abi.uv_adv); default 1
+    p.uv_adv, p.uv_cor = abi.uv_adv(cfg.get("uv_hadv", "U3"), cfg.get("uv_vadv", "C4W")), 1
     p.uv_vis2 = int(cfg.get("uv_vis2", app in ("BENCHMARK", "UPWELLING")))     # 2 = UV_VIS2 with MIX_GEO_UV (uv3dmix2_geo.h) instead of MIX_S_UV
     p.curvgrid = int(app == "BENCHMARK")
     p.var_rho_2d = 1                      # globaldefs.h:491-495, always with SOLVE3D

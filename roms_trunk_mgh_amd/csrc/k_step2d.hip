@@ -20,6 +20,7 @@
 
 int roms_entry_check(const char *name);
 int roms_launch_step2d_visc4(int krhs);      // k_uv3dmix2.hip
+int roms_uv_adv_check(const char *where);    // k_rhs3d.hip
 
 namespace {
 
@@ -370,6 +371,7 @@ extern "C" int roms_hip_step2d(const roms_step_idx_t *s)
 {
   int rc = roms_entry_check("roms_hip_step2d");
   if (rc) return rc;
+  if ((rc = roms_uv_adv_check("roms_hip_step2d"))) return rc;
   if ((rc = check_lbc())) return rc;
   if ((rc = roms_rowm_prepare())) return rc;
   ScopedTimer tm("step2d");
@@ -411,8 +413,9 @@ static int step2d_loop_body(roms_step_idx_t *s, int *indx1)
 }
 
 // One tile: the 2*nfast+1 launches of the loop are captured once per (indx1, nstp, start-up phase) into a
-// hipGraph and replayed -- the launch arguments of a replay are those of the capture, so the graphs are
-// dropped whenever bounds, parameters or a field registration change (step2d_graphs_release).  On several
+// hipGraph and replayed -- the launch arguments of a replay are those of the capture, and so is the
+// instantiation of the momentum kernel (row table, advection scheme); the graphs are dropped whenever bounds,
+// parameters -- uv_adv among them -- or a field registration change (step2d_graphs_release).  On several
 // tiles the loop contains host-side transport calls and runs eagerly.
 struct LoopGraph { hipGraphExec_t exec; int indx1_out; roms_step_idx_t s_out; };
 static std::map<int, LoopGraph> g_loop_graphs;
@@ -447,6 +450,7 @@ extern "C" int roms_hip_step2d_loop(roms_step_idx_t *s, int *indx1)
 {
   int rc = roms_entry_check("roms_hip_step2d_loop");
   if (rc) return rc;
+  if ((rc = roms_uv_adv_check("roms_hip_step2d_loop"))) return rc;
   if ((rc = check_lbc())) return rc;
   if ((rc = roms_rowm_prepare())) return rc;          // before any capture: it synchronises when it has work
   ScopedTimer tm("step2d_loop");

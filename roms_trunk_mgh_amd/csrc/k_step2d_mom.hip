@@ -98,13 +98,20 @@ __device__ __forceinline__ double VFe2(const T2 &m, int i, int j)      // :1207-
          (m.DV[a] + m.DV[a + TP] - C6 * (d2y(m.DV, m.at(i, ja)) + d2y(m.DV, m.at(i, jb))));
 }
 
+// UV_C2ADVECTION (roms_params_t.uv_adv with ROMS_UVH_C2): second-order centred, :1030-1076
+__device__ __forceinline__ double UFx2_c2(const T2 &m, int a) { return 0.25 * (m.DU[a] + m.DU[a + 1]) * (m.ub[a] + m.ub[a + 1]); }
+__device__ __forceinline__ double UFe2_c2(const T2 &m, int a) { return 0.25 * (m.DV[a] + m.DV[a - 1]) * (m.ub[a] + m.ub[a - TP]); }
+__device__ __forceinline__ double VFx2_c2(const T2 &m, int a) { return 0.25 * (m.DU[a] + m.DU[a - TP]) * (m.vb[a] + m.vb[a - 1]); }
+__device__ __forceinline__ double VFe2_c2(const T2 &m, int a) { return 0.25 * (m.DV[a] + m.DV[a + TP]) * (m.vb[a] + m.vb[a + TP]); }
+
 // FUSED: the free-surface step and the fast-time averaging are done here as well -- zeta_new and zwrk are evaluated
 // from the staged DUon/DVom tiles for the (65 x 5) points this workgroup's momentum stencil touches and kept in LDS,
 // so one step2d call is ONE launch and the zeta_new/zwrk scratch round trip disappears.  On one E-W periodic tile
 // (S2::ew_images) DUon/DVom are evaluated in place while staging; on several tiles they arrive exchanged.
 // WET (split path only): the WET_DRY blocks -- pmask_wet in the viscous stress (:1436-1438), the wet/dry factor of
 // the new velocity, of the right-hand side and, in the first predictor, of rufrc / ru(:,:,0,nstp) (:2123-2135 ...).
-template <bool FUSED, bool ROWM = false, bool ROWH = false, bool WET = false>
+// C2: the second-order centred advection of UV_C2ADVECTION in the place of the fourth-order one.
+template <bool FUSED, bool ROWM = false, bool ROWH = false, bool WET = false, bool C2 = false>
 __global__ void __launch_bounds__(BLK_X *BLK_Y)
 k2d_mom_lds(const RomsDev *__restrict__ c, S2 s, const double *__restrict__ DUon, const double *__restrict__ DVom,
             const double *__restrict__ zeta_new, const double *__restrict__ zwrk, double *__restrict__ DUnext,
@@ -308,8 +315,20 @@ k2d_mom_lds(const RomsDev *__restrict__ c, S2 s, const double *__restrict__ DUon
              (hs - h0) * (gsa + gsa0 + c3 * (rAq - rA0) * (zw - zw0)) +
              (gz2 - gz20));
   }
-  // ---- advection, :1079-1283 ----
+  // ---- advection, :1079-1283 (C2: :1026-1076, :1257-1283) ----
   if (p.uv_adv) {
+    if constexpr (C2) {
+      if (do_u) {
+        const double cff1 = UFx2_c2(m, t) - UFx2_c2(m, t - 1);
+        const double cff2 = UFe2_c2(m, t + TP) - UFe2_c2(m, t);
+        rhs_u = rhs_u - (cff1 + cff2);
+      }
+      if (do_v) {
+        const double cff1 = VFx2_c2(m, t + 1) - VFx2_c2(m, t);
+        const double cff2 = VFe2_c2(m, t) - VFe2_c2(m, t - TP);
+        rhs_v = rhs_v - (cff1 + cff2);
+      }
+    } else {
     if (do_u) {
       const double cff1 = UFx2(m, i, j) - UFx2(m, i - 1, j);
       const double cff2 = UFe2(m, i, j + 1) - UFe2(m, i, j);
@@ -319,6 +338,7 @@ k2d_mom_lds(const RomsDev *__restrict__ c, S2 s, const double *__restrict__ DUon
       const double cff1 = VFx2(m, i + 1, j) - VFx2(m, i, j);
       const double cff2 = VFe2(m, i, j) - VFe2(m, i, j - 1);
       rhs_v = rhs_v - (cff1 + cff2);
+    }
     }
   }
   const double D0 = sD[t], Dw = sD[t - 1], Ds = sD[t - TP];
@@ -620,6 +640,21 @@ int roms_rowm_prepare()
   return 0;
 }
 
+// the instantiation of a launch: split (WET or not) or fused (general, row metrics, row metrics and depth), each with
+// the fourth-order or the second-order advection
+template <bool FUSED>
+static auto pick_k2d(bool c2, bool rowm, bool rowh, bool wet) -> decltype(&k2d_mom_lds<FUSED, false, false, false, false>)
+{
+  if constexpr (!FUSED) {
+    if (wet) return c2 ? k2d_mom_lds<false, false, false, true, true> : k2d_mom_lds<false, false, false, true, false>;
+    return c2 ? k2d_mom_lds<false, false, false, false, true> : k2d_mom_lds<false, false, false, false, false>;
+  } else {
+    if (rowh) return c2 ? k2d_mom_lds<true, true, true, false, true> : k2d_mom_lds<true, true, true, false, false>;
+    if (rowm) return c2 ? k2d_mom_lds<true, true, false, false, true> : k2d_mom_lds<true, true, false, false, false>;
+    return c2 ? k2d_mom_lds<true, false, false, false, true> : k2d_mom_lds<true, false, false, false, false>;
+  }
+}
+
 // Launcher used by step2d_impl (k_step2d.hip)
 int roms_launch_k2d_mom_lds(const S2 &s, K2dLaunch mode, const double *DUon, const double *DVom, const double *zeta_new,
                             const double *zwrk, double *DUnext, double *DVnext)
@@ -627,11 +662,11 @@ int roms_launch_k2d_mom_lds(const S2 &s, K2dLaunch mode, const double *DUon, con
   const roms_bounds_t &b = g_ctx.b;
   // metrics independent of i: row table instead of fifteen 2-D arrays (... and depth and viscosity coefficients too)
   const bool rowm = g_ctx.rowm_state == 1, rowh = rowm && g_ctx.rowh;
-  const auto kernel = mode == K2dLaunch::Split ? (g_ctx.p.wet_dry ? k2d_mom_lds<false, false, false, true>
-                                                                  : k2d_mom_lds<false, false, false, false>)
-                      : rowh ? k2d_mom_lds<true, true, true, false>
-                      : rowm ? k2d_mom_lds<true, true, false, false>
-                             : k2d_mom_lds<true, false, false, false>;
+  // the advection scheme of the call: the instantiation is part of a captured LOOP_2D graph, which set_params drops
+  const bool c2 = g_ctx.p.uv_adv && ROMS_UV_HADV(g_ctx.p.uv_adv) == ROMS_UVH_C2;
+  const bool wet = g_ctx.p.wet_dry != 0;
+  const auto kernel = mode == K2dLaunch::Split ? pick_k2d<false>(c2, false, false, wet)
+                                               : pick_k2d<true>(c2, rowm, rowh, false);
   hipLaunchKernelGGL(kernel, grid2d(b.Iend - b.Istr + 1, b.Jend - b.Jstr + 1), block2d(), 0, g_ctx.stream, g_ctx.devc, s,
                      DUon, DVom, zeta_new, zwrk, DUnext, DVnext);
   KERNEL_CHECK("k2d_mom_lds");

@@ -106,6 +106,11 @@ MODULE roms_hip_mod
     TYPE(c_ptr) :: buf
   END TYPE roms_halo_msg_t
 
+  !  momentum advection = enum roms_uv_hadv, roms_uv_vadv of include/roms_hip.h:
+  !  roms_params_t%uv_adv = 0 without UV_ADV, otherwise ROMS_UV_ADV(h, v) = 1 + 16*h + 256*v (1 = the default schemes)
+  INTEGER(c_int), PARAMETER, PUBLIC :: ROMS_UVH_U3 = 0, ROMS_UVH_C2 = 1, ROMS_UVH_C4 = 2
+  INTEGER(c_int), PARAMETER, PUBLIC :: ROMS_UVV_C4W = 0, ROMS_UVV_C2 = 1, ROMS_UVV_C4 = 2, ROMS_UVV_SPLINES = 3
+
   !  field identifiers = enum roms_field_id (order of include/roms_fields.def)
   INTEGER(c_int), PARAMETER, PUBLIC :: FID_zeta=0, FID_ubar=1, FID_vbar=2, FID_rzeta=3,    &
  &    FID_rubar=4, FID_rvbar=5, FID_u=6, FID_v=7, FID_t=8, FID_ru=9, FID_rv=10, FID_W=11,   &
