@@ -375,6 +375,10 @@ k2d_mom_lds(const RomsDev *__restrict__ c, S2 s, const double *__restrict__ DUon
     if (do_v) { cell(a - ni, j - 1, t - TP, Ds, u1, v1); rhs_v = rhs_v - 0.5 * (v0 + v1); }
   }
   // ---- harmonic viscosity, :1394-1471 ----
+  // (The brackets, the mask rule and the flux-form divergence of visc.h -- strain_r / strain_p, psi_mask, div_flux --
+  // written out on the MT() / HT() accessors and the LDS tiles: filled through RhoC / PsiC this block took 4 more
+  // VGPRs in the row-table instantiations, 96 -> 100, and with them a wave per SIMD; DESIGN §3.  A change there is
+  // made here as well.)
   if (p.uv_vis2) {
     // q = flat index of the stress point, jq = its row
     auto str_r = [&](long q, int jq, int tq) {
