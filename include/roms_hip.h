@@ -293,6 +293,47 @@ int roms_hip_set_sources(int Nsrc, const int *Isrc, const int *Jsrc, const doubl
 int roms_hip_set_clima(int LnudgeM2CLM, const double *M2nudgcof, const double *ubarclm, const double *vbarclm,
                        int LnudgeM3CLM, const double *M3nudgcof, const double *uclm, const double *vclm,
                        const int *LnudgeTCLM, const double *Tnudgcof, const double *tclm, double obcfac);
+/* Time-averaged fields (AVERAGES): set_avg(ng,tile), ROMS/Nonlinear/set_avg.F:28, called after set_zeta
+ * (main3d.F:493-495).  The averages are device arrays of the library, one per selected line of roms_avg.def, with the
+ * tile's extents (LBi:UBi, LBj:UBj [, N | 0:N]) and zero wherever the reference's loops do not reach.
+ *
+ * roms_hip_set_averages hands over the window nAVG, its first step ntsAVG, ntstart and nrrec (mod_scalars.F) and the
+ * selection: Aout[AVG_COUNT] (0 / 1 per id of enum roms_avg_id; the entries of the per-tracer averages and of the
+ * counters are not looked at) and AoutT[ROMS_AVG_NTKINDS][NT], row-major with rows of the tile's NT, the rows in the
+ * order of the per-tracer lines of roms_avg.def (avgt, avgTT, avgUT, avgVT, avgHuonT, avgHvomT); NULL = none.  It
+ * allocates the selected arrays zero-filled, with wet_dry also the four counters pmask_avg ... vmask_avg; an earlier
+ * selection is released first.  nAVG = 0 releases everything; roms_hip_set_bounds drops the arrays.  Refused, leaving
+ * the library as it was: a call before bounds / params, nAVG < 0, a selected average that is not built (named in the
+ * error text), a selected average whose source field is not registered.
+ *
+ * roms_hip_set_avg reads s->iic, kstp, nrhs: one launch initialises, accumulates or accumulates-and-scales every
+ * selected average (set_avg.F:237-240, :1264, :2298-2301); after a close the ghost points are filled where the
+ * reference fills them (a periodic direction).  With wet_dry the blocks multiply by the *_full mask of their grid type,
+ * the counters count the wet steps, the close divides by max(1, count) and then clamps the counters to 1
+ * (set_masks.F:466-512).  Without a selection, or with nAVG = 0, it returns 0 and does nothing.
+ *
+ * roms_hip_get_average copies one average (itrc = 1-based tracer of a per-tracer average, otherwise ignored) or one
+ * counter to host memory, ordered after the kernels issued; n_doubles is checked against the array.  The host's
+ * wrt_avg calls it on the steps where the window closes.  roms_hip_average_device_ptr: the device array, NULL if none. */
+#define ROMS_AVG_NTKINDS 6
+enum roms_avg_id {
+#define ROMS_AVG(name, aout, grid, shape, mask, range, expr, srcA, srcB, plane) AVG_##name,
+#define ROMS_AVG_NOT_BUILT(name, aout, why) AVG_##name,
+#define ROMS_AVG_COUNTER(name, grid) AVG_##name,
+#include "roms_avg.def"
+#undef ROMS_AVG
+#undef ROMS_AVG_NOT_BUILT
+#undef ROMS_AVG_COUNTER
+  AVG_COUNT
+};
+int roms_hip_set_averages(int nAVG, int ntsAVG, int ntstart, int nrrec, const int *Aout, const int *AoutT);
+int roms_hip_set_avg(const roms_step_idx_t *s);
+int roms_hip_get_average(int avg_id, int itrc, double *host, long n_doubles);
+double *roms_hip_average_device_ptr(int avg_id, int itrc);
+/* Host-only (no GPU): what set_avg does at time step iic, as a sum of 1 = initialise (set_avg.F:237-240), 2 = accumulate
+ * (:1264), 4 = scale, "close" (:2298-2301), 8 = clamp the WET_DRY counters (set_masks.F:466-468: no nAVG = 1 branch);
+ * 0 with nAVG = 0.  The one statement of the schedule: roms_hip_set_avg asks it, the tests compare it with a table. */
+int roms_hip_avg_phase(int iic, int nAVG, int ntsAVG, int ntstart, int nrrec);
 /* wvelocity(ng,tile,nstp)          ROMS/Nonlinear/wvelocity.F:27     (main3d.F:475; writes wvel) */
 int roms_hip_wvelocity(const roms_step_idx_t *s);
 /* diag(ng,tile)                    ROMS/Nonlinear/diag.F:31          (main3d.F:314), the tile-local part

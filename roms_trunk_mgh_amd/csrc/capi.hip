@@ -78,7 +78,7 @@ __global__ void __launch_bounds__(256) k_calib_stream(const double *__restrict__
   if (e < n) dst[e] = src[e];
 }
 int roms_entry_check(const char *where);
-namespace { void sources_release(); void clima_release(); }
+namespace { void sources_release(); void clima_release(); void avg_release(); }
 extern "C" int roms_hip_calib_stream(long n)
 {
   int rc = roms_entry_check("roms_hip_calib_stream");
@@ -130,6 +130,31 @@ static void guarded_free(double **user, double **base)
   *user = *base = nullptr;
 }
 
+// ---- AVERAGES: the lines of roms_avg.def and the library-owned arrays (roms_hip_set_averages below) ----
+enum { AVG_GT_r = GT_R, AVG_GT_u = GT_U, AVG_GT_v = GT_V, AVG_GT_w = GT_R, AVG_GT_p = GT_P };
+enum { AVG_CNT_p = 0, AVG_CNT_r, AVG_CNT_u, AVG_CNT_v };
+const AvgLine k_avg_line[AVG_COUNT] = {
+#define ROMS_AVG(name, aout, grid, shape, mask, range, expr, srcA, srcB, plane)                                       \
+  {#name, nullptr, AVG_GT_##grid, shape, FID_##mask, range, expr, FID_##srcA, FID_##srcB, plane, -1},
+#define ROMS_AVG_NOT_BUILT(name, aout, why) {#name, #aout ": " #why, 0, 0, 0, 0, 0, 0, 0, 0, -1},
+#define ROMS_AVG_COUNTER(name, grid) {#name, nullptr, AVG_GT_##grid, AVS_2D, 0, 0, 0, 0, 0, 0, AVG_CNT_##grid},
+#include "roms_avg.def"
+#undef ROMS_AVG
+#undef ROMS_AVG_NOT_BUILT
+#undef ROMS_AVG_COUNTER
+};
+AvgStore g_avg;
+// row of AoutT of a per-tracer line = its rank among the AVS_NT lines of the table; -1 otherwise
+static int avg_tkind(int id)
+{
+  const AvgLine &L = k_avg_line[id];
+  if (L.why || L.counter >= 0 || L.shape != AVS_NT) return -1;
+  int r = 0;
+  for (int q = 0; q < id; q++)
+    if (!k_avg_line[q].why && k_avg_line[q].counter < 0 && k_avg_line[q].shape == AVS_NT) r++;
+  return r;
+}
+
 // ---- climatology (mod_clima.F), roms_hip_set_clima: the eight device copies, each with its guard bands ----
 namespace {
 enum { CL_M2nudgcof = 0, CL_ubarclm, CL_vbarclm, CL_M3nudgcof, CL_uclm, CL_vclm, CL_Tnudgcof, CL_tclm, CL_COUNT };
@@ -171,6 +196,10 @@ extern "C" int roms_hip_check_guards(void)
     if ((rc = check(k_field_name[id], -1, g_ctx.dev_base[id], g_ctx.count[id]))) return rc;
   for (int q = 0; q < CL_COUNT; q++)
     if ((rc = check(k_clima_name[q], -1, g_clima.base[q], g_clima.count[q]))) return rc;
+  for (int q = 0; q < g_avg.n; q++)
+    if ((rc = check(k_avg_line[g_avg.arr[q].id].name, -1, g_avg.arr[q].base, g_avg.arr[q].count))) return rc;
+  for (int q = 0; q < 4; q++)
+    if ((rc = check(k_avg_line[AVG_pmask_avg + q].name, -1, g_avg.cnt_base[q], g_avg.nij))) return rc;
   for (int q = 0; q < ROMS_NWS3; q++)
     if ((rc = check("ws3", q, g_ctx.ws3_base[q], nij * (b.N + 1)))) return rc;
   for (int q = 0; q < 32; q++)
@@ -255,6 +284,7 @@ extern "C" int roms_hip_finalize(void)
   for (int q = 0; q < 32; q++) guarded_free(&g_ctx.hostc.ws2[q], &g_ctx.ws2_base[q]);
   sources_release();
   clima_release();
+  avg_release();
   if (g_ctx.devc) (void)hipFree(g_ctx.devc);
   g_ctx.devc = nullptr;
   if (g_ctx.stream) (void)hipStreamDestroy(g_ctx.stream);
@@ -443,6 +473,143 @@ extern "C" int roms_hip_set_clima(int LnudgeM2CLM, const double *M2nudgcof, cons
   return 0;
 }
 
+// ---- time-averaged fields (AVERAGES; set_avg.F, mod_average.F) ----
+namespace {
+void avg_release()
+{
+  for (int q = 0; q < g_avg.n; q++) guarded_free(&g_avg.arr[q].dev, &g_avg.arr[q].base);
+  for (int q = 0; q < 4; q++) guarded_free(&g_avg.cnt[q], &g_avg.cnt_base[q]);
+  g_avg = AvgStore{};
+}
+}  // namespace
+
+// The schedule of set_avg_tile and set_avg_masks, stated once (mirror: roms_trunk_mgh_amd/avg.py, phase()).
+extern "C" int roms_hip_avg_phase(int iic, int nAVG, int ntsAVG, int ntstart, int nrrec)
+{
+  if (nAVG <= 0) return 0;                                                    // set_avg.F:189
+  int ph = 0;
+  const bool restart = nrrec > 0 && iic == ntstart;
+  if ((iic > ntsAVG && (iic - 1) % nAVG == 1) || (iic >= ntsAVG && nAVG == 1) || restart) ph |= AVP_SET;   // :237-240
+  else if (iic > ntsAVG) ph |= AVP_ADD;                                                                    // :1264
+  const bool window_end = iic > ntsAVG && (iic - 1) % nAVG == 0 && !restart;
+  if (window_end || (iic >= ntsAVG && nAVG == 1)) ph |= AVP_CLOSE;                                         // :2298-2301
+  if (window_end) ph |= AVP_MASKS;                                                                // set_masks.F:466-468
+  return ph;
+}
+
+extern "C" int roms_hip_set_averages(int nAVG, int ntsAVG, int ntstart, int nrrec, const int *Aout, const int *AoutT)
+{
+  const char *me = "roms_hip_set_averages";
+  if (!g_ctx.inited || !g_ctx.have_bounds || !g_ctx.have_params)
+    return roms_fail(me, "roms_hip_init, roms_hip_set_bounds and roms_hip_set_params come first");
+  if (nAVG < 0) return roms_fail(me, "averages: nAVG < 0");
+  if (nAVG == 0) {
+    if (g_avg.n || g_avg.cnt[0]) HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+    avg_release();
+    return 0;
+  }
+  if (!Aout) return roms_fail(me, "averages: Aout is NULL");
+  const roms_bounds_t &b = g_ctx.b;
+  const long nij = (long)(b.UBi - b.LBi + 1) * (long)(b.UBj - b.LBj + 1);
+  // the selection; nothing is touched before all of it has been looked at
+  AvgStore want;
+  want.nAVG = nAVG; want.ntsAVG = ntsAVG; want.ntstart = ntstart; want.nrrec = nrrec; want.nij = nij;
+  for (int id = 0; id < AVG_COUNT; id++) {
+    const AvgLine &L = k_avg_line[id];
+    if (L.counter >= 0) continue;
+    const int tk = avg_tkind(id);
+    for (int it = (tk >= 0 ? 1 : 0); it <= (tk >= 0 ? b.NT : 0); it++) {
+      if (tk >= 0 ? !(AoutT && AoutT[tk * b.NT + it - 1]) : !Aout[id]) continue;
+      if (L.why) {
+        const std::string m = std::string("averages: ") + L.name + " is not built (" + L.why + ")";
+        return roms_fail(me, m.c_str());
+      }
+      for (int fid : {L.srcA, L.srcB, L.expr == X_WPMPN ? (int)FID_pm : L.srcA, L.expr == X_WPMPN ? (int)FID_pn : L.srcA})
+        if (!g_ctx.dev[fid]) {
+          const std::string m = std::string("averages: ") + L.name + " reads " + k_field_name[fid] + ", which is not registered";
+          return roms_fail(me, m.c_str());
+        }
+      if (k_field_kind[L.srcA] == K_3DW_NAT && L.plane >= b.NAT) {
+        const std::string m = std::string("averages: ") + L.name + " reads tracer " + std::to_string(L.plane + 1) + " of " +
+                              k_field_name[L.srcA] + ", the tile has NAT = " + std::to_string(b.NAT);
+        return roms_fail(me, m.c_str());
+      }
+      if (k_field_kind[L.srcA] == K_2D_NT && L.plane >= b.NT) {
+        const std::string m = std::string("averages: ") + L.name + " reads tracer " + std::to_string(L.plane + 1) + " of " +
+                              k_field_name[L.srcA] + ", the tile has NT = " + std::to_string(b.NT);
+        return roms_fail(me, m.c_str());
+      }
+      AvgArray &a = want.arr[want.n++];
+      a.id = id; a.itrc = it;
+      a.nk = L.shape == AVS_2D ? 1 : L.shape == AVS_W ? b.N + 1 : b.N;
+      a.count = nij * a.nk;
+      a.dev = a.base = nullptr;
+    }
+  }
+  HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+  avg_release();
+  g_avg = want;
+  g_avg.n = 0;
+  for (int q = 0; q < want.n; q++) {                   // zero-filled, as the reference's allocation leaves them
+    AvgArray &a = g_avg.arr[q];
+    int rc = guarded_alloc(&a.dev, &a.base, a.count);
+    g_avg.n = q + 1;
+    if (rc) { avg_release(); return rc; }
+  }
+  if (g_ctx.p.wet_dry)
+    for (int q = 0; q < 4; q++) {
+      int rc = guarded_alloc(&g_avg.cnt[q], &g_avg.cnt_base[q], nij);
+      if (rc) { avg_release(); return rc; }
+    }
+  HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+  return 0;
+}
+
+// the array of (avg_id, itrc): an average or a counter; nullptr if it is not there
+static const AvgArray *avg_find(int id, int itrc, AvgArray *tmp)
+{
+  if (id < 0 || id >= AVG_COUNT) return nullptr;
+  const AvgLine &L = k_avg_line[id];
+  if (L.counter >= 0) {
+    if (!g_avg.cnt[L.counter]) return nullptr;
+    *tmp = AvgArray{id, 0, 1, g_avg.nij, g_avg.cnt[L.counter], g_avg.cnt_base[L.counter]};
+    return tmp;
+  }
+  const int want = avg_tkind(id) >= 0 ? itrc : 0;
+  for (int q = 0; q < g_avg.n; q++)
+    if (g_avg.arr[q].id == id && g_avg.arr[q].itrc == want) return &g_avg.arr[q];
+  return nullptr;
+}
+
+extern "C" int roms_hip_get_average(int avg_id, int itrc, double *host, long n_doubles)
+{
+  const char *me = "roms_hip_get_average";
+  if (!g_ctx.inited) return roms_fail(me, "library not initialised");
+  if (avg_id < 0 || avg_id >= AVG_COUNT) return roms_fail(me, "averages: bad id");
+  AvgArray tmp;
+  const AvgArray *a = avg_find(avg_id, itrc, &tmp);
+  if (!a) {
+    const std::string m = std::string("averages: ") + k_avg_line[avg_id].name + " is not selected (roms_hip_set_averages)";
+    return roms_fail(me, m.c_str());
+  }
+  if (!host) return roms_fail(me, "averages: host array is NULL");
+  if (n_doubles != a->count) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "averages: %s has %ld doubles, the host array %ld", k_avg_line[avg_id].name, a->count, n_doubles);
+    return roms_fail(me, msg);
+  }
+  HIP_TRY(hipMemcpyAsync(host, a->dev, sizeof(double) * a->count, hipMemcpyDeviceToHost, g_ctx.stream));
+  HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+  return 0;
+}
+
+extern "C" double *roms_hip_average_device_ptr(int avg_id, int itrc)
+{
+  AvgArray tmp;
+  const AvgArray *a = g_ctx.inited ? avg_find(avg_id, itrc, &tmp) : nullptr;
+  return a ? a->dev : nullptr;
+}
+
 extern "C" int roms_hip_set_bounds(const roms_bounds_t *b)
 {
   if (!g_ctx.inited) return roms_fail("roms_hip_set_bounds", "library not initialised");
@@ -453,6 +620,7 @@ extern "C" int roms_hip_set_bounds(const roms_bounds_t *b)
   roms_rowm_release();
   sources_release();                       // the face maps are in the old bounds' index space
   clima_release();                         // ... and the climatology has the old extents
+  avg_release();                           // ... and so have the averages
   g_ctx.b = *b;
   g_ctx.hostc.b = *b;
   g_ctx.have_bounds = true;

@@ -49,6 +49,33 @@ struct RomsClima {
   const double *Tnudgcof, *tclm;                 // [nij * N * nt]
 };
 
+// AVERAGES (roms_hip_set_averages, roms_hip_set_avg): the columns of include/roms_avg.def and the library-owned arrays.
+enum { AVS_2D = 0, AVS_N, AVS_W, AVS_NT };
+enum { RNG_RR = 0, RNG_UR, RNG_VR, RNG_II, RNG_UI, RNG_VI };
+enum { X_COPY = 0, X_SQ, X_WPMPN, X_UV, X_UT, X_VT };
+enum { AVP_SET = 1, AVP_ADD = 2, AVP_CLOSE = 4, AVP_MASKS = 8 };      // roms_hip_avg_phase
+struct AvgLine {
+  const char *name, *why;     // why != nullptr: not built
+  int gtype, shape, mask, range, expr, srcA, srcB, plane;
+  int counter;                // 0..3 = p, r, u, v counter; -1 = an average
+};
+extern const AvgLine k_avg_line[AVG_COUNT];
+struct AvgArray {
+  int id, itrc;               // line of the table, tracer (1-based; 0 = not per tracer)
+  int nk;                     // planes: 1, N or N+1
+  long count;
+  double *dev, *base;
+};
+#define ROMS_AVG_MAXARR (AVG_COUNT + ROMS_AVG_NTKINDS * ROMS_MAXNT)
+struct AvgStore {
+  int nAVG = 0, ntsAVG = 0, ntstart = 0, nrrec = 0;
+  int n = 0;
+  AvgArray arr[ROMS_AVG_MAXARR];
+  double *cnt[4] = {nullptr, nullptr, nullptr, nullptr}, *cnt_base[4] = {nullptr, nullptr, nullptr, nullptr};   // pmask_avg, rmask_avg, umask_avg, vmask_avg
+  long nij = 0;
+};
+extern AvgStore g_avg;
+
 struct RomsDev {
   roms_bounds_t b;
   roms_params_t p;

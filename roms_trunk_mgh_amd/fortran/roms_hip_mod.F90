@@ -134,6 +134,22 @@ MODULE roms_hip_mod
  &    FID_pmask_wet=106, FID_rmask_wet=107, FID_umask_wet=108, FID_vmask_wet=109, FID_rmask_wet_avg=110,   &
  &    FID_pmask_full=111, FID_rmask_full=112, FID_umask_full=113, FID_vmask_full=114
 
+  !  ids of the time-averaged fields = the lines of include/roms_avg.def (enum roms_avg_id), for Aout(0:AVG_COUNT-1)
+  INTEGER(c_int), PARAMETER, PUBLIC :: AVG_avgzeta=0, AVG_avgu2d=1, AVG_avgv2d=2, AVG_avgu3d=3,   &
+ &    AVG_avgv3d=4, AVG_avgw3d=5, AVG_avgwvel=6, AVG_avgrho=7, AVG_avgt=8, AVG_avgAKv=9, AVG_avgAKt=10,   &
+ &    AVG_avgAKs=11, AVG_avghsbl=12, AVG_avgsus=13, AVG_avgsvs=14, AVG_avgbus=15, AVG_avgbvs=16,   &
+ &    AVG_avgPair=17, AVG_avgTair=18, AVG_avgUwind=19, AVG_avgVwind=20, AVG_avgstf=21, AVG_avgswf=22,   &
+ &    AVG_avgsrf=23, AVG_avglhf=24, AVG_avglrf=25, AVG_avgshf=26, AVG_avgevap=27, AVG_avgrain=28,   &
+ &    AVG_avgZZ=29, AVG_avgU2=30, AVG_avgV2=31, AVG_avgUU=32, AVG_avgVV=33, AVG_avgUV=34, AVG_avgHuon=35,   &
+ &    AVG_avgHvom=36, AVG_avgTT=37, AVG_avgUT=38, AVG_avgVT=39, AVG_avgHuonT=40, AVG_avgHvomT=41,   &
+ &    AVG_avgu2dE=42, AVG_avgv2dN=43, AVG_avgu3dE=44, AVG_avgv3dN=45, AVG_avgpvor2d=46, AVG_avgrvor2d=47,   &
+ &    AVG_avgpvor3d=48, AVG_avgrvor3d=49, AVG_avghbbl=50, AVG_avgDU_avg1=51, AVG_avgDU_avg2=52,   &
+ &    AVG_avgDV_avg1=53, AVG_avgDV_avg2=54, AVG_avgu2Sd=55, AVG_avgv2Sd=56, AVG_avgu2RS=57, AVG_avgv2RS=58,   &
+ &    AVG_avgSxx2d=59, AVG_avgSxy2d=60, AVG_avgSyy2d=61, AVG_avgu3Sd=62, AVG_avgv3Sd=63, AVG_avgu3RS=64,   &
+ &    AVG_avgv3RS=65, AVG_avgSxx3d=66, AVG_avgSxy3d=67, AVG_avgSyy3d=68, AVG_avgSzx3d=69, AVG_avgSzy3d=70,   &
+ &    AVG_avgbedldu=71, AVG_avgbedldv=72, AVG_pmask_avg=73, AVG_rmask_avg=74, AVG_umask_avg=75,   &
+ &    AVG_vmask_avg=76, AVG_COUNT=77, ROMS_AVG_NTKINDS=6
+
   INTERFACE
     INTEGER(c_int) FUNCTION roms_hip_init (rank, ntileI, ntileJ, device_id, uid)            &
  &                 BIND(C, name='roms_hip_init')
@@ -315,6 +331,33 @@ MODULE roms_hip_mod
       INTEGER(c_int), INTENT(in) :: LnudgeTCLM(*)
       REAL(c_double), VALUE :: obcfac
     END FUNCTION
+    !  AVERAGES: the selection (Aout(0:AVG_COUNT-1) by the ids above, AoutT(NT,ROMS_AVG_NTKINDS) = avgt, avgTT, avgUT,
+    !  avgVT, avgHuonT, avgHvomT per tracer, as 0 / 1) after roms_hip_set_params; set_avg(ng,tile) (main3d.F:494);
+    !  the D->H copy of one average for wrt_avg
+    INTEGER(c_int) FUNCTION roms_hip_set_averages (nAVG, ntsAVG, ntstart, nrrec, Aout, AoutT)                      &
+   &                        BIND(C, name='roms_hip_set_averages')
+      IMPORT :: c_int
+      INTEGER(c_int), VALUE :: nAVG, ntsAVG, ntstart, nrrec
+      INTEGER(c_int), INTENT(in) :: Aout(*), AoutT(*)
+    END FUNCTION
+    INTEGER(c_int) FUNCTION roms_hip_set_avg (s) BIND(C, name='roms_hip_set_avg')
+      IMPORT :: c_int, roms_step_idx_t
+      TYPE(roms_step_idx_t), INTENT(in) :: s
+    END FUNCTION
+    INTEGER(c_int) FUNCTION roms_hip_get_average (avg_id, itrc, host, n_doubles) BIND(C, name='roms_hip_get_average')
+      IMPORT :: c_int, c_long, c_ptr
+      INTEGER(c_int), VALUE :: avg_id, itrc
+      TYPE(c_ptr), VALUE :: host
+      INTEGER(c_long), VALUE :: n_doubles
+    END FUNCTION
+    TYPE(c_ptr) FUNCTION roms_hip_average_device_ptr (avg_id, itrc) BIND(C, name='roms_hip_average_device_ptr')
+      IMPORT :: c_int, c_ptr
+      INTEGER(c_int), VALUE :: avg_id, itrc
+    END FUNCTION
+    INTEGER(c_int) FUNCTION roms_hip_avg_phase (iic, nAVG, ntsAVG, ntstart, nrrec) BIND(C, name='roms_hip_avg_phase')
+      IMPORT :: c_int
+      INTEGER(c_int), VALUE :: iic, nAVG, ntsAVG, ntstart, nrrec
+    END FUNCTION
     !  GLS_MIXING: gls_prestep (main3d.F:567) and gls_corstep (main3d.F:793)
     INTEGER(c_int) FUNCTION roms_hip_gls_prestep (s) BIND(C, name='roms_hip_gls_prestep')
       IMPORT :: c_int, roms_step_idx_t
@@ -343,6 +386,7 @@ MODULE roms_hip_mod
   PUBLIC :: roms_hip_ana_srflux, roms_hip_wvelocity, roms_hip_diag, roms_hip_snapshot_begin, roms_hip_snapshot_end
   PUBLIC :: roms_hip_ini_zeta, roms_hip_ini_fields, roms_hip_gls_prestep, roms_hip_gls_corstep, roms_hip_wetdry
   PUBLIC :: roms_hip_set_sources, roms_hip_set_clima
+  PUBLIC :: roms_hip_set_averages, roms_hip_set_avg, roms_hip_get_average, roms_hip_average_device_ptr, roms_hip_avg_phase
   PUBLIC :: roms_hip_entry, roms_hip_make_idx, roms_hip_status
 
 CONTAINS

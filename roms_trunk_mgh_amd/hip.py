@@ -29,7 +29,7 @@ def use_library(path):
 ENTRIES = ["set_massflux", "rho_eos", "omega", "set_zeta", "set_depth", "rhs3d",
            "pre_step3d", "prsgrd", "t3dmix2", "rhs3d_tile", "uv3dmix2", "step2d",
            "step3d_uv", "step3d_t", "bulk_flux", "set_vbc", "lmd_vmix", "wvelocity", "ini_zeta", "ini_fields",
-           "t3dmix4", "uv3dmix4", "gls_prestep", "gls_corstep", "wetdry"]
+           "t3dmix4", "uv3dmix4", "gls_prestep", "gls_corstep", "wetdry", "set_avg"]
 
 # every symbol include/roms_hip.h declares
 DECLARED_SYMBOLS = (
@@ -42,7 +42,8 @@ DECLARED_SYMBOLS = (
      "roms_hip_snapshot_begin", "roms_hip_snapshot_end", "roms_hip_halo_plan",
      "roms_hip_ana_srflux", "roms_hip_check_guards", "roms_hip_row_metrics_state",
      "roms_hip_graph_exchanges", "roms_hip_graph_exchanges_state", "roms_hip_set_sources",
-     "roms_hip_set_clima"] + ["roms_hip_" + e for e in ENTRIES])
+     "roms_hip_set_clima", "roms_hip_set_averages", "roms_hip_get_average", "roms_hip_average_device_ptr",
+     "roms_hip_avg_phase"] + ["roms_hip_" + e for e in ENTRIES])
 
 
 _DP = C.POINTER(C.c_double)
@@ -86,6 +87,11 @@ def load():
     _ip = C.POINTER(C.c_int)
     lib.roms_hip_set_sources.argtypes = [C.c_int, _ip, _ip, _DP, _DP, _DP, _DP, _ip]
     lib.roms_hip_set_clima.argtypes = [C.c_int, _DP, _DP, _DP, C.c_int, _DP, _DP, _DP, _ip, _DP, _DP, C.c_double]
+    lib.roms_hip_set_averages.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip]
+    lib.roms_hip_get_average.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_long]
+    lib.roms_hip_average_device_ptr.restype = C.c_void_p
+    lib.roms_hip_average_device_ptr.argtypes = [C.c_int, C.c_int]
+    lib.roms_hip_avg_phase.argtypes = [C.c_int] * 5
     lib.roms_hip_set_halo_relay.argtypes = [RELAY_FN, C.c_void_p]
     if hasattr(lib, "roms_hip_tile_neighbors"):
         lib.roms_hip_tile_neighbors.argtypes = [C.c_int] * 7 + [C.POINTER(C.c_int)]
@@ -159,6 +165,23 @@ class RomsHip:
         """CLIMA(ng) with LnudgeM2CLM / LnudgeM3CLM / LnudgeTCLM (roms_trunk_mgh_amd/clima.py) -> roms_hip_set_clima;
         only = names of the arrays to hand over again (the others keep their device copy)."""
         self._chk(self.l.roms_hip_set_clima(*clima.c_args(only)), "set_clima")
+
+    def set_averages(self, averages):
+        """The selection of time-averaged fields (roms_trunk_mgh_amd/avg.py) -> roms_hip_set_averages; None switches
+        the averages off (nAVG = 0)."""
+        self.averages = averages
+        args = averages.c_args() if averages is not None else (0, 0, 0, 0, None, None)
+        self._chk(self.l.roms_hip_set_averages(*args), "set_averages")
+
+    def get_average(self, name, itrc=0):
+        """One average (itrc = the 1-based tracer of a per-tracer one) or WET_DRY counter of roms_avg.def as a host
+        array with the tile's extents (roms_hip_get_average)."""
+        from . import avg
+        if getattr(self, "averages", None) is None:
+            raise RuntimeError("roms_hip get_average: no averages selected (set_averages)")
+        out = np.zeros(self.averages.shape(name), dtype=np.float64, order="F")
+        self._chk(self.l.roms_hip_get_average(avg.AVG_ID[name], int(itrc), out.ctypes.data, out.size), "get_average " + name)
+        return out
 
     def _chk(self, rc, what):
         if rc != 0:

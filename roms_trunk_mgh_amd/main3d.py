@@ -14,6 +14,7 @@ against either backend (`hip.RomsHip` = the product, or the CPU oracle in tests)
     main3d.F:388-394  bulk_flux, set_vbc               (physics=True; else fixed forcing inputs)
     main3d.F:467-475  lmd_vmix (physics=True; else fixed mixing inputs); omega; wvelocity (diagnostics=True)
     main3d.F:489      set_zeta
+    main3d.F:494      set_avg                          (AVERAGES: averages=...)
     main3d.F:563      rhs3d
     main3d.F:567      gls_prestep                      (GLS_MIXING applications)
     main3d.F:592-700  LOOP_2D (predictor/corrector step2d)
@@ -42,7 +43,7 @@ def host_clock(tdays):
 
 
 class Main3D:
-    def __init__(self, backend, ntstart=1, physics=False, diagnostics=False, ninfo=1):
+    def __init__(self, backend, ntstart=1, physics=False, diagnostics=False, ninfo=1, averages=None):
         """physics=True also runs the per-step physics that is on the device:
         bulk_flux and lmd_vmix (BULK_FLUXES / LMD_MIXING applications, i.e. BENCHMARK) and set_vbc, in
         the reference's order;
@@ -50,8 +51,14 @@ class Main3D:
         diagnostics=True adds the two diagnostics the reference's step carries: wvelocity after the
         first omega (main3d.F:475) and, every `ninfo` steps, the tile-local part of diag after rho_eos
         (main3d.F:314; it therefore sees the wvel of the previous step, as in the reference); the
-        12-vector of the last call is kept in `last_diag` (layout: roms_hip.h, roms_hip_diag)."""
+        12-vector of the last call is kept in `last_diag` (layout: roms_hip.h, roms_hip_diag).
+        averages: an avg.Averages (AVERAGES applications): handed to the backend here (set_averages), and every step
+        issues set_avg directly after set_zeta (main3d.F:493-495); the host fetches a window with
+        backend.get_average on the steps where averages.phase(iic) has avg.CLOSE set."""
         self.be = backend
+        self.averages = averages
+        if averages is not None:
+            backend.set_averages(averages)
         self.physics = physics
         self.diagnostics = diagnostics
         self.ninfo = ninfo
@@ -108,6 +115,8 @@ class Main3D:
         if self.diagnostics:
             be.call("wvelocity", s)
         be.call("set_zeta", s)
+        if self.averages is not None:
+            be.call("set_avg", s)
         be.call("rhs3d", s)
         gls = bool(be.st.p.gls_mixing)
         if gls:                               # main3d.F:564-567
