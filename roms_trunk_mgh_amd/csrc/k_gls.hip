@@ -20,6 +20,7 @@
 // configurations: written for parity first.  Pinned: the oracle against the reference's GLS builds bit for bit, this
 // file against the oracle (tests/test_gpu_gls.py).
 #include "roms_dev.h"
+#include "gls.h"
 
 int roms_entry_check(const char *name);
 
@@ -170,39 +171,6 @@ int gls_check(const char *where)
   return 0;
 }
 
-// gradient of field A at the u-face i (v-face j) of level offset `lk`, with the MASKING multiply and the reference's
-// rule for the face outside a physical edge (the next face's value)
-struct GradX {
-  const roms_bounds_t &b; const double *um; bool mk; long ni;
-  __device__ double operator()(const double *A, long base, int i, int j, int LBi, int LBj) const
-  {
-    int ii = i;
-    if (!b.EWperiodic) {
-      if (b.west_edge && ii == b.Istr - 1) ii = b.Istr;
-      if (b.east_edge && ii == b.Iend + 2) ii = b.Iend + 1;
-    }
-    const long a = base + (long)(ii - LBi) + (long)(j - LBj) * ni;
-    double g = (A[a] - A[a - 1]);
-    if (mk) g = g * um[(long)(ii - LBi) + (long)(j - LBj) * ni];
-    return g;
-  }
-};
-struct GradY {
-  const roms_bounds_t &b; const double *vm; bool mk; long ni;
-  __device__ double operator()(const double *A, long base, int i, int j, int LBi, int LBj) const
-  {
-    int jj = j;
-    if (!b.NSperiodic) {
-      if (b.south_edge && jj == b.Jstr - 1) jj = b.Jstr;
-      if (b.north_edge && jj == b.Jend + 2) jj = b.Jend + 1;
-    }
-    const long a = base + (long)(i - LBi) + (long)(jj - LBj) * ni;
-    double g = (A[a] - A[a - ni]);
-    if (mk) g = g * vm[(long)(i - LBi) + (long)(jj - LBj) * ni];
-    return g;
-  }
-};
-
 // ------------------------------------------------------------ gls_prestep --
 __global__ void __launch_bounds__(BLK_X *BLK_Y)
 k_gls_prestep(const RomsDev *__restrict__ c, roms_step_idx_t s)
@@ -212,80 +180,49 @@ k_gls_prestep(const RomsDev *__restrict__ c, roms_step_idx_t s)
   const int i = b.Istr + XB.x * BLK_X + threadIdx.x;
   const int j = b.Jstr + XB.y * BLK_Y + threadIdx.y;
   if (i > b.Iend || j > b.Jend) return;
-  const roms_params_t &p = c->p;
   const int nstp = s.nstp, nnew = s.nnew;
-  const double dt = p.dt, Gamma = 1.0 / 6.0;
-  const bool mk = p.masking != 0;
+  const double dt = c->p.dt, Gamma = 1.0 / 6.0;
   const double *Huon = c->F.Huon, *Hvom = c->F.Hvom, *Hz = c->F.Hz, *Wv = c->F.W;
   double *tke = c->F.tke, *gls = c->F.gls;
   const long Ls = (long)(nstp - 1) * n3w, Ln = (long)(nnew - 1) * n3w, L3 = 2L * n3w;
-  const GradX gx{b, c->F.umask, mk, ni};
-  const GradY gy{b, c->F.vmask, mk, ni};
+  const Grad<false> gx = grad_dir<false>(c, ni);
+  const Grad<true> gy = grad_dir<true>(c, ni);
   const long a2 = I2(i, j);
-  const double pmn = 0.0;
-  (void)pmn;
   double cff1, cff2, cff3;
   int indx;
   if (s.iic == s.ntfirst) { cff1 = 1.0; cff2 = 0.0; cff3 = 0.5 * dt; indx = nstp; }
   else { cff1 = 0.5 + Gamma; cff2 = 0.5 - Gamma; cff3 = (1.0 - Gamma) * dt; indx = 3 - nstp; }
   const long Li = (long)(indx - 1) * n3w;
-  const double c6 = 1.0 / 6.0;
-  // vertical flux through the rho-level kk between W-levels kk-1 and kk (gls_prestep.F:322-352): CF and FC, FCL
-  auto vflux = [&](int kk, double &CFk, double &FCk, double &FCLk) {
-    const long w = a2 + (long)kk * nij;                   // W-level kk
-    CFk = 0.5 * (Wv[w] + Wv[w - nij]);
-    const double *T = tke + Ls, *G = gls + Ls;
-    if (kk == 1) {
-      FCk = CFk * (1.0 / 3.0 * T[w - nij] + 5.0 / 6.0 * T[w] - 1.0 / 6.0 * T[w + nij]);
-      FCLk = CFk * (1.0 / 3.0 * G[w - nij] + 5.0 / 6.0 * G[w] - 1.0 / 6.0 * G[w + nij]);
-    } else if (kk == N) {
-      FCk = CFk * (1.0 / 3.0 * T[w] + 5.0 / 6.0 * T[w - nij] - 1.0 / 6.0 * T[w - 2 * nij]);
-      FCLk = CFk * (1.0 / 3.0 * G[w] + 5.0 / 6.0 * G[w - nij] - 1.0 / 6.0 * G[w - 2 * nij]);
-    } else {
-      FCk = CFk * (7.0 / 12.0 * (T[w - nij] + T[w]) - 1.0 / 12.0 * (T[w - 2 * nij] + T[w + nij]));
-      FCLk = CFk * (7.0 / 12.0 * (G[w - nij] + G[w]) - 1.0 / 12.0 * (G[w - 2 * nij] + G[w + nij]));
-    }
-  };
-  double CFlo, FClo, FCLlo;
-  vflux(1, CFlo, FClo, FCLlo);
+  // vertical flux through the rho-level kk between W-levels kk-1 and kk (gls_prestep.F:322-352): CF, and CF * vface()
+  auto wface = [&](int kk) { return 0.5 * (Wv[a2 + (long)kk * nij] + Wv[a2 + (long)(kk - 1) * nij]); };
+  double CFlo = wface(1);
+  double FClo = CFlo * vface(tke + Ls, a2 + nij, 1, N, nij), FCLlo = CFlo * vface(gls + Ls, a2 + nij, 1, N, nij);
   for (int k = 1; k <= N - 1; k++) {
     const long wk = (long)k * nij;                                  // plane of W-level k
     const long r = a2 + (long)(k - 1) * nij;                        // rho-level k
-    const double *T = tke + Ls + wk, *G = gls + Ls + wk;
-    // horizontal fluxes at the faces i, i+1, j, j+1 (fourth-order centred, :176-263)
-    auto fx = [&](int ii, double &XF, double &FX, double &FXL) {
-      const long q = (long)(ii - LBi) + (long)(j - LBj) * ni;
-      XF = 0.5 * (Huon[q + (long)(k - 1) * nij] + Huon[q + (long)k * nij]);
-      FX = XF * 0.5 * (T[q - 1] + T[q] - c6 * (gx(T, 0, ii + 1, j, LBi, LBj) - gx(T, 0, ii - 1, j, LBi, LBj)));
-      FXL = XF * 0.5 * (G[q - 1] + G[q] - c6 * (gx(G, 0, ii + 1, j, LBi, LBj) - gx(G, 0, ii - 1, j, LBi, LBj)));
-    };
-    auto fe = [&](int jj, double &EF, double &FE, double &FEL) {
-      const long q = (long)(i - LBi) + (long)(jj - LBj) * ni;
-      EF = 0.5 * (Hvom[q + (long)(k - 1) * nij] + Hvom[q + (long)k * nij]);
-      FE = EF * 0.5 * (T[q - ni] + T[q] - c6 * (gy(T, 0, i, jj + 1, LBi, LBj) - gy(T, 0, i, jj - 1, LBi, LBj)));
-      FEL = EF * 0.5 * (G[q - ni] + G[q] - c6 * (gy(G, 0, i, jj + 1, LBi, LBj) - gy(G, 0, i, jj - 1, LBi, LBj)));
-    };
-    double XF0, FX0, FXL0, XF1, FX1, FXL1, EF0, FE0, FEL0, EF1, FE1, FEL1;
-    fx(i, XF0, FX0, FXL0); fx(i + 1, XF1, FX1, FXL1);
-    fe(j, EF0, FE0, FEL0); fe(j + 1, EF1, FE1, FEL1);
+    // transports through the faces i, i+1, j, j+1 (:176-263), shared by the two fields
+    const double XF0 = face_transport(Huon, r, nij), XF1 = face_transport(Huon, r + 1, nij);
+    const double EF0 = face_transport(Hvom, r, nij), EF1 = face_transport(Hvom, r + ni, nij);
     const double cff = 0.5 * (Hz[r] + Hz[r + nij]);
     const double cff4 = cff3 * c->F.pm[a2] * c->F.pn[a2];
-    double Hz_half = cff - cff4 * (XF1 - XF0 + EF1 - EF0);
-    const double tk = tke[Ls + a2 + wk], gk = gls[Ls + a2 + wk];
-    double t3 = cff * (cff1 * tk + cff2 * tke[Li + a2 + wk]) - cff4 * (FX1 - FX0 + FE1 - FE0);
-    double g3 = cff * (cff1 * gk + cff2 * gls[Li + a2 + wk]) - cff4 * (FXL1 - FXL0 + FEL1 - FEL0);
-    tke[Ln + a2 + wk] = cff * tk;
-    gls[Ln + a2 + wk] = cff * gk;
-    // vertical advection (:300-375)
-    double CFhi, FChi, FCLhi;
-    vflux(k + 1, CFhi, FChi, FCLhi);
-    Hz_half = Hz_half - cff4 * (CFhi - CFlo);
+    const double CFhi = wface(k + 1);                               // vertical advection (:300-375)
+    const double Hz_half = cff - cff4 * (XF1 - XF0 + EF1 - EF0) - cff4 * (CFhi - CFlo);
     const double o = 1.0 / Hz_half;
-    t3 = o * (t3 - cff4 * (FChi - FClo));
-    g3 = o * (g3 - cff4 * (FCLhi - FCLlo));
-    tke[L3 + a2 + wk] = t3;
-    gls[L3 + a2 + wk] = g3;
-    CFlo = CFhi; FClo = FChi; FCLlo = FCLhi;
+    // one field: its Hz-weighted start value of the corrector, its half-step value and its flux through rho-level k+1
+    struct Pre { double start, half, FC; };
+    auto pre = [&](const double *X, double FCl) {
+      const double *Xs = X + Ls + wk;
+      const double xk = Xs[a2];
+      const double x3 = cff * (cff1 * xk + cff2 * X[Li + a2 + wk]) -
+                        cff4 * (flux_c4(gx, XF1, Xs, a2 + 1, i + 1) - flux_c4(gx, XF0, Xs, a2, i) +
+                                flux_c4(gy, EF1, Xs, a2 + ni, j + 1) - flux_c4(gy, EF0, Xs, a2, j));
+      const double FCh = CFhi * vface(X + Ls, a2 + wk + nij, k + 1, N, nij);
+      return Pre{cff * xk, o * (x3 - cff4 * (FCh - FCl)), FCh};
+    };
+    const Pre t = pre(tke, FClo), g = pre(gls, FCLlo);
+    tke[Ln + a2 + wk] = t.start; gls[Ln + a2 + wk] = g.start;
+    tke[L3 + a2 + wk] = t.half; gls[L3 + a2 + wk] = g.half;
+    CFlo = CFhi; FClo = t.FC; FCLlo = g.FC;
   }
 }
 
@@ -342,354 +279,288 @@ struct GlsArgs {
 };
 
 // --------------------------------------------------------- gls_corstep: column --
-__global__ void __launch_bounds__(BLK_X *BLK_Y)
-k_gls_corstep(const RomsDev *__restrict__ c, GlsArgs A)
+// The column of one thread and what the stages of k_gls_corstep share.  T3 / G3: the predictor's half-step values,
+// Ts / Gs: time level nstp, Tn / Gn: nnew (Hz-weighted on entry).
+struct GlsCol {
+  const RomsDev *__restrict__ c; const GlsArgs &A; int i, j; long a2;
+  double dt, cdt;            // cdt = dt*pm*pn
+  bool my25;                 // MY25_MIXING: my25_corstep.F, the same routine up to the vertical terms
+  const double *T3, *G3, *Ts, *Gs; double *Tn, *Gn;
+};
+constexpr double vonKar = 0.41, eps = 1.0E-10;
+
+// shear2 / buoy2 of the column -> A.SH, A.BU, with N2S2_HORAVG (gls_corstep.F:384-440) evaluated on the fly: the
+// reference copies shear2 (not buoy2) across the tile's domain edges before averaging, which is an index clamp here
+__device__ __forceinline__ void gls_n2s2(const GlsCol &q)
 {
-  DEV_PROLOGUE(c)
-  const Blk XB = xcd_block();
-  const int i = b.Istr + XB.x * BLK_X + threadIdx.x;
-  const int j = b.Jstr + XB.y * BLK_Y + threadIdx.y;
-  if (i > b.Iend || j > b.Jend) return;
-  const roms_params_t &p = c->p;
-  const GlsConst &K = A.K;
-  const GlsFac &f = A.f;
-  const int nstp = A.s.nstp, nnew = A.s.nnew;
-  const double dt = p.dt;
-  const double vonKar = 0.41, Gadv = 1.0 / 3.0, eps = 1.0E-10;
-  const bool mk = p.masking != 0;
-  const bool my25 = p.gls_mixing == 2;       // MY25_MIXING: my25_corstep.F, the same routine up to the vertical terms
-  const double gls_p = p.gls_p, gls_m = p.gls_m, gls_n = p.gls_n, gls_cmu0 = p.gls_cmu0;
-  const double gls_c1 = p.gls_c1, gls_c2 = p.gls_c2, gls_sigk = p.gls_sigk, gls_sigp = p.gls_sigp;
-  const double gls_Kmin = p.gls_Kmin, gls_Pmin = p.gls_Pmin;
-  const double Akv_bak = p.Akv_bak, Akk_bak = p.Akk_bak, Akp_bak = p.Akp_bak, AktT_bak = p.Akt_bak[0];
-  (void)gls_p;
-  const double *Huon = c->F.Huon, *Hvom = c->F.Hvom, *Hz = c->F.Hz, *Wv = c->F.W, *z_w = c->F.z_w, *bvf = c->F.bvf;
-  double *tke = c->F.tke, *gls = c->F.gls, *Akv = c->F.Akv, *Akt = c->F.Akt, *Akk = c->F.Akk, *Akp = c->F.Akp, *Lscale = c->F.Lscale;
-  const long Ls = (long)(nstp - 1) * n3w, Ln = (long)(nnew - 1) * n3w, L3 = 2L * n3w;
-  const GradX gx{b, c->F.umask, mk, ni};
-  const GradY gy{b, c->F.vmask, mk, ni};
-  const long a2 = I2(i, j);
-  const double cdt = dt * c->F.pm[a2] * c->F.pn[a2];
-  double *Tn = tke + Ln, *Gn = gls + Ln;
-  // ---- shear2 / buoy2 of the column, with N2S2_HORAVG (:384-440) evaluated on the fly: the reference copies shear2
-  //      (not buoy2) across the tile's domain edges before averaging, which is an index clamp here
-  {
-    const int Istr = b.Istr, Iend = b.Iend, Jstr = b.Jstr, Jend = b.Jend;
-    auto Sfix = [&](int ii, int jj, long wk) {
-      if (b.west_edge && ii == Istr - 1) ii = Istr;
-      if (b.east_edge && ii == Iend + 1) ii = Iend;
-      if (b.south_edge && jj == Jstr - 1) jj = Jstr;
-      if (b.north_edge && jj == Jend + 1) jj = Jend;
-      return A.S[I2(ii, jj) + wk];
-    };
-    for (int k = 1; k <= N - 1; k++) {
-      const long wk = (long)k * nij;
-      double sh, bu;
-      if (p.gls_n2s2_horavg) {
-        auto avgS = [&](int ii, int jj) { return 0.25 * (Sfix(ii, jj, wk) + Sfix(ii + 1, jj, wk) + Sfix(ii, jj + 1, wk) + Sfix(ii + 1, jj + 1, wk)); };
-        auto avgB = [&](int ii, int jj) {
-          const long q = I2(ii, jj) + wk;
-          return 0.25 * (bvf[q] + bvf[q + 1] + bvf[q + ni] + bvf[q + ni + 1]);
-        };
-        bu = 0.25 * (avgB(i, j) + avgB(i - 1, j) + avgB(i, j - 1) + avgB(i - 1, j - 1));
-        sh = 0.25 * (avgS(i, j) + avgS(i - 1, j) + avgS(i, j - 1) + avgS(i - 1, j - 1));
-      } else {
-        sh = A.S[a2 + wk];
-        bu = bvf[a2 + wk];
-      }
-      A.SH[a2 + wk] = sh;
-      A.BU[a2 + wk] = bu;
-    }
-  }
-  // ---- horizontal advection, third-order upstream bias (:444-640)
+  DEV_PROLOGUE(q.c)
+  const GlsArgs &A = q.A;
+  const int i = q.i, j = q.j;
+  const double *bvf = q.c->F.bvf;
+  const int Istr = b.Istr, Iend = b.Iend, Jstr = b.Jstr, Jend = b.Jend;
+  auto Sfix = [&](int ii, int jj, long wk) {
+    if (b.west_edge && ii == Istr - 1) ii = Istr;
+    if (b.east_edge && ii == Iend + 1) ii = Iend;
+    if (b.south_edge && jj == Jstr - 1) jj = Jstr;
+    if (b.north_edge && jj == Jend + 1) jj = Jend;
+    return A.S[I2(ii, jj) + wk];
+  };
   for (int k = 1; k <= N - 1; k++) {
     const long wk = (long)k * nij;
-    const double *T = tke + L3 + wk, *G = gls + L3 + wk;
-    auto fx = [&](int ii, double &FXK, double &FXP) {
-      const long q = (long)(ii - LBi) + (long)(j - LBj) * ni;
-      const double cff = 0.5 * (Huon[q + (long)(k - 1) * nij] + Huon[q + (long)k * nij]);
-      double c1, c2;
-      if (cff > 0.0) {
-        c1 = gx(T, 0, ii, j, LBi, LBj) - gx(T, 0, ii - 1, j, LBi, LBj);          // curvK(ii-1)
-        c2 = gx(G, 0, ii, j, LBi, LBj) - gx(G, 0, ii - 1, j, LBi, LBj);
-      } else {
-        c1 = gx(T, 0, ii + 1, j, LBi, LBj) - gx(T, 0, ii, j, LBi, LBj);          // curvK(ii)
-        c2 = gx(G, 0, ii + 1, j, LBi, LBj) - gx(G, 0, ii, j, LBi, LBj);
-      }
-      FXK = cff * 0.5 * (T[q - 1] + T[q] - Gadv * c1);
-      FXP = cff * 0.5 * (G[q - 1] + G[q] - Gadv * c2);
-    };
-    auto fe = [&](int jj, double &FEK, double &FEP) {
-      const long q = (long)(i - LBi) + (long)(jj - LBj) * ni;
-      const double cff = 0.5 * (Hvom[q + (long)(k - 1) * nij] + Hvom[q + (long)k * nij]);
-      double c1, c2;
-      if (cff > 0.0) {
-        c1 = gy(T, 0, i, jj, LBi, LBj) - gy(T, 0, i, jj - 1, LBi, LBj);
-        c2 = gy(G, 0, i, jj, LBi, LBj) - gy(G, 0, i, jj - 1, LBi, LBj);
-      } else {
-        c1 = gy(T, 0, i, jj + 1, LBi, LBj) - gy(T, 0, i, jj, LBi, LBj);
-        c2 = gy(G, 0, i, jj + 1, LBi, LBj) - gy(G, 0, i, jj, LBi, LBj);
-      }
-      FEK = cff * 0.5 * (T[q - ni] + T[q] - Gadv * c1);
-      FEP = cff * 0.5 * (G[q - ni] + G[q] - Gadv * c2);
+    double sh, bu;
+    if (q.c->p.gls_n2s2_horavg) {
+      auto avgS = [&](int ii, int jj) { return 0.25 * (Sfix(ii, jj, wk) + Sfix(ii + 1, jj, wk) + Sfix(ii, jj + 1, wk) + Sfix(ii + 1, jj + 1, wk)); };
+      auto avgB = [&](int ii, int jj) {
+        const long a = I2(ii, jj) + wk;
+        return 0.25 * (bvf[a] + bvf[a + 1] + bvf[a + ni] + bvf[a + ni + 1]);
+      };
+      bu = 0.25 * (avgB(i, j) + avgB(i - 1, j) + avgB(i, j - 1) + avgB(i - 1, j - 1));
+      sh = 0.25 * (avgS(i, j) + avgS(i - 1, j) + avgS(i, j - 1) + avgS(i - 1, j - 1));
+    } else {
+      sh = A.S[q.a2 + wk];
+      bu = bvf[q.a2 + wk];
+    }
+    A.SH[q.a2 + wk] = sh;
+    A.BU[q.a2 + wk] = bu;
+  }
+}
+
+// the floor of an advected value: gls_corstep.F has one, my25_corstep.F:511-514, :569-576 has none
+__device__ __forceinline__ double adv_floor(const GlsCol &q, double v, double vmin) { return q.my25 ? v : fmax(v, vmin); }
+
+// horizontal advection, third-order upstream bias (gls_corstep.F:444-640)
+__device__ __forceinline__ void gls_hadv(const GlsCol &q)
+{
+  DEV_PROLOGUE(q.c)
+  const int i = q.i, j = q.j;
+  const long a2 = q.a2;
+  const Grad<false> gx = grad_dir<false>(q.c, ni);
+  const Grad<true> gy = grad_dir<true>(q.c, ni);
+  for (int k = 1; k <= N - 1; k++) {
+    const long wk = (long)k * nij;
+    const double *T = q.T3 + wk, *G = q.G3 + wk;
+    auto face = [&](const auto &g, const double *H, long qf, int f, double &FK, double &FP) {      // both fields at one face
+      const double HF = face_transport(H, qf + wk - nij, nij);
+      if (HF > 0.0) { FK = flux_u3(g, HF, T, qf, f, -1); FP = flux_u3(g, HF, G, qf, f, -1); }      // a branch, not a select: gls.h
+      else { FK = flux_u3(g, HF, T, qf, f, 0); FP = flux_u3(g, HF, G, qf, f, 0); }
     };
     double FXK0, FXP0, FXK1, FXP1, FEK0, FEP0, FEK1, FEP1;
-    fx(i, FXK0, FXP0); fx(i + 1, FXK1, FXP1);
-    fe(j, FEK0, FEP0); fe(j + 1, FEK1, FEP1);
-    double tv = Tn[a2 + wk] - cdt * (FXK1 - FXK0 + FEK1 - FEK0);
-    if (!my25) tv = fmax(tv, gls_Kmin);                  // my25_corstep.F:511-514 has no floor
-    double gv = Gn[a2 + wk] - cdt * (FXP1 - FXP0 + FEP1 - FEP0);
-    if (!my25) gv = fmax(gv, gls_Pmin);
-    Tn[a2 + wk] = tv;
-    Gn[a2 + wk] = gv;
+    face(gx, q.c->F.Huon, a2, i, FXK0, FXP0); face(gx, q.c->F.Huon, a2 + 1, i + 1, FXK1, FXP1);
+    face(gy, q.c->F.Hvom, a2, j, FEK0, FEP0); face(gy, q.c->F.Hvom, a2 + ni, j + 1, FEK1, FEP1);
+    const double tv = adv_floor(q, q.Tn[a2 + wk] - q.cdt * (FXK1 - FXK0 + FEK1 - FEK0), q.c->p.gls_Kmin);
+    const double gv = adv_floor(q, q.Gn[a2 + wk] - q.cdt * (FXP1 - FXP0 + FEP1 - FEP0), q.c->p.gls_Pmin);
+    q.Tn[a2 + wk] = tv; q.Gn[a2 + wk] = gv;
   }
-  // ---- vertical advection (:644-700), fourth-order centred with the one-sided end formulas
-  {
-    const double *T = tke + L3, *G = gls + L3;
-    auto vflux = [&](int kk, double &FCK, double &FCP) {
-      const long w = a2 + (long)kk * nij;
-      const double cff = 0.5 * (Wv[w] + Wv[w - nij]);
-      if (kk == 1) {
-        FCK = cff * (1.0 / 3.0 * T[w - nij] + 5.0 / 6.0 * T[w] - 1.0 / 6.0 * T[w + nij]);
-        FCP = cff * (1.0 / 3.0 * G[w - nij] + 5.0 / 6.0 * G[w] - 1.0 / 6.0 * G[w + nij]);
-      } else if (kk == N) {
-        FCK = cff * (1.0 / 3.0 * T[w] + 5.0 / 6.0 * T[w - nij] - 1.0 / 6.0 * T[w - 2 * nij]);
-        FCP = cff * (1.0 / 3.0 * G[w] + 5.0 / 6.0 * G[w - nij] - 1.0 / 6.0 * G[w - 2 * nij]);
-      } else {
-        FCK = cff * (7.0 / 12.0 * (T[w - nij] + T[w]) - 1.0 / 12.0 * (T[w - 2 * nij] + T[w + nij]));
-        FCP = cff * (7.0 / 12.0 * (G[w - nij] + G[w]) - 1.0 / 12.0 * (G[w - 2 * nij] + G[w + nij]));
-      }
-    };
-    double FKlo, FPlo;
-    vflux(1, FKlo, FPlo);
-    for (int k = 1; k <= N - 1; k++) {
-      const long wk = (long)k * nij;
-      double FKhi, FPhi;
-      vflux(k + 1, FKhi, FPhi);
-      double tv = Tn[a2 + wk] - cdt * (FKhi - FKlo);
-      if (!my25) tv = fmax(tv, gls_Kmin);                // my25_corstep.F:569-576
-      double gv = Gn[a2 + wk] - cdt * (FPhi - FPlo);
-      if (!my25) gv = fmax(gv, gls_Pmin);
-      Tn[a2 + wk] = tv;
-      Gn[a2 + wk] = gv;
-      FKlo = FKhi; FPlo = FPhi;
-    }
+}
+
+// vertical advection (gls_corstep.F:644-700), fourth-order centred with the one-sided end formulas
+__device__ __forceinline__ void gls_vadv(const GlsCol &q)
+{
+  DEV_PROLOGUE(q.c)
+  const long a2 = q.a2;
+  const double *Wv = q.c->F.W;
+  auto wface = [&](int kk) { return 0.5 * (Wv[a2 + (long)kk * nij] + Wv[a2 + (long)(kk - 1) * nij]); };
+  double FKlo = wface(1) * vface(q.T3, a2 + nij, 1, N, nij), FPlo = wface(1) * vface(q.G3, a2 + nij, 1, N, nij);
+  for (int k = 1; k <= N - 1; k++) {
+    const long w = a2 + (long)k * nij;
+    const double cff = wface(k + 1);
+    const double FKhi = cff * vface(q.T3, w + nij, k + 1, N, nij), FPhi = cff * vface(q.G3, w + nij, k + 1, N, nij);
+    const double tv = adv_floor(q, q.Tn[w] - q.cdt * (FKhi - FKlo), q.c->p.gls_Kmin);
+    const double gv = adv_floor(q, q.Gn[w] - q.cdt * (FPhi - FPlo), q.c->p.gls_Pmin);
+    q.Tn[w] = tv; q.Gn[w] = gv;
+    FKlo = FKhi; FPlo = FPhi;
   }
-  if (my25) {
-    // ---- MY25_MIXING, my25_corstep.F:580-770: Mellor and Yamada (1982) level 2.5 with the Galperin et al. (1988)
-    //      stability functions (Kantha and Clayson's Sm under KANTHA_CLAYSON); tke = q2, gls = q2l
-    const double my_B1 = 16.6, my_E1 = 1.8, my_E2 = 1.33, my_Gh0 = 0.0233, my_Sq = 0.2, my_lmax = 0.53, my_qmin = 1.0E-8;
-    const double *Ts = tke + Ls, *Gs = gls + Ls;
-    const long wN = a2 + (long)N * nij, w0 = a2;
-    {
-      const double cff = -0.5 * dt;
-      for (int k = 1; k <= N; k++) {
-        const long w = a2 + (long)k * nij, r = a2 + (long)(k - 1) * nij;
-        A.FCK[w] = cff * (Akk[w] + Akk[w - nij]) / Hz[r];
-      }
-    }
-    const double cff3 = my_E2 / (vonKar * vonKar);
-    const double zN = z_w[wN], z0 = z_w[w0];
-    for (int k = 1; k <= N - 1; k++) {
-      const long w = a2 + (long)k * nij, r = a2 + (long)(k - 1) * nij;
-      const double bu = A.BU[w];
-      const double strat2 = ((bu > -5.0E-5) && (bu < 0.0)) ? 0.0 : bu;
-      const double Qprod = A.SH[w] * (Akv[w] - Akv_bak) - strat2 * (Akt[w] - AktT_bak);
-      const double Ls_unlmt = fmax(eps, Gs[w] / (fmax(Ts[w], eps)));
-      const double cff1 = 0.5 * (Hz[r] + Hz[r + nij]);
-      Tn[w] = Tn[w] + dt * cff1 * Qprod * 2.0;
-      Gn[w] = Gn[w] + dt * cff1 * Qprod * my_E1 * Ls_unlmt;
-      const double Qdiss = dt * sqrt(Ts[w]) / (my_B1 * Ls_unlmt);
-      const double zk = z_w[w];
-      const double cff = Ls_unlmt * (1.0 / (zN - zk) + 1.0 / (zk - z0));
-      const double Wscale = 1.0 + cff3 * cff * cff;
-      const double FCKk = A.FCK[w], FCKk1 = A.FCK[w + nij];
-      A.BCK[w] = cff1 * (1.0 + 2.0 * Qdiss) - FCKk - FCKk1;
-      A.BCP[w] = cff1 * (1.0 + Wscale * Qdiss) - FCKk - FCKk1;
-    }
-    {
-      const double sx = c->F.sustr[a2] + c->F.sustr[a2 + 1], sy = c->F.svstr[a2] + c->F.svstr[a2 + ni];
-      const double bx = c->F.bustr[a2] + c->F.bustr[a2 + 1], by = c->F.bvstr[a2] + c->F.bvstr[a2 + ni];
-      Tn[wN] = K.my_B1p2o3 * 0.5 * sqrt(sx * sx + sy * sy);
-      Gn[wN] = 0.0;
-      Tn[w0] = K.my_B1p2o3 * 0.5 * sqrt(bx * bx + by * by);
-      Gn[w0] = 0.0;
-    }
-    // the two tridiagonal systems (:649-692): elimination from the top, substitution from the bottom
-    for (int sys = 0; sys < 2; sys++) {
-      double *X = sys == 0 ? Tn : Gn;
-      const double *BC = sys == 0 ? A.BCK : A.BCP;
-      const long wt = a2 + (long)(N - 1) * nij;
-      double cff = 1.0 / BC[wt];
-      double CFp = cff * A.FCK[wt];
-      A.CF[wt] = CFp;
-      double Xp = cff * (X[wt] - A.FCK[wN] * X[wN]);
-      X[wt] = Xp;
-      for (int k = N - 2; k >= 1; k--) {
-        const long w = a2 + (long)k * nij;
-        const double FCK1 = A.FCK[w + nij];
-        cff = 1.0 / (BC[w] - CFp * FCK1);
-        CFp = cff * A.FCK[w];
-        A.CF[w] = CFp;
-        Xp = cff * (X[w] - FCK1 * Xp);
-        X[w] = Xp;
-      }
-      double Xm = X[w0];
-      for (int k = 1; k <= N - 1; k++) {
-        const long w = a2 + (long)k * nij;
-        Xm = X[w] - A.CF[w] * Xm;
-        X[w] = Xm;
-      }
-    }
-    // mixing coefficients (:699-770)
-    for (int k = 1; k <= N - 1; k++) {
-      const long w = a2 + (long)k * nij;
-      const double tk = fmax(Tn[w], my_qmin), gk = fmax(Gn[w], my_qmin);
-      const double buoy2 = A.BU[w];
-      const double Ls_unlmt = gk / tk;
-      const double Ls_lmt = fmin(Ls_unlmt, my_lmax * sqrt(tk / (fmax(0.0, buoy2) + eps)));
-      const double Gh = fmin(my_Gh0, -buoy2 * Ls_lmt * Ls_lmt / tk);
-      const double cff = 1.0 - K.my_Sh2 * Gh;
-      const double Sh = K.my_Sh1 / cff;
-      double Sm;
-      if (p.gls_stability == GLS_KANTHA_CLAYSON) Sm = (K.my_B1pm1o3 + Sh * Gh * K.my_Sm4) / (1.0 - K.my_Sm2 * Gh);
-      else Sm = (K.my_Sm3 + Sh * Gh * K.my_Sm4) / (1.0 - K.my_Sm2 * Gh);
-      const double ql = 0.5 * (Ls_lmt * sqrt(tk) + Lscale[w] * sqrt(Ts[w]));
-      Tn[w] = tk;
-      Gn[w] = gk;
-      Akv[w] = Akv_bak + ql * Sm;
-      for (int it = 0; it < b.NAT; it++) Akt[w + (long)it * n3w] = p.Akt_bak[it] + ql * Sh;
-      Akk[w] = Akk_bak + ql * my_Sq;
-      Lscale[w] = Ls_lmt;
-    }
-    return;
+}
+
+// The stability functions of Galperin et al. (1988), the same text in gls_corstep.F:1052-1058 and my25_corstep.F:
+// 735-741.  Kantha and Clayson's Sm is NOT: my25_corstep.F has Sh*Gh*my_Sm4, gls_corstep.F my_Sm4*Sh*Gh, which round
+// differently, so each caller writes its own.
+__device__ __forceinline__ double galperin_Sh(const GlsConst &K, double Gh)
+{
+  const double cff = 1.0 - K.my_Sh2 * Gh;
+  return K.my_Sh1 / cff;
+}
+__device__ __forceinline__ double galperin_Sm(const GlsConst &K, double Sh, double Gh)
+{
+  return (K.my_Sm3 + Sh * Gh * K.my_Sm4) / (1.0 - K.my_Sm2 * Gh);
+}
+
+constexpr double my_qmin = 1.0E-8;
+// MY25_MIXING, my25_corstep.F:580-692: Mellor and Yamada (1982) level 2.5; tke = q2, gls = q2l.  Production,
+// dissipation and wall proximity, the Dirichlet values and the two implicit solves.
+__device__ __forceinline__ void my25_column(const GlsCol &q)
+{
+  DEV_PROLOGUE(q.c)
+  const RomsDev *__restrict__ c = q.c;
+  const GlsArgs &A = q.A;
+  const long a2 = q.a2;
+  const double dt = q.dt, my_B1 = 16.6, my_E1 = 1.8, my_E2 = 1.33;
+  const double *Hz = c->F.Hz, *z_w = c->F.z_w, *Akv = c->F.Akv, *Akt = c->F.Akt;
+  const double *Ts = q.Ts, *Gs = q.Gs;
+  double *Tn = q.Tn, *Gn = q.Gn;
+  const double Akv_bak = c->p.Akv_bak, AktT_bak = c->p.Akt_bak[0];
+  const long wN = a2 + (long)N * nij, w0 = a2;
+  diff_coef(A.FCK, c->F.Akk, Hz, a2, nij, dt, 1, N);
+  const double cff3 = my_E2 / (vonKar * vonKar);
+  const double zN = z_w[wN], z0 = z_w[w0];
+  for (int k = 1; k <= N - 1; k++) {
+    const long w = a2 + (long)k * nij, r = a2 + (long)(k - 1) * nij;
+    const double bu = A.BU[w];
+    const double strat2 = ((bu > -5.0E-5) && (bu < 0.0)) ? 0.0 : bu;
+    const double Qprod = A.SH[w] * (Akv[w] - Akv_bak) - strat2 * (Akt[w] - AktT_bak);
+    const double Ls_unlmt = fmax(eps, Gs[w] / (fmax(Ts[w], eps)));
+    const double cff1 = 0.5 * (Hz[r] + Hz[r + nij]);
+    Tn[w] = Tn[w] + dt * cff1 * Qprod * 2.0;
+    Gn[w] = Gn[w] + dt * cff1 * Qprod * my_E1 * Ls_unlmt;
+    const double Qdiss = dt * sqrt(Ts[w]) / (my_B1 * Ls_unlmt);
+    const double zk = z_w[w];
+    const double cff = Ls_unlmt * (1.0 / (zN - zk) + 1.0 / (zk - z0));
+    const double Wscale = 1.0 + cff3 * cff * cff;
+    const double FCKk = A.FCK[w], FCKk1 = A.FCK[w + nij];
+    A.BCK[w] = cff1 * (1.0 + 2.0 * Qdiss) - FCKk - FCKk1;
+    A.BCP[w] = cff1 * (1.0 + Wscale * Qdiss) - FCKk - FCKk1;
   }
+  Tn[wN] = stress_tke(A.K.my_B1p2o3, c->F.sustr, c->F.svstr, a2, ni); Gn[wN] = 0.0;
+  Tn[w0] = stress_tke(A.K.my_B1p2o3, c->F.bustr, c->F.bvstr, a2, ni); Gn[w0] = 0.0;
+  // the two tridiagonal systems (:649-692): the top row carries the Dirichlet value, -FCK(N)*X(N)
+  const long wt = wN - nij;
+  thomas(Tn, A.BCK, A.FCK, A.CF, a2, nij, N, Tn[wt] - A.FCK[wN] * Tn[wN], 0.0, 1);
+  thomas(Gn, A.BCP, A.FCK, A.CF, a2, nij, N, Gn[wt] - A.FCK[wN] * Gn[wN], 0.0, 1);
+}
+
+// ... and its mixing coefficients (my25_corstep.F:699-770): no floors but my_qmin, Akp untouched
+__device__ __forceinline__ void my25_mixing(const GlsCol &q)
+{
+  DEV_PROLOGUE(q.c)
+  const roms_params_t &p = q.c->p;
+  const GlsConst &K = q.A.K;
+  const double my_Gh0 = 0.0233, my_Sq = 0.2, my_lmax = 0.53;
+  double *Akv = q.c->F.Akv, *Akt = q.c->F.Akt, *Akk = q.c->F.Akk, *Lscale = q.c->F.Lscale;
+  for (int k = 1; k <= N - 1; k++) {
+    const long w = q.a2 + (long)k * nij;
+    const double tk = fmax(q.Tn[w], my_qmin), gk = fmax(q.Gn[w], my_qmin);
+    const double buoy2 = q.A.BU[w];
+    const double Ls_unlmt = gk / tk;
+    const double Ls_lmt = fmin(Ls_unlmt, my_lmax * sqrt(tk / (fmax(0.0, buoy2) + eps)));
+    const double Gh = fmin(my_Gh0, -buoy2 * Ls_lmt * Ls_lmt / tk);
+    const double Sh = galperin_Sh(K, Gh);
+    double Sm;
+    if (p.gls_stability == GLS_KANTHA_CLAYSON) Sm = (K.my_B1pm1o3 + Sh * Gh * K.my_Sm4) / (1.0 - K.my_Sm2 * Gh);   // this order here
+    else Sm = galperin_Sm(K, Sh, Gh);
+    const double ql = 0.5 * (Ls_lmt * sqrt(tk) + Lscale[w] * sqrt(q.Ts[w]));
+    q.Tn[w] = tk; q.Gn[w] = gk;
+    Akv[w] = p.Akv_bak + ql * Sm;
+    for (int it = 0; it < b.NAT; it++) Akt[w + (long)it * n3w] = p.Akt_bak[it] + ql * Sh;
+    Akk[w] = p.Akk_bak + ql * my_Sq;
+    Lscale[w] = Ls_lmt;
+  }
+}
+
+// the turbulent length scale of a (tke, gls) pair (gls_corstep.F:761, :1003)
+__device__ __forceinline__ double gls_length(const GlsFac &f, double gls, double tke)
+{
+  return pow(gls, f.gls_exp1) * f.cmu_fac1 * pow(tke, -f.tke_exp1);
+}
+// bottom roughness of the column (gls_corstep.F:846)
+__device__ __forceinline__ double gls_zob(const GlsCol &q) { return fmax(q.c->F.ZoBot[q.a2], 0.0001); }
+
+// GLS_MIXING, gls_corstep.F:706-960: production and dissipation, the Dirichlet values and the two implicit solves
+__device__ __forceinline__ void gls_column(const GlsCol &q)
+{
+  DEV_PROLOGUE(q.c)
+  const RomsDev *__restrict__ c = q.c;
+  const roms_params_t &p = c->p;
+  const GlsArgs &A = q.A;
+  const GlsFac &f = A.f;
+  const long a2 = q.a2;
+  const double dt = q.dt;
+  const double gls_m = p.gls_m, gls_n = p.gls_n, gls_c1 = p.gls_c1, gls_c2 = p.gls_c2;
+  const double gls_Kmin = p.gls_Kmin, gls_Pmin = p.gls_Pmin, Akv_bak = p.Akv_bak, AktT_bak = p.Akt_bak[0];
+  const double *Hz = c->F.Hz, *z_w = c->F.z_w, *Akv = c->F.Akv, *Akt = c->F.Akt, *Akp = c->F.Akp;
+  const double *Ts = q.Ts, *Gs = q.Gs;
+  double *Tn = q.Tn, *Gn = q.Gn;
+  const long wN = a2 + (long)N * nij, w0 = a2, wt = wN - nij;
   // ---- vertical mixing terms, production, dissipation (:706-800)
-  const double *Ts = tke + Ls, *Gs = gls + Ls;
-  {
-    const double cff = -0.5 * dt;
-    for (int k = 2; k <= N - 1; k++) {
-      const long w = a2 + (long)k * nij, r = a2 + (long)(k - 1) * nij;
-      A.FCK[w] = cff * (Akk[w] + Akk[w - nij]) / Hz[r];
-      A.FCP[w] = cff * (Akp[w] + Akp[w - nij]) / Hz[r];
-    }
-    A.FCP[a2 + nij] = 0.0; A.FCP[a2 + (long)N * nij] = 0.0;
-    A.FCK[a2 + nij] = 0.0; A.FCK[a2 + (long)N * nij] = 0.0;
-  }
+  diff_coef(A.FCK, c->F.Akk, Hz, a2, nij, dt, 2, N - 1);
+  diff_coef(A.FCP, Akp, Hz, a2, nij, dt, 2, N - 1);
+  A.FCP[a2 + nij] = 0.0; A.FCP[wN] = 0.0;
+  A.FCK[a2 + nij] = 0.0; A.FCK[wN] = 0.0;
   for (int k = 1; k <= N - 1; k++) {
     const long w = a2 + (long)k * nij, r = a2 + (long)(k - 1) * nij;
     const double strat2 = A.BU[w], shear2 = A.SH[w];
     const double gls_c3 = (strat2 > 0.0) ? p.gls_c3m : p.gls_c3p;
-    const double akt = Akt[w];
-    double Kprod = shear2 * (Akv[w] - Akv_bak) - strat2 * (akt - AktT_bak);
-    double Pprod = gls_c1 * shear2 * (Akv[w] - Akv_bak) - gls_c3 * strat2 * (akt - AktT_bak);
-    double cff1 = 1.0;
-    if (Kprod < 0.0) { Kprod = Kprod + strat2 * (akt - AktT_bak); cff1 = 0.0; }
-    double cff2 = 1.0;
-    if (Pprod < 0.0) { Pprod = Pprod + gls_c3 * strat2 * (akt - AktT_bak); cff2 = 0.0; }
+    // the buoyancy production of the two equations.  The reference writes strat2*(Akt-Akt_bak) five times, but as a
+    // product of its own only in Kprod: dt*(1-cff1)*strat2*(...) and gls_c3*strat2*(...) associate from the left.
+    const double dAkt = Akt[w] - AktT_bak;
+    const double Kbuoy = strat2 * dAkt, Pbuoy = gls_c3 * strat2 * dAkt;
+    double Kprod = shear2 * (Akv[w] - Akv_bak) - Kbuoy;
+    double Pprod = gls_c1 * shear2 * (Akv[w] - Akv_bak) - Pbuoy;
+    double cff1 = 1.0, cff2 = 1.0;
+    if (Kprod < 0.0) { Kprod = Kprod + Kbuoy; cff1 = 0.0; }
+    if (Pprod < 0.0) { Pprod = Pprod + Pbuoy; cff2 = 0.0; }
     const double cff = 0.5 * (Hz[r] + Hz[r + nij]);
     const double tks = Ts[w], gss = Gs[w];
     Tn[w] = Tn[w] + dt * cff * Kprod;
     Gn[w] = Gn[w] + dt * cff * Pprod * gss / fmax(tks, gls_Kmin);
     double wall_fac = 1.0;
     if (f.Lmy25) {
-      const double zN = z_w[a2 + (long)N * nij], z0 = z_w[a2], zk = z_w[w];
-      const double q1 = pow(gss, f.gls_exp1) * f.cmu_fac1 * pow(tks, -f.tke_exp1) * (1.0 / (zk - z0));
-      const double q2 = pow(gss, f.gls_exp1) * f.cmu_fac1 * pow(tks, -f.tke_exp1) * (1.0 / (zN - zk));
-      wall_fac = 1.0 + K.E2 / (vonKar * vonKar) * (q1 * q1) + 0.25 / (vonKar * vonKar) * (q2 * q2);
+      const double zN = z_w[wN], z0 = z_w[w0], zk = z_w[w];
+      const double Ls = gls_length(f, gss, tks);
+      const double q1 = Ls * (1.0 / (zk - z0)), q2 = Ls * (1.0 / (zN - zk));
+      wall_fac = 1.0 + A.K.E2 / (vonKar * vonKar) * (q1 * q1) + 0.25 / (vonKar * vonKar) * (q2 * q2);
     }
-    const double FCKk = A.FCK[w], FCKk1 = A.FCK[w + nij], FCPk = A.FCP[w], FCPk1 = A.FCP[w + nij];
-    A.BCK[w] = cff * (1.0 + dt * pow(gss, -f.gls_exp1) * f.cmu_fac2 * pow(tks, f.tke_exp2) +
-                      dt * (1.0 - cff1) * strat2 * (akt - AktT_bak) / tks) - FCKk - FCKk1;
-    A.BCP[w] = cff * (1.0 + dt * gls_c2 * wall_fac * pow(gss, -f.gls_exp1) * f.cmu_fac2 * pow(tks, f.tke_exp2) +
-                      dt * (1.0 - cff2) * gls_c3 * strat2 * (akt - AktT_bak) / tks) - FCPk - FCPk1;
+    // the dissipation's two powers; dt and gls_c2*wall_fac multiply them from the left, so no common product
+    const double pg = pow(gss, -f.gls_exp1), pt = pow(tks, f.tke_exp2);
+    A.BCK[w] = cff * (1.0 + dt * pg * f.cmu_fac2 * pt + dt * (1.0 - cff1) * strat2 * dAkt / tks) - A.FCK[w] - A.FCK[w + nij];
+    A.BCP[w] = cff * (1.0 + dt * gls_c2 * wall_fac * pg * f.cmu_fac2 * pt + dt * (1.0 - cff2) * gls_c3 * strat2 * dAkt / tks) -
+               A.FCP[w] - A.FCP[w + nij];
   }
   // ---- Dirichlet surface and bottom values (:806-860)
-  const double sus = (c->F.sustr[a2] + c->F.sustr[a2 + 1]), svs = (c->F.svstr[a2] + c->F.svstr[a2 + ni]);
-  const double bus = (c->F.bustr[a2] + c->F.bustr[a2 + 1]), bvs = (c->F.bvstr[a2] + c->F.bvstr[a2 + ni]);
-  const long wN = a2 + (long)N * nij, w0 = a2;
-  const double tkeN = fmax(f.cmu_fac3 * 0.5 * sqrt(sus * sus + svs * svs), gls_Kmin);
-  const double tke0 = fmax(f.cmu_fac3 * 0.5 * sqrt(bus * bus + bvs * bvs), gls_Kmin);
-  Tn[wN] = tkeN;
-  Tn[w0] = tke0;
-  const double Zos_eff = f.Zos_min;
-  const double Zob_min = fmax(c->F.ZoBot[a2], 0.0001);
+  const double tkeN = fmax(stress_tke(f.cmu_fac3, c->F.sustr, c->F.svstr, a2, ni), gls_Kmin);
+  const double tke0 = fmax(stress_tke(f.cmu_fac3, c->F.bustr, c->F.bvstr, a2, ni), gls_Kmin);
+  Tn[wN] = tkeN; Tn[w0] = tke0;
+  const double Zos_eff = f.Zos_min, Zob_min = gls_zob(q);
   Gn[wN] = fmax(f.cmu0p * pow(tkeN, gls_m) * pow(f.L_sft * Zos_eff, gls_n), gls_Pmin);
-  {
-    const double cff = f.gls_fac4 * pow(vonKar * Zob_min, gls_n);
-    Gn[w0] = fmax(cff * pow(tke0, gls_m), gls_Pmin);
-  }
-  // ---- tri-diagonal system for tke (:864-895): elimination from the top, substitution from the bottom
-  {
-    const double tke_fluxt = 0.0, tke_fluxb = 0.0;
-    const long wt = a2 + (long)(N - 1) * nij;
-    double cff = 1.0 / A.BCK[wt];
-    double CFp = cff * A.FCK[wt];
-    A.CF[wt] = CFp;
-    double Tp = cff * (Tn[wt] + tke_fluxt);
-    Tn[wt] = Tp;
-    for (int k = N - 2; k >= 1; k--) {
-      const long w = a2 + (long)k * nij;
-      const double FCK1 = A.FCK[w + nij];
-      cff = 1.0 / (A.BCK[w] - CFp * FCK1);
-      CFp = cff * A.FCK[w];
-      A.CF[w] = CFp;
-      Tp = cff * (Tn[w] - FCK1 * Tp);
-      Tn[w] = Tp;
-    }
-    Tn[a2 + nij] = Tn[a2 + nij] - cff * tke_fluxb;
-    double Tm = Tn[a2 + nij];
-    for (int k = 2; k <= N - 1; k++) {
-      const long w = a2 + (long)k * nij;
-      Tm = Tn[w] - A.CF[w] * Tm;
-      Tn[w] = Tm;
-    }
-  }
+  const double cffb = f.gls_fac4 * pow(vonKar * Zob_min, gls_n);
+  Gn[w0] = fmax(cffb * pow(tke0, gls_m), gls_Pmin);
+  // ---- tri-diagonal system for tke (:864-895); tke_fluxt and tke_fluxb are literal zeros there, and their operations
+  //      are kept (x + 0.0 and x - cff*0.0 are not x for every x)
+  const double tke_fluxt = 0.0, tke_fluxb = 0.0;
+  thomas(Tn, A.BCK, A.FCK, A.CF, a2, nij, N, Tn[wt] + tke_fluxt, tke_fluxb, 2);
   // ---- tri-diagonal system for gls (:899-960)
-  {
-    const long wt = a2 + (long)(N - 1) * nij;
-    double cffa = 0.5 * (Tn[wN] + Tn[wt]);
-    const double gls_fluxt = dt * f.gls_fac3 * pow(cffa, gls_m) * pow(f.L_sft, gls_n) *
-                             pow(Zos_eff + 0.5 * Hz[a2 + (long)(N - 1) * nij], gls_n - 1.0) * 0.5 * (Akp[wN] + Akp[wt]);
-    cffa = 0.5 * (Tn[w0] + Tn[a2 + nij]);
-    const double gls_fluxb = dt * f.gls_fac2 * (pow(cffa, gls_m)) * pow(0.5 * Hz[a2] + Zob_min, gls_n - 1.0) * 0.5 *
-                             (Akp[w0] + Akp[a2 + nij]);
-    double cff = 1.0 / A.BCP[wt];
-    double CFp = cff * A.FCP[wt];
-    A.CF[wt] = CFp;
-    double Gp = cff * (Gn[wt] - gls_fluxt);
-    Gn[wt] = Gp;
-    for (int k = N - 2; k >= 1; k--) {
-      const long w = a2 + (long)k * nij;
-      const double FCP1 = A.FCP[w + nij];
-      cff = 1.0 / (A.BCP[w] - CFp * FCP1);
-      CFp = cff * A.FCP[w];
-      A.CF[w] = CFp;
-      Gp = cff * (Gn[w] - FCP1 * Gp);
-      Gn[w] = Gp;
-    }
-    Gn[a2 + nij] = Gn[a2 + nij] - cff * gls_fluxb;
-    double Gm = Gn[a2 + nij];
-    for (int k = 2; k <= N - 1; k++) {
-      const long w = a2 + (long)k * nij;
-      Gm = Gn[w] - A.CF[w] * Gm;
-      Gn[w] = Gm;
-    }
-  }
-  // ---- vertical mixing coefficients (:964-1095)
+  double cffa = 0.5 * (Tn[wN] + Tn[wt]);
+  const double gls_fluxt = dt * f.gls_fac3 * pow(cffa, gls_m) * pow(f.L_sft, gls_n) *
+                           pow(Zos_eff + 0.5 * Hz[a2 + (long)(N - 1) * nij], gls_n - 1.0) * 0.5 * (Akp[wN] + Akp[wt]);
+  cffa = 0.5 * (Tn[w0] + Tn[a2 + nij]);
+  const double gls_fluxb = dt * f.gls_fac2 * (pow(cffa, gls_m)) * pow(0.5 * Hz[a2] + Zob_min, gls_n - 1.0) * 0.5 *
+                           (Akp[w0] + Akp[a2 + nij]);
+  thomas(Gn, A.BCP, A.FCP, A.CF, a2, nij, N, Gn[wt] - gls_fluxt, gls_fluxb, 2);
+}
+
+// ... and its mixing coefficients (gls_corstep.F:964-1095)
+__device__ __forceinline__ void gls_mixing(const GlsCol &q)
+{
+  DEV_PROLOGUE(q.c)
+  const RomsDev *__restrict__ c = q.c;
+  const roms_params_t &p = c->p;
+  const GlsConst &K = q.A.K;
+  const GlsFac &f = q.A.f;
+  const long a2 = q.a2;
+  const double gls_m = p.gls_m, gls_n = p.gls_n, gls_cmu0 = p.gls_cmu0, gls_sigk = p.gls_sigk, gls_sigp = p.gls_sigp;
+  const double gls_Kmin = p.gls_Kmin, gls_Pmin = p.gls_Pmin, Akv_bak = p.Akv_bak, Akk_bak = p.Akk_bak, Akp_bak = p.Akp_bak;
+  double *Akv = c->F.Akv, *Akt = c->F.Akt, *Akk = c->F.Akk, *Akp = c->F.Akp, *Lscale = c->F.Lscale;
+  double *Tn = q.Tn, *Gn = q.Gn;
+  const long wN = a2 + (long)N * nij, w0 = a2;
   const int NAT = b.NAT;
   for (int k = 1; k <= N - 1; k++) {
     const long w = a2 + (long)k * nij;
-    const double buoy2 = A.BU[w], shear2 = A.SH[w];
-    double tk = fmax(Tn[w], gls_Kmin);
-    double gk = fmax(Gn[w], gls_Pmin);
+    const double buoy2 = q.A.BU[w], shear2 = q.A.SH[w];
+    double tk = fmax(Tn[w], gls_Kmin), gk = fmax(Gn[w], gls_Pmin);
     const double lim = f.gls_fac5 * pow(tk, f.tke_exp4) * pow(sqrt(fmax(0.0, buoy2)) + eps, -gls_n);
     if (gls_n >= 0.0) gk = fmin(gk, lim);
     else gk = fmax(gk, lim);
-    const double Ls_unlmt = fmax(eps, pow(gk, f.gls_exp1) * f.cmu_fac1 * pow(tk, -f.tke_exp1));
-    double Ls_lmt;
-    if (buoy2 > 0.0) Ls_lmt = fmin(Ls_unlmt, sqrt(0.56 * tk / (fmax(0.0, buoy2) + eps)));
-    else Ls_lmt = Ls_unlmt;
+    const double Ls_unlmt = fmax(eps, gls_length(f, gk, tk));
+    const double Ls_lmt = buoy2 > 0.0 ? fmin(Ls_unlmt, sqrt(0.56 * tk / (fmax(0.0, buoy2) + eps))) : Ls_unlmt;
     gk = fmax(f.cmu0p * pow(tk, gls_m) * pow(Ls_lmt, gls_n), gls_Pmin);
     double Gh = fmin(K.Gh0, -buoy2 * Ls_lmt * Ls_lmt / (2.0 * tk));
     Gh = fmin(Gh, Gh - ((Gh - K.Ghcri) * (Gh - K.Ghcri)) / (Gh + K.Gh0 - 2.0 * K.Ghcri));
@@ -703,38 +574,50 @@ k_gls_corstep(const RomsDev *__restrict__ c, GlsArgs A)
                          K.b5 * (f6 * f6) * Gm * Gm;
       Sm = (K.s0 - K.s1 * f6 * Gh + K.s2 * f6 * Gm) / cff;
       Sh = (K.s4 - K.s5 * f6 * Gh + K.s6 * f6 * Gm) / cff;
-      Sm = fmax(Sm, 0.0);
-      Sh = fmax(Sh, 0.0);
+      Sm = fmax(Sm, 0.0); Sh = fmax(Sh, 0.0);
       Sm = Sm * f.sqrt2 / (gls_cmu0 * gls_cmu0 * gls_cmu0);
       Sh = Sh * f.sqrt2 / (gls_cmu0 * gls_cmu0 * gls_cmu0);
-    } else if (p.gls_stability == GLS_KANTHA_CLAYSON) {
-      const double cff = 1.0 - K.my_Sh2 * Gh;
-      Sh = K.my_Sh1 / cff;
-      Sm = (K.my_B1pm1o3 + K.my_Sm4 * Sh * Gh) / (1.0 - K.my_Sm2 * Gh);
     } else {
-      const double cff = 1.0 - K.my_Sh2 * Gh;
-      Sh = K.my_Sh1 / cff;
-      Sm = (K.my_Sm3 + Sh * Gh * K.my_Sm4) / (1.0 - K.my_Sm2 * Gh);
+      Sh = galperin_Sh(K, Gh);
+      if (p.gls_stability == GLS_KANTHA_CLAYSON) Sm = (K.my_B1pm1o3 + K.my_Sm4 * Sh * Gh) / (1.0 - K.my_Sm2 * Gh);   // this order here
+      else Sm = galperin_Sm(K, Sh, Gh);
     }
-    const double ql = f.sqrt2 * 0.5 * (Ls_lmt * sqrt(tk) + Lscale[w] * sqrt(Ts[w]));
-    Tn[w] = tk;
-    Gn[w] = gk;
+    const double ql = f.sqrt2 * 0.5 * (Ls_lmt * sqrt(tk) + Lscale[w] * sqrt(q.Ts[w]));
+    Tn[w] = tk; Gn[w] = gk;
     Akv[w] = Akv_bak + Sm * ql;
     for (int it = 0; it < NAT; it++) Akt[w + (long)it * n3w] = p.Akt_bak[it] + Sh * ql;
     Akk[w] = Akk_bak + Sm * ql / gls_sigk;
     Akp[w] = Akp_bak + Sm * ql * f.ogls_sigp;
     Lscale[w] = Ls_lmt;
   }
+  const double Zos_eff = f.Zos_min, Zob_min = gls_zob(q);
   Akv[wN] = Akv_bak + f.L_sft * Zos_eff * gls_cmu0 * sqrt(Tn[wN]);
   Akv[w0] = Akv_bak + vonKar * Zob_min * gls_cmu0 * sqrt(Tn[w0]);
   Akk[wN] = Akk_bak + Akv[wN] / gls_sigk;
   Akk[w0] = Akk_bak + Akv[w0] / gls_sigk;
   Akp[wN] = Akp_bak + Akv[wN] * f.ogls_sigp;
   Akp[w0] = Akp_bak + Akv[w0] / gls_sigp;
-  for (int it = 0; it < NAT; it++) {
-    Akt[wN + (long)it * n3w] = p.Akt_bak[it];
-    Akt[w0 + (long)it * n3w] = p.Akt_bak[it];
-  }
+  for (int it = 0; it < NAT; it++) Akt[wN + (long)it * n3w] = Akt[w0 + (long)it * n3w] = p.Akt_bak[it];
+}
+
+__global__ void __launch_bounds__(BLK_X *BLK_Y)
+k_gls_corstep(const RomsDev *__restrict__ c, GlsArgs A)
+{
+  DEV_PROLOGUE(c)
+  const Blk XB = xcd_block();
+  const int i = b.Istr + XB.x * BLK_X + threadIdx.x;
+  const int j = b.Jstr + XB.y * BLK_Y + threadIdx.y;
+  if (i > b.Iend || j > b.Jend) return;
+  double *tke = c->F.tke, *gls = c->F.gls;
+  const long Ls = (long)(A.s.nstp - 1) * n3w, Ln = (long)(A.s.nnew - 1) * n3w, L3 = 2L * n3w;
+  const long a2 = I2(i, j);
+  const GlsCol q{c, A, i, j, a2, c->p.dt, c->p.dt * c->F.pm[a2] * c->F.pn[a2], c->p.gls_mixing == 2,
+                 tke + L3, gls + L3, tke + Ls, gls + Ls, tke + Ln, gls + Ln};
+  gls_n2s2(q);
+  gls_hadv(q);
+  gls_vadv(q);
+  if (q.my25) { my25_column(q); my25_mixing(q); }
+  else { gls_column(q); gls_mixing(q); }
 }
 
 // lateral conditions of Akv and Akt as gls_corstep.F:1100-1185 writes them: on every tile that holds a domain edge
