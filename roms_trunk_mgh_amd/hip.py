@@ -142,20 +142,27 @@ class RomsHip:
         if nccl_unique_id is not None:
             self._uid = C.create_string_buffer(bytes(nccl_unique_id), 128)
             uid = C.cast(self._uid, C.c_void_p)
-        self._chk(self.l.roms_hip_init(rank, b.ntileI, b.ntileJ, device, uid), "init")
-        self._chk(self.l.roms_hip_set_bounds(C.byref(b)), "set_bounds")
-        self._chk(self.l.roms_hip_set_params(C.byref(state.p)), "set_params")
-        for name, _, _ in abi.FIELDS:
-            if name in leave_unregistered:
-                continue
-            a = state.arr[name]
-            self._chk(self.l.roms_hip_register_field(abi.FIELD_ID[name], a.ctypes.data, a.size),
-                      "register_field " + name)
-        self._chk(self.l.roms_hip_sync_all_to_device(), "sync_all_to_device")
-        if getattr(state, "sources", None) is not None:
-            self.set_sources(state.sources)
-        if getattr(state, "clima", None) is not None:
-            self.set_clima(state.clima)
+        try:
+            self._chk(self.l.roms_hip_init(rank, b.ntileI, b.ntileJ, device, uid), "init")
+            self._chk(self.l.roms_hip_set_bounds(C.byref(b)), "set_bounds")
+            self._chk(self.l.roms_hip_set_params(C.byref(state.p)), "set_params")
+            for name, _, _ in abi.FIELDS:
+                if name in leave_unregistered:
+                    continue
+                a = state.arr[name]
+                self._chk(self.l.roms_hip_register_field(abi.FIELD_ID[name], a.ctypes.data, a.size),
+                          "register_field " + name)
+            self._chk(self.l.roms_hip_sync_all_to_device(), "sync_all_to_device")
+            if getattr(state, "sources", None) is not None:
+                self.set_sources(state.sources)
+            if getattr(state, "clima", None) is not None:
+                self.set_clima(state.clima)
+        except Exception:
+            # a refused set-up (more levels than ROMS_MAXN, say) leaves no half-made context behind: the next
+            # RomsHip() would otherwise fail while closing it (check_guards without bounds)
+            RomsHip._live = None
+            self.l.roms_hip_finalize()
+            raise
 
     def set_sources(self, src):
         """SOURCES(ng) with LuvSrc (roms_trunk_mgh_amd/sources.py) -> roms_hip_set_sources"""

@@ -41,6 +41,20 @@ VARIANTS = ["island", "closed", "open_island", "radnud"]
 BASIN_OF = {"w3": "closed", "w10": "open_island", "thin": "radnud"}      # the basin variant of the shapes other than w8
 NEEDS_4_LEVELS = ("pre_step3d", "rhs3d_tile", "rhs3d", "step3d_t")
 I0 = 1                                  # Istr of the one-tile grids
+
+
+def shape_of(shape):
+    """(dimensions, configuration) of a shape: a name of SHAPES, or that pair itself where the caller brings its own
+    shape (tests/test_gpu_levels.py)"""
+    return (SHAPES[shape], CONFIG[shape]) if isinstance(shape, str) else shape
+
+
+def dims(shape):
+    return shape_of(shape)[0]
+
+
+def config_of(shape):
+    return shape_of(shape)[1]
 SEAM = range(I0 + 62, I0 + 67)          # the columns around the first seam (Istr+63 | Istr+64)
 LAND_ROW = 2
 
@@ -110,7 +124,7 @@ def seam_land(shape):
 
 
 def seam_dry(shape):
-    row = 3 if SHAPES[shape]["Mm"] > 3 else 1      # dry | wet | dry dry: u-faces -1, 1, 0 at Istr+62 .. Istr+64
+    row = 3 if dims(shape)["Mm"] > 3 else 1        # dry | wet | dry dry: u-faces -1, 1, 0 at Istr+62 .. Istr+64
     return [(I0 + 61, row), (I0 + 63, row), (I0 + 64, row)]
 
 
@@ -128,7 +142,7 @@ def _edges(st, variant):
 
 
 def _kw(shape, variant, ov=None, wet=False):
-    o = dict(SHAPES[shape], **(ov or {}))
+    o = dict(dims(shape), **(ov or {}))
     if variant != "island":
         o["EWperiodic"] = False
     masked = "island" in variant
@@ -137,14 +151,14 @@ def _kw(shape, variant, ov=None, wet=False):
 
 
 def prepared(shape, variant, ov=None, NT=None, wet=False, config=None):
-    st = util.prepared_state(config or CONFIG[shape], NT=NT, **_kw(shape, variant, ov, wet))
+    st = util.prepared_state(config or config_of(shape), NT=NT, **_kw(shape, variant, ov, wet))
     return _edges(st, variant)
 
 
 def tile(shape, variant, ov=None, NT=None, config=None):
     """ana.make_tile for the whole-step runs, with the seam's land"""
     kw = _kw(shape, variant, ov)
-    st = ana.make_tile(config or CONFIG[shape], perturb=1.0, NT=NT, overrides=kw["overrides"], mask=kw["mask"])
+    st = ana.make_tile(config or config_of(shape), perturb=1.0, NT=NT, overrides=kw["overrides"], mask=kw["mask"])
     if kw["land"]:
         util.add_land(st, kw["land"])
     if variant in ("open_island", "radnud"):
@@ -186,7 +200,7 @@ def _detune_forcing(st):
 
 
 def _base(label, shape, variant):
-    ov = _mix_ov(CONFIG[shape]) if label in ("t3dmix2", "uv3dmix2", "rhs3d") else None
+    ov = _mix_ov(config_of(shape)) if label in ("t3dmix2", "uv3dmix2", "rhs3d") else None
     st = prepared(shape, variant, ov)
     if label == "step3d_t":
         util.hz_weighted_tnew(st)
@@ -204,7 +218,7 @@ DIF4 = {"UPWELLING": {"ts_dif4": 1, "uv_vis4": 1, "tnu4": 2.0e7, "visc4": 4.0e7}
 
 
 def _dif4(label, shape, variant):
-    st = prepared(shape, variant, DIF4[CONFIG[shape]])
+    st = prepared(shape, variant, DIF4[config_of(shape)])
     assert st.b.NghostPoints == 3 and st.p.uv_vis4 == 1
     return st, _calls(label.split(":")[0])
 
@@ -219,7 +233,7 @@ def _iso(label, shape, variant):
     """tests/ref_worker.py::iso_state with TS_MIX_STABILITY and TS_MIX_MIN_STRAT: a weakly and a strongly stratified band
     of columns; nrhs = 3 and nstp = 1 distinct, so that the 1/4 part of the stability form counts"""
     import oracle
-    ov = dict(DIF4[CONFIG[shape]], mix_iso_ts=1, tnu2=300.0, ts_mix_stability=1, ts_mix_min_strat=1)
+    ov = dict(DIF4[config_of(shape)], mix_iso_ts=1, tnu2=300.0, ts_mix_stability=1, ts_mix_min_strat=1)
     st = prepared(shape, variant, ov)
     assert st.p.mix_iso_ts == 1 and st.p.ts_mix_stability == 1 and st.p.ts_mix_min_strat == 1
     oracle.Oracle(st).call("rho_eos", util.step_idx())
@@ -235,7 +249,7 @@ def _iso(label, shape, variant):
 def _gls(label, shape, variant):
     kernel, gset = label.split(":")
     kw = _kw(shape, variant)
-    st = util.gls_state(CONFIG[shape], gls=gset, mask=kw["mask"], extra=kw["overrides"], land=kw["land"])
+    st = util.gls_state(config_of(shape), gls=gset, mask=kw["mask"], extra=kw["overrides"], land=kw["land"])
     _edges(st, variant)
     if variant == "open_island":                             # tkebc: the tracers' condition, closed or gradient only
         for sd in range(4):
@@ -322,7 +336,7 @@ def seam_sources(shape):
     """(I, J, Dsrc, fraction): a u-face and a cell-centred source in the first column of the second workgroup, a v-face
     source in the last column of the first, a v-face and a cell-centred one further into the second; none on the seam's
     land or dry cells"""
-    Mm = SHAPES[shape]["Mm"]
+    Mm = dims(shape)["Mm"]
     if Mm < 4:
         return [(I0 + 64, 1, 0, 0.5), (I0 + 63, 1, 1, 0.4), (I0 + 65, 1, 1, 0.3), (I0 + 64, 1, 2, 0.3), (I0 + 66, 3, 2, -0.2)]
     jm = Mm // 2 + 1
@@ -413,7 +427,7 @@ def run_calls(be, calls):
 
 
 def refused(shape, calls):
-    return SHAPES[shape]["N"] < 4 and any(k in NEEDS_4_LEVELS for k, _ in calls)
+    return dims(shape)["N"] < 4 and any(k in NEEDS_4_LEVELS for k, _ in calls)
 
 
 def run_oracle(st0, calls):
