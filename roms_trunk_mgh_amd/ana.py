@@ -253,6 +253,51 @@ GLS_SETS = {
 }
 
 
+def derived_metrics(st, pm, pn, f):
+    """metrics.F: every array derived from pm, pn and f (arrays over the allocated range of the state's tile), written
+    into the state.  pm, pn and f themselves are not written."""
+    A, b = st.arr, st.b
+    A["om_r"][:] = 1.0 / pm
+    A["on_r"][:] = 1.0 / pn
+    A["omn"][:] = 1.0 / (pm * pn)
+    A["fomn"][:] = f * A["omn"]
+    A["pnom_r"][:] = pn / pm
+    A["pmon_r"][:] = pm / pn
+    s = slice(1, None)
+    m = slice(0, -1)
+    A["pmon_u"][s, :] = (pm[m, :] + pm[s, :]) / (pn[m, :] + pn[s, :])
+    A["pnom_u"][s, :] = (pn[m, :] + pn[s, :]) / (pm[m, :] + pm[s, :])
+    A["om_u"][s, :] = 2.0 / (pm[m, :] + pm[s, :])
+    A["on_u"][s, :] = 2.0 / (pn[m, :] + pn[s, :])
+    A["pmon_v"][:, s] = (pm[:, m] + pm[:, s]) / (pn[:, m] + pn[:, s])
+    A["pnom_v"][:, s] = (pn[:, m] + pn[:, s]) / (pm[:, m] + pm[:, s])
+    A["om_v"][:, s] = 2.0 / (pm[:, m] + pm[:, s])
+    A["on_v"][:, s] = 2.0 / (pn[:, m] + pn[:, s])
+    pm4 = pm[m, m] + pm[m, s] + pm[s, m] + pm[s, s]
+    pn4 = pn[m, m] + pn[m, s] + pn[s, m] + pn[s, s]
+    A["pnom_p"][s, s] = pn4 / pm4
+    A["pmon_p"][s, s] = pm4 / pn4
+    A["om_p"][s, s] = 4.0 / pm4
+    A["on_p"][s, s] = 4.0 / pn4
+    # metrics.F exchanges the u- and psi-type combinations: their western-most ghost column is the periodic image
+    if b.EWperiodic and b.ntileI == 1:
+        for name in ("pmon_u", "pnom_u", "om_u", "on_u", "pmon_p", "pnom_p", "om_p", "on_p"):
+            A[name][0, :] = A[name][b.Lm, :]
+
+
+def curvature_metrics(st, pm, pn):
+    """ana_grid.h:757-770 (CURVGRID && UV_ADV): dndx, dmde by centred differences; interior rows only, wall rows stay 0"""
+    A, b = st.arr, st.b
+    c = slice(1, -1)
+    dndx = np.zeros((st.ni, st.nj))
+    dmde = np.zeros((st.ni, st.nj))
+    dndx[c, :] = 0.5 * (1.0 / pn[2:, :] - 1.0 / pn[:-2, :])
+    dmde[:, c] = 0.5 * (1.0 / pm[:, 2:] - 1.0 / pm[:, :-2])
+    jlo, jhi = st.J(max(b.LBj, 1)), st.J(min(b.UBj, b.Mm))
+    A["dndx"][:, jlo:jhi + 1] = dndx[:, jlo:jhi + 1]
+    A["dmde"][:, jlo:jhi + 1] = dmde[:, jlo:jhi + 1]
+
+
 def _grid_global(cfg, b, st):
     """Fill the 2-D grid arrays over the whole allocated range of tile bounds b
     (analytic functions are evaluated directly at ghost indices, which equals
@@ -311,43 +356,10 @@ def _grid_global(cfg, b, st):
         hb = np.where(d > 0.0, 0.25 * d + 0.15 * d * d, 0.25 * d)
         h = np.minimum(h, hb * ones)
     A["h"][:] = h
-    # ---- metrics.F ----
-    A["om_r"][:] = 1.0 / pm
-    A["on_r"][:] = 1.0 / pn
-    A["omn"][:] = 1.0 / (pm * pn)
-    A["fomn"][:] = f * A["omn"]
-    A["pnom_r"][:] = pn / pm
-    A["pmon_r"][:] = pm / pn
-    s = slice(1, None)
-    m = slice(0, -1)
-    A["pmon_u"][s, :] = (pm[m, :] + pm[s, :]) / (pn[m, :] + pn[s, :])
-    A["pnom_u"][s, :] = (pn[m, :] + pn[s, :]) / (pm[m, :] + pm[s, :])
-    A["om_u"][s, :] = 2.0 / (pm[m, :] + pm[s, :])
-    A["on_u"][s, :] = 2.0 / (pn[m, :] + pn[s, :])
-    A["pmon_v"][:, s] = (pm[:, m] + pm[:, s]) / (pn[:, m] + pn[:, s])
-    A["pnom_v"][:, s] = (pn[:, m] + pn[:, s]) / (pm[:, m] + pm[:, s])
-    A["om_v"][:, s] = 2.0 / (pm[:, m] + pm[:, s])
-    A["on_v"][:, s] = 2.0 / (pn[:, m] + pn[:, s])
-    pm4 = pm[m, m] + pm[m, s] + pm[s, m] + pm[s, s]
-    pn4 = pn[m, m] + pn[m, s] + pn[s, m] + pn[s, s]
-    A["pnom_p"][s, s] = pn4 / pm4
-    A["pmon_p"][s, s] = pm4 / pn4
-    A["om_p"][s, s] = 4.0 / pm4
-    A["on_p"][s, s] = 4.0 / pn4
-    # metrics.F exchanges the u- and psi-type combinations: their western-most ghost column is the periodic image
-    if b.EWperiodic and b.ntileI == 1:
-        for name in ("pmon_u", "pnom_u", "om_u", "on_u", "pmon_p", "pnom_p", "om_p", "on_p"):
-            A[name][0, :] = A[name][Lm, :]
-    # ana_grid.h:757-770 (CURVGRID && UV_ADV): interior rows only, wall rows stay 0
+    derived_metrics(st, pm, pn, f)
+    # ana_grid.h:757-770 (CURVGRID && UV_ADV)
     if app == "BENCHMARK":
-        c = slice(1, -1)
-        dndx = np.zeros((ni, nj))
-        dmde = np.zeros((ni, nj))
-        dndx[c, :] = 0.5 * (1.0 / pn[2:, :] - 1.0 / pn[:-2, :])
-        dmde[:, c] = 0.5 * (1.0 / pm[:, 2:] - 1.0 / pm[:, :-2])
-        jlo, jhi = st.J(max(b.LBj, 1)), st.J(min(b.UBj, Mm))
-        A["dndx"][:, jlo:jhi + 1] = dndx[:, jlo:jhi + 1]
-        A["dmde"][:, jlo:jhi + 1] = dmde[:, jlo:jhi + 1]
+        curvature_metrics(st, pm, pn)
     # horizontal mixing coefficients (ini_hmixcoef.F: uniform, not grid-scaled here)
     A["visc2_r"][:] = cfg["visc2"]
     A["visc2_p"][:] = cfg["visc2"]

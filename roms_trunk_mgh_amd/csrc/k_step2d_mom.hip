@@ -557,7 +557,8 @@ k2d_mom_lds(const RomsDev *__restrict__ c, S2 s, const double *__restrict__ DUon
   }
 }
 
-// One workgroup per (row, metric array): is the row constant in i (bit for bit) over LBi:UBi?  Lane 0 stores the
+// One workgroup per (row, metric array): is the row constant in i (bit for bit) over Istr-NghostPoints :
+// Iend+NghostPoints (clamped to the allocated LBi:UBi)?  Lane 0 stores the
 // row's value in the table; any difference raises the flag.
 __global__ void k_rowm_build(const RomsDev *__restrict__ c, double *__restrict__ tab, int *__restrict__ flag)
 {
@@ -571,9 +572,11 @@ __global__ void k_rowm_build(const RomsDev *__restrict__ c, double *__restrict__
     if (threadIdx.x == 0) tab[(long)jr * RM_COUNT + f] = 0.0;
     return;
   }
-  // the columns a kernel can read: the tile's own and two on either side (ghost columns; the reference's padding
-  // column beyond them is never read and need not be filled)
-  const int i0 = (b.Istr - 2 > b.LBi) ? b.Istr - 2 : b.LBi, i1 = (b.Iend + 2 < b.UBi) ? b.Iend + 2 : b.UBi;
+  // the columns a kernel can read: the tile's own and the ghost columns on either side -- two, or three with UV_VIS4,
+  // whose biharmonic stress reads pn at Istr-3 (the reference's padding column beyond them is never read and need
+  // not be filled)
+  const int ng = b.NghostPoints;
+  const int i0 = (b.Istr - ng > b.LBi) ? b.Istr - ng : b.LBi, i1 = (b.Iend + ng < b.UBi) ? b.Iend + ng : b.UBi;
   const unsigned long long *row = reinterpret_cast<const unsigned long long *>(a + (long)jr * ni) - LBi;
   const unsigned long long v0 = row[b.Istr];
   bool differs = false;

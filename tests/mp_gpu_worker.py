@@ -39,6 +39,12 @@ def run_rank(rank, world, ntI, ntJ, config, nsteps, port, outdir, variant=""):
     if "geouv" in opts:                  # UV_VIS2 with MIX_GEO_UV (uv3dmix2_geo.h)
         kw.setdefault("overrides", {}).update({"uv_vis2": 2, **({"visc2": 50.0} if config == "SEAMOUNT" else {})})
     st = ana.make_tile(config, ntileI=ntI, ntileJ=ntJ, tile=rank, perturb=1.0, **kw)
+    if opts & {"curv", "curveast", "edge"}:
+        import curv_util as cv
+        if "edge" in opts:               # pn differs along one column that the eastern tile holds as ghost column Istr-3 only
+            cv.ghost_only_column(st)
+        else:                            # a curvilinear grid; curveast: in the eastern tile's columns only
+            cv.curvilinear(st, columns=cv.east_columns(st.b) if "curveast" in opts else None)
     if "river" in opts:                  # point sources (LuvSrc) in the walls and, with a mask, on the island's coast
         import util
         util.river_sources(st, "all" if "wells" in opts else "both" if "mask" in opts else "walls")
@@ -61,6 +67,7 @@ def run_rank(rank, world, ntI, ntJ, config, nsteps, port, outdir, variant=""):
     m = main3d.Main3D(be, physics=("physics" in opts), diagnostics=("physics" in opts))
     m.initial()
     m.run(nsteps)
+    rowm = be.row_metrics_state()
     be.to_host()
     be.close()
     out = {k: st[k] for k in ("zeta", "ubar", "vbar", "u", "v", "t", "Huon", "W", "Hz", "Akv", "tke", "rmask_wet", "umask_wet",
@@ -69,7 +76,7 @@ def run_rank(rank, world, ntI, ntJ, config, nsteps, port, outdir, variant=""):
         lev = m.s.nnew - 1
         out["u"], out["v"], out["t"] = st["u"][:, :, :, lev], st["v"][:, :, :, lev], st["t"][:, :, :, lev, :]
     np.savez(os.path.join(outdir, f"tile{rank}.npz"),
-             bounds=np.array([b.Istr, b.Iend, b.Jstr, b.Jend, b.LBi, b.LBj]), **out)
+             bounds=np.array([b.Istr, b.Iend, b.Jstr, b.Jend, b.LBi, b.LBj]), rowm=np.array(rowm), **out)
     dist.barrier()
     dist.destroy_process_group()
 

@@ -710,7 +710,35 @@ GRID2D = ["h", "f", "fomn", "pm", "pn", "om_r", "on_r", "om_u", "on_u", "om_v", 
           "pmon_r", "pnom_r", "pmon_p", "pnom_p", "pmon_u", "pnom_u", "pmon_v", "pnom_v"]
 
 
+def curvilinear_states():
+    """"... curv": every mode on the curvilinear grid of tests/curv_util.py -- util.prepared_state (and with it gls_state,
+    kpp_state, iso_state, basin_state) returns its state with pm, pn, f, every derived metric and the mixing
+    coefficients varying in i and j.  The reference takes the grid from the state's arrays (oracle/ref_wrap.F90), so
+    the builds are the same."""
+    import curv_util
+    import util as _util
+    plain = _util.prepared_state
+
+    def prepared_state(*args, **kw):
+        st = curv_util.curvilinear(plain(*args, **kw))
+        assert st.p.curvgrid == 1 and float(np.ptp(st["pn"][:, 5])) > 0.0 and float(np.ptp(st["visc2_p"][:, 5])) > 0.0
+        return st
+    _util.prepared_state = prepared_state
+    # every mode prints one JSON line: mark it
+    import builtins
+    plain_print = builtins.print
+
+    def marked(*args, **kw):
+        if len(args) == 1 and isinstance(args[0], str) and args[0].startswith("{"):
+            args = (json.dumps(dict(json.loads(args[0]), curvilinear=1)),)
+        plain_print(*args, **kw)
+    builtins.print = marked
+
+
 if __name__ == "__main__":
+    if sys.argv[-1] == "curv":
+        curvilinear_states()
+        sys.argv.pop()
     if sys.argv[-1] == "wet":                  # ... wet: the same comparison on a WET_DRY state against the _WET builds
         import util as _util
         _util.WET = True

@@ -768,3 +768,91 @@ def test_hip_reproduces_reference_uv3dmix2_geo(case):
         finally:
             h.close()
     _geouv_check(case, run, 1e-13)
+
+
+# ------------------------------------------------------------------------------------- the curvilinear grid --
+def _curv_mod():
+    import sys
+    gd = os.path.join(HERE, "golden")
+    if gd not in sys.path:
+        sys.path.insert(0, gd)
+    import make_golden_curv as mc
+    return mc
+
+
+def _curv_check(config, backend, hows):
+    """tests/golden/make_golden_curv.py: every case of the kinds `hows` on `backend(st)`, against what the reference's
+    Fortran left on the same curvilinear state: the same elements changed, to the same bits"""
+    mc = _curv_mod()
+    g = np.load(os.path.join(HERE, "golden", f"ref_curv_{config}.npz"))
+    seen = 0
+    for key, make, how in mc.cases(config):
+        if how[0] not in hows:
+            continue
+        st = make()
+        st0 = st.copy()
+        be = backend(st)
+        try:
+            got = mc.results(st, st0, mc.run(be, st, how)) if how[0] == "mpdata" else None
+            if got is None:
+                mc.run(be, st, how)
+                if hasattr(be, "to_host"):
+                    be.to_host()
+                got = mc.results(st, st0, None)
+        finally:
+            if hasattr(be, "close"):
+                be.close()
+        want = {k[len(key) + 2:]: g[k] for k in g.files if k.startswith(key + "__")}
+        assert want and sorted(got) == sorted(want), (key, sorted(got), sorted(want))
+        for k, v in got.items():
+            assert (str(v) == str(want[k])) if k.endswith("__sha256") else np.array_equal(v, want[k]), (key, k)
+        seen += 1
+    assert seen > 0
+
+
+class _OracleWithMpdata:
+    def __init__(self, st):
+        import oracle
+        self.o = oracle.Oracle(st)
+        self.call, self.bc = self.o.call, self.o.bc
+
+    def mpdata_adiff(self, st, oHz, Ta0, t3):
+        return util.oracle_mpdata_adiff(st, oHz, Ta0, t3)
+
+
+@pytest.mark.parametrize("config", ["UPWELLING", "BENCHMARK_TINY"])
+def test_oracle_reproduces_reference_on_the_curvilinear_grid(config):
+    """set_massflux, set_zeta, prsgrd32 / 31 / 31 + WJ / 40, t3dmix2 and t3dmix4 (s / geo / iso), uv3dmix2_s, uv3dmix4_s,
+    mpdata_adiff, gls_prestep / gls_corstep, wvelocity and the six boundary routines (Chapman, Flather, Shchepetkin,
+    radiation, radiation + nudging) on a channel and a basin whose metrics and mixing coefficients vary in i and j
+    (tests/curv_util.py), against the committed outputs of the reference's Fortran, bit for bit."""
+    _curv_check(config, _OracleWithMpdata, ("call", "gls", "wvelocity", "bc", "mpdata"))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("config", ["UPWELLING", "BENCHMARK_TINY"])
+def test_hip_reproduces_reference_on_the_curvilinear_grid(config):
+    """The entries of the HIP library among those cases (the boundary routines and mpdata_adiff have no entry of their
+    own).  The fixtures hold digests of the large fields, so the comparison goes through the oracle: the oracle's result
+    equals the reference's bit for bit (asserted here again, case by case), and the HIP result lies within the bounds
+    of the other fixtures of it -- 1e-13 of each field's maximum, 1e-10 for the closure (device pow)."""
+    import oracle
+    from roms_trunk_mgh_amd import hip
+    mc = _curv_mod()
+    kinds = ("call", "gls", "wvelocity")
+    _curv_check(config, _OracleWithMpdata, kinds)
+    for key, make, how in mc.cases(config):
+        if how[0] not in kinds:
+            continue
+        st_o = make()
+        st_h = st_o.copy()
+        mc.run(oracle.Oracle(st_o), st_o, how)
+        h = hip.RomsHip(st_h)
+        try:
+            mc.run(h, st_h, how)
+            h.to_host()
+            h.check_guards()
+        finally:
+            h.close()
+        diffs = util.compare_states(st_h, st_o)
+        assert all(v <= (1e-10 if how[0] == "gls" else 1e-13) for v in diffs.values()), (key, diffs)

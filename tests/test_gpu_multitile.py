@@ -51,6 +51,12 @@ def _single(config, nsteps, variant=""):
     if "geouv" in opts:                  # UV_VIS2 with MIX_GEO_UV (uv3dmix2_geo.h)
         kw.setdefault("overrides", {}).update({"uv_vis2": 2, **({"visc2": 50.0} if config == "SEAMOUNT" else {})})
     st = ana.make_tile(config, perturb=1.0, **kw)
+    if opts & {"curv", "curveast", "edge"}:   # tests/curv_util.py: a curvilinear grid (as tests/mp_gpu_worker.py)
+        import curv_util as cv
+        if "edge" in opts:
+            cv.ghost_only_column(st)
+        else:
+            cv.curvilinear(st, columns=cv.east_columns(st.b) if "curveast" in opts else None)
     if "river" in opts:                  # point sources (LuvSrc) in the walls and, with a mask, on the island's coast
         util.river_sources(st, "all" if "wells" in opts else "both" if "mask" in opts else "walls")
     be = hip.RomsHip(st)
@@ -98,7 +104,17 @@ def _single(config, nsteps, variant=""):
                                                     # 512-column tiles of the 8-GPU run (4x1), both tile rows (2x2), the
                                                     # deferred-flux step2d path and, with six MPDATA tracers, three ghost points
                                                     (4, 1, "BENCHMARK3", "physics+slim"), (2, 2, "BENCHMARK3", "physics+slim"),
-                                                    (2, 2, "BENCHMARK3", "mpdata+slim")])
+                                                    (2, 2, "BENCHMARK3", "mpdata+slim"),
+                                                    # a curvilinear grid (tests/curv_util.py): metrics and mixing
+                                                    # coefficients varying in i and j, the general barotropic kernel
+                                                    (2, 1, "UPWELLING", "curv"), (1, 2, "UPWELLING", "curv"),
+                                                    # ... in the eastern tile's columns only: the western tile takes its
+                                                    # metrics from the row table, the eastern one from the arrays
+                                                    (2, 1, "UPWELLING", "curveast"),
+                                                    # pn differs along the one column that is Istr-3 of the eastern
+                                                    # tile: read there with three ghost points, so that tile must not
+                                                    # use the row table either
+                                                    (2, 1, "BENCHMARK_TINY", "dif4+edge")])
 def test_tiled_hip_equals_single_hip(tmp_path, ntI, ntJ, config, variant):
     slim = "slim" in variant
     nsteps = 2 if slim else 3
@@ -119,6 +135,10 @@ def test_tiled_hip_equals_single_hip(tmp_path, ntI, ntJ, config, variant):
     rb = ref.b
     for r in range(world):
         d = np.load(os.path.join(tmp_path, f"tile{r}.npz"))
+        if "curveast" in variant:        # row_metrics_state(): the table on the western tile, the arrays on the eastern
+            assert (int(d["rowm"]) in (1, 3)) == (r == 0) and (int(d["rowm"]) == 2) == (r == 1), (r, int(d["rowm"]))
+        if "edge" in variant or "curv" in variant.split("+"):
+            assert int(d["rowm"]) == 2, (r, int(d["rowm"]))
         Istr, Iend, Jstr, Jend, LBi, LBj = [int(x) for x in d["bounds"]]
         for name in ("zeta", "ubar", "vbar", "u", "v", "t", "Huon", "W", "Hz", "Akv", "tke", "rmask_wet", "umask_wet",
                      "vmask_wet", "pmask_wet", "rmask_wet_avg"):

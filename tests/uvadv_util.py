@@ -245,13 +245,14 @@ def step2d_advection(st, krhs, DUon, DVom, c2):
 
 def zero_pressure_gradient(st, seed=9):
     """The set-up in which a step2d call shows its advection term alone: g = 0 (the pressure gradient is an exact zero),
-    no Coriolis, no viscosity, rufrc = rvfrc = 0, so that rhs_ubar = 0 - (cff1 + cff2) of step2d_LF_AM3.h:1257-1283 for a
+    no Coriolis, no viscosity, rufrc = rvfrc = 0, so that rhs_ubar = 0 - (cff1 + cff2) of step2d_LF_AM3.h:1257-1283 (plus,
+    with CURVGRID, the curvilinear term of :1333-1382) for a
     call that is not the first predictor; random ubar, vbar, zeta, rubar, rvbar at every level.  On an E-W periodic
     grid the ghost columns hold the periodic images, as the exchange leaves them.  Changes st in place (a private copy
     of its parameters)."""
     st.p = type(st.p).from_buffer_copy(st.p)
     st.p.g, st.p.uv_cor, st.p.uv_vis2 = 0.0, 0, 0
-    assert not st.p.curvgrid and not st.p.masking and not st.p.uv_vis4
+    assert not st.p.masking and not st.p.uv_vis4
     rng = np.random.default_rng(seed)
     for name, amp in (("ubar", 0.2), ("vbar", 0.2), ("zeta", 0.3), ("rubar", 50.0), ("rvbar", 50.0), ("rzeta", 1.0)):
         st[name][:] = amp * rng.standard_normal(st[name].shape)
@@ -278,6 +279,14 @@ def step2d_expected(st, s, zeta_knew, c2):
     DVom = st["vbar"][:, :, s.krhs - 1] * ((0.5 * st["om_v"]) * (D + sh(D, 0, -1)))
     adv_u, adv_v = step2d_advection(st, s.krhs, DUon, DVom, c2)
     rhs = {"u": 0.0 - adv_u, "v": 0.0 - adv_v}
+    if p.curvgrid and p.uv_adv:                                                  # curvilinear terms, :1333-1382
+        ub, vb = st["ubar"][:, :, s.krhs - 1], st["vbar"][:, :, s.krhs - 1]
+        cff1 = 0.5 * (vb + sh(vb, 0, 1))
+        cff2 = 0.5 * (ub + sh(ub, 1, 0))
+        cff = D * (cff1 * st["dndx"] - cff2 * st["dmde"])
+        UFx, VFe = cff * cff1, cff * cff2
+        rhs["u"] = rhs["u"] + 0.5 * (UFx + sh(UFx, -1, 0))
+        rhs["v"] = rhs["v"] - 0.5 * (VFe + sh(VFe, 0, -1))
     Dnew = zeta_knew + st["h"]
     Dstp = st["zeta"][:, :, s.kstp - 1] + st["h"]
     ptsk = 3 - s.kstp
