@@ -335,6 +335,36 @@ double *roms_hip_average_device_ptr(int avg_id, int itrc);
  * (:1264), 4 = scale, "close" (:2298-2301), 8 = clamp the WET_DRY counters (set_masks.F:466-468: no nAVG = 1 branch);
  * 0 with nAVG = 0.  The one statement of the schedule: roms_hip_set_avg asks it, the tests compare it with a table. */
 int roms_hip_avg_phase(int iic, int nAVG, int ntsAVG, int ntstart, int nrrec);
+/* Lagrangian floats (FLOATS): step_floats(ng, Lstr, Lend), ROMS/Nonlinear/step_floats.F:80-1053, with interp_floats
+ * (ROMS/Nonlinear/interp_floats.F:56-541), the block at the end of the step (main3d.F:873-906).  Built for SOLVE3D and
+ * FLOATS with or without MASKING; not built: FLOAT_VWALK, FLOAT_STICKY, FLOAT_BIOLOGY / FLOAT_OYSTER, the 2-D branch,
+ * N-S periodic grids.  NFT = 4 time levels 0:NFT, NFV = NT + 10 variables, the indices of mod_floats.F:80-90.
+ * Precondition, as in the reference: a float moves less than one cell per step, so that its owner reads at most two
+ * ghost points.
+ *
+ * roms_hip_set_floats hands DRIFTER(ng) over once: Ftype(Nfloats) (1 = flt_Lagran, 2 = flt_Isobar, 3 = flt_Geopot),
+ * Tinfo(0:izrhs,Nfloats) in Fortran order, Fz0(Nfloats), and the two coordinate arrays iflon / iflat are interpolated
+ * from (lonr, latr if spherical, else xr, yr; extents LBi:UBi,LBj:UBj).  All are copied.  track and bounded are
+ * allocated zero-filled (mod_floats.F:219-246); an earlier set is released first.  Nfloats = 0 releases everything;
+ * roms_hip_set_bounds drops them.  Refused, leaving the library as it was: a call before bounds / params, an Ftype
+ * outside 1..3, N-S periodic bounds.
+ *
+ * roms_hip_floats_put / roms_hip_floats_get copy track(NFV,0:NFT,Nfloats) and bounded(Nfloats) (0 / 1) in the host's
+ * element order (restart; get before wrt_floats), ordered after the kernels issued; n_track = NFV*(NFT+1)*Nfloats and
+ * n_bounded = Nfloats are checked.
+ *
+ * roms_hip_step_floats: nfl = {nfm3, nfm2, nfm1, nf, nfp1} (a permutation of 0..4, refused otherwise), time = time(ng)
+ * before main3d.F:914 advances it; reads s->nnew.  The caller rotates the five indices afterwards (main3d.F:899-903).
+ * Ownership (:185-207), Milne predictor (:238-346), slopes (:353-389), Hamming corrector (:465-579), status
+ * (:585-691), release (:698-748), slopes and outputs at the corrected position (:755-960), reflection (:1009-1021), and
+ * the collection over the tiles (mp_collect, :1030-1049; with E-W periodicity on several tile columns also :604-627)
+ * over the active transport.  On one tile nothing is collected; the ownership switch is applied all the same (rank 0
+ * is the master).  Without floats it returns 0 and does nothing.  Timer name: "step_floats". */
+int roms_hip_set_floats(int Nfloats, const int *Ftype, const double *Tinfo, const double *Fz0,
+                        const double *xcoord, const double *ycoord);
+int roms_hip_floats_put(const double *track, long n_track, const int *bounded, long n_bounded);
+int roms_hip_floats_get(double *track, long n_track, int *bounded, long n_bounded);
+int roms_hip_step_floats(const roms_step_idx_t *s, double time, const int nfl[5]);
 /* wvelocity(ng,tile,nstp)          ROMS/Nonlinear/wvelocity.F:27     (main3d.F:475; writes wvel) */
 int roms_hip_wvelocity(const roms_step_idx_t *s);
 /* diag(ng,tile)                    ROMS/Nonlinear/diag.F:31          (main3d.F:314), the tile-local part

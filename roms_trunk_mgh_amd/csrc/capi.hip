@@ -285,6 +285,7 @@ extern "C" int roms_hip_finalize(void)
   sources_release();
   clima_release();
   avg_release();
+  floats_release();
   if (g_ctx.devc) (void)hipFree(g_ctx.devc);
   g_ctx.devc = nullptr;
   if (g_ctx.stream) (void)hipStreamDestroy(g_ctx.stream);
@@ -621,6 +622,7 @@ extern "C" int roms_hip_set_bounds(const roms_bounds_t *b)
   sources_release();                       // the face maps are in the old bounds' index space
   clima_release();                         // ... and the climatology has the old extents
   avg_release();                           // ... and so have the averages
+  floats_release();                        // ... and the floats' coordinate arrays
   g_ctx.b = *b;
   g_ctx.hostc.b = *b;
   g_ctx.have_bounds = true;

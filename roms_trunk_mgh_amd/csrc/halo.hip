@@ -29,6 +29,7 @@ typedef int (*fn_destroy)(rccl_comm_t);
 typedef int (*fn_send)(const void *, size_t, int, int, rccl_comm_t, hipStream_t);
 typedef int (*fn_recv)(void *, size_t, int, int, rccl_comm_t, hipStream_t);
 typedef int (*fn_group)(void);
+typedef int (*fn_allreduce)(const void *, void *, size_t, int, int, rccl_comm_t, hipStream_t);
 typedef const char *(*fn_errstr)(int);
 static struct {
   bool loaded = false;
@@ -38,9 +39,11 @@ static struct {
   fn_send send = nullptr;
   fn_recv recv = nullptr;
   fn_group gstart = nullptr, gend = nullptr;
+  fn_allreduce allreduce = nullptr;
   fn_errstr errstr = nullptr;
 } rccl;
 static const int RCCL_FLOAT64 = 8;   // ncclFloat64 / ncclDouble
+static const int RCCL_SUM = 0;       // ncclSum
 
 static int rccl_load()
 {
@@ -60,6 +63,7 @@ static int rccl_load()
   rccl.gstart = (fn_group)dlsym(h, "ncclGroupStart");
   rccl.gend = (fn_group)dlsym(h, "ncclGroupEnd");
   rccl.errstr = (fn_errstr)dlsym(h, "ncclGetErrorString");
+  rccl.allreduce = (fn_allreduce)dlsym(h, "ncclAllReduce");
   if (!rccl.getuid || !rccl.initrank || !rccl.send || !rccl.recv || !rccl.gstart || !rccl.gend)
     return roms_fail("rccl_load", "RCCL symbols missing");
   rccl.loaded = true;
@@ -150,6 +154,7 @@ int halo_init()
   return 0;
 }
 
+static void coll_release();
 int halo_finalize()
 {
   for (auto &p : g_buf) { if (p) (void)hipFree(p); p = nullptr; }
@@ -157,6 +162,7 @@ int halo_finalize()
   g_buf_doubles = g_hbuf_doubles = 0;
   g_have_neigh = false;
   g_have_plan = false;
+  coll_release();
   g_relay = nullptr;
   g_relay_user = nullptr;
   if (g_ctx.nccl_comm && rccl.destroy) rccl.destroy((rccl_comm_t)g_ctx.nccl_comm);
@@ -511,6 +517,59 @@ int halo_exchange3d(int gtype, int nk, double *A)
 }
 
 int halo_exchange2d(int gtype, double *A, int) { return halo_exchange3d(gtype, 1, A); }
+
+// mp_collect (ROMS/Utility/distribute.F, a SUM over all tiles) of n doubles of a device array, in place, on whichever
+// transport is active (step_floats.F:604-608, :1030-1049: only the owner of a float contributes, all others hold 0).
+// RCCL: one ncclAllReduce.  Host relay: every rank sends its array to every other rank through the relay callback and
+// adds what it holds and receives in rank order, so that every rank forms the same sum.
+static double *g_coll = nullptr;                  // pinned: world arrays of g_coll_doubles each
+static size_t g_coll_doubles = 0;
+static void coll_release()
+{
+  if (g_coll) (void)hipHostFree(g_coll);
+  g_coll = nullptr;
+  g_coll_doubles = 0;
+}
+int halo_allreduce_sum(double *A, long n)
+{
+  if (n <= 0) return 0;
+  const int world = g_ctx.ntileI * g_ctx.ntileJ, me = g_ctx.rank;
+  if (g_ctx.nccl_comm) {
+    if (!rccl.allreduce) return roms_fail("collect", "RCCL symbol ncclAllReduce missing");
+    RCCL_TRY(rccl.allreduce(A, A, (size_t)n, RCCL_FLOAT64, RCCL_SUM, (rccl_comm_t)g_ctx.nccl_comm, g_ctx.stream));
+    return 0;
+  }
+  if (world == 1) return 0;
+  if (!g_relay)
+    return roms_fail("collect", "multi-tile run without a transport: pass an RCCL unique id to "
+                                "roms_hip_init or set a host relay (roms_hip_set_halo_relay)");
+  if (world > 64) return roms_fail("collect", "host relay: more than 64 tiles");
+  if ((size_t)n > g_coll_doubles) {
+    coll_release();
+    HIP_TRY(hipHostMalloc(&g_coll, sizeof(double) * (size_t)n * world, hipHostMallocDefault));
+    g_coll_doubles = (size_t)n;
+  }
+  double *mine = g_coll + (size_t)me * g_coll_doubles;
+  HIP_TRY(hipMemcpyAsync(mine, A, sizeof(double) * n, hipMemcpyDeviceToHost, g_ctx.stream));
+  HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+  roms_halo_msg_t sm[64], rm[64];
+  int ns = 0;
+  for (int r = 0; r < world; r++) {
+    if (r == me) continue;
+    sm[ns] = roms_halo_msg_t{r, 100 + me, n, mine};
+    rm[ns] = roms_halo_msg_t{r, 100 + r, n, g_coll + (size_t)r * g_coll_doubles};
+    ns++;
+  }
+  if (g_relay(g_relay_user, ns, sm, ns, rm)) return roms_fail("collect", "host relay callback failed");
+  double *acc = g_coll;                           // rank 0's array, then + rank 1, + rank 2 ...
+  for (int r = 1; r < world; r++) {
+    const double *x = g_coll + (size_t)r * g_coll_doubles;
+    for (long e = 0; e < n; e++) acc[e] = acc[e] + x[e];
+  }
+  HIP_TRY(hipMemcpyAsync(A, acc, sizeof(double) * n, hipMemcpyHostToDevice, g_ctx.stream));
+  HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+  return 0;
+}
 
 // Exported for tests: exchange one registered field (all planes, or one
 // trailing level when level > 0 and the field has time levels / tracers).

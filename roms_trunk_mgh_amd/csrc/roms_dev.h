@@ -364,6 +364,8 @@ int halo_exchange2d(int gtype, double *A, int nfields_stride_unused = 0);
 int halo_exchange3d(int gtype, int nk, double *A);
 void halo_batch_begin();                  // record the exchanges that follow ...
 int halo_batch_end();                     // ... and run them as one message per neighbour and phase
+int halo_allreduce_sum(double *A, long n); // mp_collect: SUM over all tiles of a device array, in place (halo.hip)
+void floats_release();                    // k_floats.hip: frees what roms_hip_set_floats allocated
 // lateral boundary conditions on the S/N edges (k_base.hip); s = the barotropic time indices (Chapman, Flather),
 // nstp = the time level the radiation condition compares with
 int bc_zeta(int kout, const roms_step_idx_t *s);

@@ -358,6 +358,35 @@ MODULE roms_hip_mod
       IMPORT :: c_int
       INTEGER(c_int), VALUE :: iic, nAVG, ntsAVG, ntstart, nrrec
     END FUNCTION
+    !  FLOATS: DRIFTER(ng) handed over once after roms_hip_set_params (Ftype, Tinfo(0:izrhs,Nfloats), Fz0 and the two
+    !  coordinate arrays iflon / iflat are interpolated from: lonr, latr or xr, yr); track and bounded to and from the
+    !  device (restart, wrt_floats); step_floats (main3d.F:894) with nfl = (/ nfm3, nfm2, nfm1, nf, nfp1 /) and
+    !  time(ng); the caller rotates the five indices afterwards (main3d.F:899-903).  bounded travels as 0 / 1.
+    INTEGER(c_int) FUNCTION roms_hip_set_floats (Nfloats, Ftype, Tinfo, Fz0, xcoord, ycoord)                        &
+   &                        BIND(C, name='roms_hip_set_floats')
+      IMPORT :: c_int, c_double
+      INTEGER(c_int), VALUE :: Nfloats
+      INTEGER(c_int), INTENT(in) :: Ftype(*)
+      REAL(c_double), INTENT(in) :: Tinfo(*), Fz0(*), xcoord(*), ycoord(*)
+    END FUNCTION
+    INTEGER(c_int) FUNCTION roms_hip_floats_put (track, n_track, bounded, n_bounded) BIND(C, name='roms_hip_floats_put')
+      IMPORT :: c_int, c_long, c_double
+      REAL(c_double), INTENT(in) :: track(*)
+      INTEGER(c_long), VALUE :: n_track, n_bounded
+      INTEGER(c_int), INTENT(in) :: bounded(*)
+    END FUNCTION
+    INTEGER(c_int) FUNCTION roms_hip_floats_get (track, n_track, bounded, n_bounded) BIND(C, name='roms_hip_floats_get')
+      IMPORT :: c_int, c_long, c_double
+      REAL(c_double), INTENT(out) :: track(*)
+      INTEGER(c_long), VALUE :: n_track, n_bounded
+      INTEGER(c_int), INTENT(out) :: bounded(*)
+    END FUNCTION
+    INTEGER(c_int) FUNCTION roms_hip_step_floats (s, time, nfl) BIND(C, name='roms_hip_step_floats')
+      IMPORT :: c_int, c_double, roms_step_idx_t
+      TYPE(roms_step_idx_t), INTENT(in) :: s
+      REAL(c_double), VALUE :: time
+      INTEGER(c_int), INTENT(in) :: nfl(5)
+    END FUNCTION
     !  GLS_MIXING: gls_prestep (main3d.F:567) and gls_corstep (main3d.F:793)
     INTEGER(c_int) FUNCTION roms_hip_gls_prestep (s) BIND(C, name='roms_hip_gls_prestep')
       IMPORT :: c_int, roms_step_idx_t
@@ -387,6 +416,7 @@ MODULE roms_hip_mod
   PUBLIC :: roms_hip_ini_zeta, roms_hip_ini_fields, roms_hip_gls_prestep, roms_hip_gls_corstep, roms_hip_wetdry
   PUBLIC :: roms_hip_set_sources, roms_hip_set_clima
   PUBLIC :: roms_hip_set_averages, roms_hip_set_avg, roms_hip_get_average, roms_hip_average_device_ptr, roms_hip_avg_phase
+  PUBLIC :: roms_hip_set_floats, roms_hip_floats_put, roms_hip_floats_get, roms_hip_step_floats
   PUBLIC :: roms_hip_entry, roms_hip_make_idx, roms_hip_status
 
 CONTAINS

@@ -43,7 +43,8 @@ DECLARED_SYMBOLS = (
      "roms_hip_ana_srflux", "roms_hip_check_guards", "roms_hip_row_metrics_state",
      "roms_hip_graph_exchanges", "roms_hip_graph_exchanges_state", "roms_hip_set_sources",
      "roms_hip_set_clima", "roms_hip_set_averages", "roms_hip_get_average", "roms_hip_average_device_ptr",
-     "roms_hip_avg_phase"] + ["roms_hip_" + e for e in ENTRIES])
+     "roms_hip_avg_phase", "roms_hip_set_floats", "roms_hip_floats_put", "roms_hip_floats_get",
+     "roms_hip_step_floats"] + ["roms_hip_" + e for e in ENTRIES])
 
 
 _DP = C.POINTER(C.c_double)
@@ -92,6 +93,10 @@ def load():
     lib.roms_hip_average_device_ptr.restype = C.c_void_p
     lib.roms_hip_average_device_ptr.argtypes = [C.c_int, C.c_int]
     lib.roms_hip_avg_phase.argtypes = [C.c_int] * 5
+    lib.roms_hip_set_floats.argtypes = [C.c_int, _ip, _DP, _DP, _DP, _DP]
+    lib.roms_hip_floats_put.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_long]
+    lib.roms_hip_floats_get.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_long]
+    lib.roms_hip_step_floats.argtypes = [C.POINTER(abi.StepIdx), C.c_double, _ip]
     lib.roms_hip_set_halo_relay.argtypes = [RELAY_FN, C.c_void_p]
     if hasattr(lib, "roms_hip_tile_neighbors"):
         lib.roms_hip_tile_neighbors.argtypes = [C.c_int] * 7 + [C.POINTER(C.c_int)]
@@ -189,6 +194,32 @@ class RomsHip:
         out = np.zeros(self.averages.shape(name), dtype=np.float64, order="F")
         self._chk(self.l.roms_hip_get_average(avg.AVG_ID[name], int(itrc), out.ctypes.data, out.size), "get_average " + name)
         return out
+
+    def set_floats(self, floats):
+        """DRIFTER(ng) (roms_trunk_mgh_amd/floats.py) -> roms_hip_set_floats; None releases the floats (Nfloats = 0)."""
+        self.floats = floats
+        args = floats.c_args() if floats is not None else (0, None, None, None, None, None)
+        self._chk(self.l.roms_hip_set_floats(*args), "set_floats")
+
+    def floats_put(self, track, bounded):
+        """track(NFV,0:NFT,Nfloats) and bounded(Nfloats) to the device (restart), roms_hip_floats_put"""
+        t = np.asfortranarray(track, dtype=np.float64)
+        bd = np.ascontiguousarray(bounded, dtype=np.int32)
+        self._chk(self.l.roms_hip_floats_put(t.ctypes.data, t.size, bd.ctypes.data, bd.size), "floats_put")
+
+    def floats_get(self):
+        """(track(NFV,0:NFT,Nfloats), bounded(Nfloats)) from the device, roms_hip_floats_get"""
+        if getattr(self, "floats", None) is None:
+            raise RuntimeError("roms_hip floats_get: no floats set (set_floats)")
+        t = np.zeros(self.floats.track_shape(), dtype=np.float64, order="F")
+        bd = np.zeros(self.floats.n, dtype=np.int32)
+        self._chk(self.l.roms_hip_floats_get(t.ctypes.data, t.size, bd.ctypes.data, bd.size), "floats_get")
+        return t, bd.astype(bool)
+
+    def step_floats(self, s, time, nfl):
+        """step_floats (main3d.F:894) with nfl = (nfm3, nfm2, nfm1, nf, nfp1), roms_hip_step_floats"""
+        v = (C.c_int * 5)(*nfl)
+        self._chk(self.l.roms_hip_step_floats(C.byref(s), float(time), v), "step_floats")
 
     def _chk(self, rc, what):
         if rc != 0:

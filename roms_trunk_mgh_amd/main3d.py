@@ -23,6 +23,7 @@ against either backend (`hip.RomsHip` = the product, or the CPU oracle in tests)
     main3d.F:789      omega
     main3d.F:793      gls_corstep                      (GLS_MIXING applications)
     main3d.F:814      step3d_t
+    main3d.F:894-903  step_floats, rotation of nfm3 ... nfp1   (FLOATS: floats=...)
     main3d.F:914      iic += 1
 """
 from . import abi
@@ -43,7 +44,7 @@ def host_clock(tdays):
 
 
 class Main3D:
-    def __init__(self, backend, ntstart=1, physics=False, diagnostics=False, ninfo=1, averages=None):
+    def __init__(self, backend, ntstart=1, physics=False, diagnostics=False, ninfo=1, averages=None, floats=None):
         """physics=True also runs the per-step physics that is on the device:
         bulk_flux and lmd_vmix (BULK_FLUXES / LMD_MIXING applications, i.e. BENCHMARK) and set_vbc, in
         the reference's order;
@@ -54,8 +55,14 @@ class Main3D:
         12-vector of the last call is kept in `last_diag` (layout: roms_hip.h, roms_hip_diag).
         averages: an avg.Averages (AVERAGES applications): handed to the backend here (set_averages), and every step
         issues set_avg directly after set_zeta (main3d.F:493-495); the host fetches a window with
-        backend.get_average on the steps where averages.phase(iic) has avg.CLOSE set."""
+        backend.get_average on the steps where averages.phase(iic) has avg.CLOSE set.
+        floats: a floats.Floats (FLOATS applications): handed to the backend here (set_floats); every step issues
+        step_floats after step3d_t with time = (iic - ntstart) * dt, the clock before main3d.F:914 advances it, and
+        rotates the five float time levels afterwards (main3d.F:894-903)."""
         self.be = backend
+        self.floats = floats
+        if floats is not None:
+            backend.set_floats(floats)
         self.averages = averages
         if averages is not None:
             backend.set_averages(averages)
@@ -128,6 +135,9 @@ class Main3D:
         if gls:                               # main3d.F:790-793
             be.call("gls_corstep", s)
         be.call("step3d_t", s)
+        if self.floats is not None:
+            be.step_floats(s, (self.iic - self.ntstart) * be.st.p.dt, self.floats.nfl())
+            self.floats.rotate()
         self.iic += 1
 
     def run(self, nsteps):
