@@ -154,7 +154,13 @@ int roms_hip_finalize(void);
 /* 128-byte id for roms_hip_init, generated on rank 0 (ncclGetUniqueId). */
 int roms_hip_get_unique_id(void *out128);
 
-/* BOUNDS(ng)%...(tile): get_bounds.F:738 (get_tile), :1009 (var_bounds). */
+/* BOUNDS(ng)%...(tile): get_bounds.F:738 (get_tile), :1009 (var_bounds).
+ * May be called again in a live context (a re-grid; the tiling of roms_hip_init stays).  It forgets everything that
+ * has the old extents: every field registration and device mirror, the library-kept defaults, the source table, the
+ * climatology, the averages, the floats, the row table of the grid metrics, the halo neighbour table and message
+ * plan, and the captured LOOP_2D graphs.  The caller then sets the parameters, registers and uploads every field
+ * and hands sources / climatology / averages / floats over again, as after roms_hip_init; the context then computes
+ * what a fresh one does, bit for bit. */
 int roms_hip_set_bounds(const roms_bounds_t *b);
 int roms_hip_set_params(const roms_params_t *p);
 
@@ -376,7 +382,20 @@ int roms_hip_diag(const roms_step_idx_t *s, double *out12);
 
 /* The whole barotropic loop LOOP_2D of main3d.F:592-700 in one call
  * (predictor/corrector sequencing done inside: 2*nfast+1 launches queued on the library's
- * stream without returning to the host).  indx1 is mod_stepping's indx1(ng), updated on return. */
+ * stream without returning to the host).  indx1 is mod_stepping's indx1(ng), updated on return.
+ * Equal, bit for bit, to the same 2*nfast+1 roms_hip_step2d calls; the two may be mixed from step to step.
+ * On one tile the launches are captured once per (indx1, nstp, nnew, start-up phase) and replayed.  Between steps a
+ * caller may, at the stated cost:
+ *   - hand over new values on the same source faces (roms_hip_set_sources), new climatology arrays under the same
+ *     switches and obcfac (roms_hip_set_clima), upload any field that is not a grid metric, switch averages or
+ *     floats: nothing is recaptured;
+ *   - call roms_hip_set_params, register a field again, change the source faces or their number (0 included), the
+ *     climatology switches or obcfac, roms_hip_graph_exchanges: the graphs are dropped and captured again (one
+ *     eager-cost loop per key, up to four);
+ *   - upload a grid-metric array, h, visc2_r or visc2_p: the row table is examined again at the next barotropic
+ *     call (one small kernel and one synchronisation) and the graphs are captured again;
+ *   - roms_hip_set_bounds: everything, see there.
+ * The results are those of a fresh context started from the same fields (tests/test_gpu_context_reuse.py). */
 int roms_hip_step2d_loop(roms_step_idx_t *s, int *indx1);
 
 /* Several tiles over RCCL: replay LOOP_2D as ONE hipGraph that contains the compute launches, the pack / unpack

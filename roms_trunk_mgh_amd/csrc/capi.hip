@@ -224,6 +224,7 @@ extern "C" const char *roms_hip_last_error(void) { return g_ctx.last_error.c_str
 
 int halo_init();      // halo.hip
 int halo_finalize();
+void halo_bounds_changed();
 extern "C" int roms_hip_finalize(void);
 
 extern "C" int roms_hip_init(int rank, int ntileI, int ntileJ, int device_id, const void *nccl_unique_id)
@@ -270,7 +271,7 @@ extern "C" int roms_hip_finalize(void)
 {
   if (!g_ctx.inited) return 0;
   (void)hipStreamSynchronize(g_ctx.stream);
-  step2d_graphs_release();
+  (void)roms_hip_graph_exchanges(0);       // drops the graphs; the next context starts from the default, as documented
   roms_rowm_release();
   snapshot_release();
   halo_finalize();
@@ -330,6 +331,7 @@ extern "C" int roms_hip_set_sources(int Nsrc, const int *Isrc, const int *Jsrc, 
   const bool luv = (g_ctx.p.point_sources & 1) != 0, lw = (g_ctx.p.point_sources & 2) != 0;
   if (Nsrc == 0) {
     HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+    step2d_graphs_release();               // captured source launches hold the freed table's size
     sources_release();
     g_src.given = true;
     return 0;
@@ -623,6 +625,7 @@ extern "C" int roms_hip_set_bounds(const roms_bounds_t *b)
   clima_release();                         // ... and the climatology has the old extents
   avg_release();                           // ... and so have the averages
   floats_release();                        // ... and the floats' coordinate arrays
+  halo_bounds_changed();                   // ... and the message plan has the old extents and ghost points
   g_ctx.b = *b;
   g_ctx.hostc.b = *b;
   g_ctx.have_bounds = true;

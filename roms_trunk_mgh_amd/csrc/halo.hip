@@ -154,6 +154,14 @@ int halo_init()
   return 0;
 }
 
+// roms_hip_set_bounds: the neighbour table (ghost-point counts) and the message plan (extents) were built from the
+// bounds of the first exchange; the next exchange builds them again.  The buffers grow on demand.
+void halo_bounds_changed()
+{
+  g_have_neigh = false;
+  g_have_plan = false;
+}
+
 static void coll_release();
 int halo_finalize()
 {
