@@ -371,6 +371,42 @@ int roms_hip_set_floats(int Nfloats, const int *Ftype, const double *Tinfo, cons
 int roms_hip_floats_put(const double *track, long n_track, const int *bounded, long n_bounded);
 int roms_hip_floats_get(double *track, long n_track, int *bounded, long n_bounded);
 int roms_hip_step_floats(const roms_step_idx_t *s, double time, const int nfl[5]);
+/* Tidal forcing of the open boundaries (SSH_TIDES, UV_TIDES): set_tides(ng,tile), ROMS/Nonlinear/set_tides.F:28, called
+ * after set_vbc (main3d.F:395-397).  Built with or without MASKING, RAMP_TIDES, ADD_FSOBC, ADD_M2OBC; not built:
+ * AVERAGES_DETIDE, TIDE_GENERATING_FORCES, the CLIMA(ng)%ssh / ubarclm / vbarclm additions of the two ADD options, N-S
+ * periodic grids.
+ *
+ * roms_hip_set_tides hands TIDES(ng) over: NTC constituents of MTC planes, Tperiod[MTC] (s; a constituent with
+ * Tperiod <= 0 is skipped), SSH_Tamp, SSH_Tphase (both, or both NULL: SSH_TIDES), UV_Tangle, UV_Tphase, UV_Tmajor,
+ * UV_Tminor (all four, or all NULL: UV_TIDES), each (LBi:UBi, LBj:UBj, MTC) in the host's layout with the ghost points
+ * filled (one ghost point beside the tile is read; no exchange is made), angles and phases in radians; angler
+ * (LBi:UBi, LBj:UBj; NULL = zero); tide_start (days), ramp_tides (0 / 1: RAMP_TIDES) with dstart (days); add_fsobc with
+ * zeta_base and add_m2obc with ubar_base, vbar_base: the sub-tidal boundary data (LBi:UBi, LBj:UBj, the point
+ * convention of zeta_bry / ubar_bry / vbar_bry).  The library keeps device copies of the bases and writes base + tide
+ * every step -- never += on its own output, which the reference gets from set_data refreshing BOUNDARY(ng) first; a
+ * later call with a NULL base keeps the copy.  Only the two lines of rho-points beside each edge are kept on the
+ * device (edge-major strips, gathered one constituent plane at a time), with the land/sea masks of those lines as the
+ * device holds them at this call: call it again after uploading other masks or changing roms_params_t.masking.
+ * Refused, leaving the library as it was: a call before bounds / params; NTC < 0, NTC > MTC, NTC > 32; one array of the
+ * pair or of the quadruple missing; NTC > 0 with neither group; an ADD option without its group or its base; add_m2obc
+ * while LnudgeM2CLM is on (set_tides.F:476-508 then moves ubarclm / vbarclm as well); masking = 1 before the masks are
+ * registered; N-S periodic bounds.  NTC = 0 with all arrays NULL releases everything; roms_hip_set_bounds drops the
+ * strips.  With SSH_TIDES alone the Flather and Shchepetkin conditions of the normal barotropic velocity take the
+ * reduced-physics boundary value instead of ubar_bry / vbar_bry (u2dbc_im.F:219-255, :291-327, :567-603, :639-675 and the
+ * four blocks of v2dbc_im.F); the captured LOOP_2D graphs are dropped when that switch changes.
+ *
+ * roms_hip_tides: time = time(ng) at the call, before main3d.F:914 advances it.  One launch evaluates the harmonics
+ * and writes zeta_bry (a side's free surface, ubar or vbar acquires boundary data: Cla, Fla, Shc, RadNud; Fla / Shc on
+ * ubar or vbar count for the free surface, inp_decode.F:1621-1655), ubar_bry and vbar_bry (a side's ubar and vbar both
+ * acquire) on the tiles of a physical, non-periodic edge, over the reference's ranges -- but for the four corner
+ * rho-points of zeta_bry, which no condition reads (k_set_tides.hip).  Without tides it returns 0 and does nothing.
+ * Timer name: "set_tides". */
+int roms_hip_set_tides(int NTC, int MTC, const double *Tperiod, const double *SSH_Tamp, const double *SSH_Tphase,
+                       const double *UV_Tangle, const double *UV_Tphase, const double *UV_Tmajor, const double *UV_Tminor,
+                       const double *angler, double tide_start, int ramp_tides, double dstart,
+                       int add_fsobc, const double *zeta_base, int add_m2obc, const double *ubar_base,
+                       const double *vbar_base);
+int roms_hip_tides(double time);
 /* wvelocity(ng,tile,nstp)          ROMS/Nonlinear/wvelocity.F:27     (main3d.F:475; writes wvel) */
 int roms_hip_wvelocity(const roms_step_idx_t *s);
 /* diag(ng,tile)                    ROMS/Nonlinear/diag.F:31          (main3d.F:314), the tile-local part

@@ -613,3 +613,46 @@ def analytic_clima(st, sides=("south", "north"), width=6.0, tnudg=None, m2=True,
         kw.update(LnudgeTCLM=flags, Tnudgcof=tn, tclm=tc)
     st.clima = Clima(b, **kw)
     return st.clima
+
+
+# (period in s, elevation amplitude in m, semi-major axis in m/s) of M2, S2, N2, K2, K1, O1, P1, Q1
+TIDAL_CONSTITUENTS = ((44714.16, 0.50, 0.20), (43200.0, 0.20, 0.08), (45570.05, 0.10, 0.04), (43082.05, 0.05, 0.02),
+                      (86164.09, 0.15, 0.05), (92949.63, 0.10, 0.04), (86637.20, 0.05, 0.02), (96726.08, 0.02, 0.01))
+
+
+def analytic_tides(st, ntc=1, mtc=None, ssh=True, uv=True, angler=None, periods=None, amp=None, **kw):
+    """An analytic constituent set for the tile (roms_trunk_mgh_amd/tides.py), the stand-in for an application's tidal
+    forcing file: per constituent a uniform elevation amplitude with a phase that varies along the edges (a wave
+    travelling around the basin), and a current ellipse with a non-zero minor axis (a fifth of the major one, turning
+    clockwise for every other constituent) and an inclination that varies over the grid.  Everything is a function of
+    the GLOBAL indices (of the periodic image in a periodic direction), so that any tile of any tiling fills its own
+    arrays, ghost points included, with the values its neighbours hold.  periods / amp: override the periods (s) and
+    the elevation amplitudes (m) of TIDAL_CONSTITUENTS; angler: the grid's angle (radians; default none = zero); the
+    other keywords go to tides.Tides (tide_start, ramp, dstart, add_fsobc, zeta_base ...)."""
+    from .tides import Tides
+    b = st.b
+    mtc = mtc or ntc
+    ii = np.arange(b.LBi, b.UBi + 1, dtype=np.float64)[:, None]
+    jj = np.arange(b.LBj, b.UBj + 1, dtype=np.float64)[None, :]
+    iw = np.mod(ii - 1.0, b.Lm) + 1.0 if b.EWperiodic else ii
+    x, y = (iw - 0.5) / b.Lm, (jj - 0.5) / b.Mm
+    T = np.zeros(mtc)
+    arr = {n: np.zeros((st.ni, st.nj, mtc), order="F") for n in
+           ("SSH_Tamp", "SSH_Tphase", "UV_Tangle", "UV_Tphase", "UV_Tmajor", "UV_Tminor")}
+    for it in range(mtc):
+        per, a0, u0 = TIDAL_CONSTITUENTS[it % len(TIDAL_CONSTITUENTS)]
+        T[it] = periods[it] if periods is not None else per
+        arr["SSH_Tamp"][:, :, it] = amp[it] if amp is not None else a0
+        arr["SSH_Tphase"][:, :, it] = 2.0 * math.pi * ((1 + it % 2) * x + 0.5 * y) + 0.3 * it
+        arr["UV_Tmajor"][:, :, it] = u0 * (1.0 + 0.2 * np.cos(2.0 * math.pi * x + it) * np.sin(math.pi * y))
+        arr["UV_Tminor"][:, :, it] = (0.2 if it % 2 == 0 else -0.2) * arr["UV_Tmajor"][:, :, it]
+        arr["UV_Tangle"][:, :, it] = 0.4 + 0.3 * it + 0.5 * np.sin(2.0 * math.pi * x) * np.cos(math.pi * y)
+        arr["UV_Tphase"][:, :, it] = arr["SSH_Tphase"][:, :, it] + 0.7 + 0.1 * np.cos(2.0 * math.pi * (x + y))
+    args = {}
+    if ssh:
+        args.update(SSH_Tamp=arr["SSH_Tamp"], SSH_Tphase=arr["SSH_Tphase"])
+    if uv:
+        args.update({n: arr[n] for n in ("UV_Tangle", "UV_Tphase", "UV_Tmajor", "UV_Tminor")})
+        if angler is not None:
+            args["angler"] = angler
+    return Tides(b, T, NTC=ntc, **args, **kw)

@@ -287,6 +287,7 @@ extern "C" int roms_hip_finalize(void)
   clima_release();
   avg_release();
   floats_release();
+  tides_release();
   if (g_ctx.devc) (void)hipFree(g_ctx.devc);
   g_ctx.devc = nullptr;
   if (g_ctx.stream) (void)hipStreamDestroy(g_ctx.stream);
@@ -625,6 +626,7 @@ extern "C" int roms_hip_set_bounds(const roms_bounds_t *b)
   clima_release();                         // ... and the climatology has the old extents
   avg_release();                           // ... and so have the averages
   floats_release();                        // ... and the floats' coordinate arrays
+  tides_release();                         // ... and the tidal strips
   halo_bounds_changed();                   // ... and the message plan has the old extents and ghost points
   g_ctx.b = *b;
   g_ctx.hostc.b = *b;

@@ -80,6 +80,7 @@ struct BcArgs {
   // a RadNud edge takes its time scale from (M2nudgcof, M3nudgcof, Tnudgcof of the tracer's ic), and obcfac; or nullptr
   const double *C;
   double obcfac;
+  int ssh_only;          // SSH_TIDES without UV_TIDES (RomsTides.ssh_only): bry_val of Flather / Shchepetkin, bc_bry_val
 };
 
 __device__ __forceinline__ double bc_radiate(double xb_old, double x1_old, double x1, double x2, double gL, double gR,
@@ -98,6 +99,48 @@ __device__ __forceinline__ double bc_radiate(double xb_old, double x1_old, doubl
     return (cff * xb_old + Cn * x1 - fmax(Ct, 0.0) * gLb - fmin(Ct, 0.0) * gRb) / (cff + Cn);
   }
   return (cff * xb_old + Cn * x1) / (cff + Cn);
+}
+
+// The reduced-physics balance of the normal barotropic component at boundary point B: bry_pgr + bry_cor + bry_str
+// (pressure gradient -- from the boundary data of the free surface where they are acquired -- Coriolis, surface minus
+// bottom stress).  Stated once for the Red condition (u2dbc_im.F:395-420, :743-768; v2dbc_im.F:397-424, :746-773) and
+// for the SSH_TIDES-without-UV_TIDES boundary value of Flather / Shchepetkin (u2dbc_im.F:220-245, :292-317, :568-593,
+// :640-665; v2dbc_im.F:222-247, :294-319, :571-596, :643-668): the eight tidal blocks repeat the Red ones term by term.
+__device__ __forceinline__ double bc_reduced_rhs(const RomsDev *__restrict__ c, const BcArgs &a, int side, bool we, bool hi,
+                                                 long B, long st)
+{
+  const roms_params_t &p = c->p;
+  const long ni = c->b.UBi - c->b.LBi + 1;
+  const double *pmn = we ? c->F.pm : c->F.pn;
+  const long un = we ? 1 : ni, lo = B - un, qi = hi ? lo : B, qo = hi ? B : lo;
+  double bry_pgr, bry_cor = 0.0;
+  if (a.acquire[side]) bry_pgr = hi ? -p.g * (a.Zb[qo] - a.Z[qi]) * 0.5 * pmn[qi] : -p.g * (a.Z[qi] - a.Zb[qo]) * 0.5 * pmn[qi];
+  else bry_pgr = -p.g * (a.Z[B] - a.Z[lo]) * 0.5 * (pmn[lo] + pmn[B]);
+  if (p.uv_cor) {
+    bry_cor = 0.125 * (a.T[lo] + a.T[lo + st] + a.T[B] + a.T[B + st]) * (c->F.f[lo] + c->F.f[B]);
+    if (!we) bry_cor = -bry_cor;
+  }
+  const double cff = 1.0 / (0.5 * (c->F.h[lo] + a.Z[lo] + c->F.h[B] + a.Z[B]));
+  const double bry_str = cff * ((we ? c->F.sustr : c->F.svstr)[B] - (we ? c->F.bustr : c->F.bvstr)[B]);
+  return bry_pgr + bry_cor + bry_str;
+}
+
+// bry_val of the normal component on a Flather / Shchepetkin edge: the boundary data, or -- elevations set by the tides
+// and currents not (SSH_TIDES without UV_TIDES, BcArgs.ssh_only) -- the first inside point at know plus the reduced
+// balance over cff2 = om_u Cx (on_v Ce), Cx = 1 / sqrt(g 1/2 (h + zeta + h + zeta)) with the outside point first on the
+// eastern / northern edge, as written (u2dbc_im.F:246-255, :594-603; v2dbc_im.F:248-257, :597-606).
+__device__ __forceinline__ double bc_bry_val(const RomsDev *__restrict__ c, const BcArgs &a, int side, bool we, bool hi,
+                                             long B, long P1, long st)
+{
+  if (!a.ssh_only) return a.D[B];
+  const roms_params_t &p = c->p;
+  const long ni = c->b.UBi - c->b.LBi + 1;
+  const long lo = B - (we ? 1 : ni);
+  const double rhs = bc_reduced_rhs(c, a, side, we, hi, B, st);
+  const double Cx = hi ? 1.0 / sqrt(p.g * 0.5 * (c->F.h[B] + a.Z[B] + c->F.h[lo] + a.Z[lo]))
+                       : 1.0 / sqrt(p.g * 0.5 * (c->F.h[lo] + a.Z[lo] + c->F.h[B] + a.Z[B]));
+  const double cff2 = (we ? c->F.om_u : c->F.on_v)[B] * Cx;
+  return a.Xold[P1] + cff2 * rhs;
 }
 
 // grid: x = position along the edge, y = level, z = edge (0 W, 1 E, 2 S, 3 N)
@@ -185,11 +228,11 @@ __global__ void k_edge_bc(const RomsDev *__restrict__ c, BcArgs a)
     const double cff1 = sqrt(p.g * (c->F.h[P1] + a.Xold[P1]));
     const double Cn = cff * cff1;
     x = (1.0 - Cn) * a.Xold[B] + Cn * a.Xold[P1];
-  } else if (code == LBC_SHCHEPETKIN && normal) {   // u2dbc_im.F:288-362, :636-710; v2dbc_im.F:290-364, :639-713 (no SSH_TIDES)
+  } else if (code == LBC_SHCHEPETKIN && normal) {   // u2dbc_im.F:288-362, :636-710; v2dbc_im.F:290-364, :639-713 (bry_val: bc_bry_val)
     const double *pmn = we ? c->F.pm : c->F.pn;
     const long lo = B - (we ? 1 : ni), qi = hi ? lo : B, qo = hi ? B : lo;     // rho-points inside / outside
     const double Co = 1.0 / (2.0 + sqrt(2.0));      // mod_scalars.F:4175
-    const double bry_val = a.D[B];
+    const double bry_val = bc_bry_val(c, a, side, we, hi, B, P1, st);
     // WET_DRY: the total depth instead of the resting one (u2dbc_im.F:331-340, :679-688; v2dbc_im.F:333, :682)
     const double cff = p.wet_dry ? 0.5 * (c->F.h[lo] + a.Z[lo] + c->F.h[B] + a.Z[B]) : 0.5 * (c->F.h[lo] + c->F.h[B]);
     const double cff1 = sqrt(p.g / cff);
@@ -203,21 +246,10 @@ __global__ void k_edge_bc(const RomsDev *__restrict__ c, BcArgs a)
     x = hi ? 0.5 * ((1.0 - Cn) * a.Xold[B] + Cn * a.Xold[P1] + bry_val + cff1 * (Zx - a.Zb[qo]))
            : 0.5 * ((1.0 - Cn) * a.Xold[B] + Cn * a.Xold[P1] + bry_val - cff1 * (Zx - a.Zb[qo]));
   } else if (code == LBC_REDUCED && normal) {       // u2dbc_im.F:392-432, :740-780; v2dbc_im.F:394-436, :743-785
-    const double *pmn = we ? c->F.pm : c->F.pn;
-    const long un = we ? 1 : ni, lo = B - un, qi = hi ? lo : B, qo = hi ? B : lo;
-    double bry_pgr, bry_cor = 0.0;
-    if (a.acquire[side]) bry_pgr = hi ? -p.g * (a.Zb[qo] - a.Z[qi]) * 0.5 * pmn[qi] : -p.g * (a.Z[qi] - a.Zb[qo]) * 0.5 * pmn[qi];
-    else bry_pgr = -p.g * (a.Z[B] - a.Z[lo]) * 0.5 * (pmn[lo] + pmn[B]);
-    if (p.uv_cor) {
-      bry_cor = 0.125 * (a.T[lo] + a.T[lo + st] + a.T[B] + a.T[B + st]) * (c->F.f[lo] + c->F.f[B]);
-      if (!we) bry_cor = -bry_cor;
-    }
-    const double cff = 1.0 / (0.5 * (c->F.h[lo] + a.Z[lo] + c->F.h[B] + a.Z[B]));
-    const double bry_str = cff * ((we ? c->F.sustr : c->F.svstr)[B] - (we ? c->F.bustr : c->F.bvstr)[B]);
-    x = a.Xold[B] + a.dt2d * (bry_pgr + bry_cor + bry_str);
-  } else if (code == LBC_FLATHER && normal) {       // u2dbc_im.F:214-300, v2dbc_im.F:216-286 (bry_val = boundary data)
+    x = a.Xold[B] + a.dt2d * bc_reduced_rhs(c, a, side, we, hi, B, st);
+  } else if (code == LBC_FLATHER && normal) {       // u2dbc_im.F:214-300, v2dbc_im.F:216-286 (bry_val: bc_bry_val)
     const long qa = B - (we ? 1 : ni), qc = B;      // the two rho-points around the velocity point, lower index first
-    const double bry_val = a.D[B];
+    const double bry_val = bc_bry_val(c, a, side, we, hi, B, P1, st);
     const double cff = 1.0 / (0.5 * (c->F.h[qa] + a.Z[qa] + c->F.h[qc] + a.Z[qc]));
     const double Cn = sqrt(p.g * cff);
     const double zb = a.Zb[hi ? qc : qa];
@@ -428,6 +460,7 @@ int bc_u2d(int kout, const roms_step_idx_t *s)
   a.Zb = g_ctx.dev[FID_zeta_bry];
   a.Zn = g_ctx.dev[FID_zeta] + (long)(kout - 1) * nij_host();
   a.T = g_ctx.dev[FID_vbar] + (long)(know - 1) * nij_host();
+  a.ssh_only = g_ctx.hostc.tides.ssh_only;
   bc_acquire(a);
   a.dt2d = dt2d;
   return edge_bc(a);
@@ -444,6 +477,7 @@ int bc_v2d(int kout, const roms_step_idx_t *s)
   a.Z = g_ctx.dev[FID_zeta] + (long)(know - 1) * nij_host();
   a.Zb = g_ctx.dev[FID_zeta_bry];
   a.T = g_ctx.dev[FID_ubar] + (long)(know - 1) * nij_host();
+  a.ssh_only = g_ctx.hostc.tides.ssh_only;
   bc_acquire(a);
   a.dt2d = dt2d;
   return edge_bc(a);

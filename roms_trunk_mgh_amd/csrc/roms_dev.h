@@ -49,6 +49,31 @@ struct RomsClima {
   const double *Tnudgcof, *tclm;                 // [nij * N * nt]
 };
 
+// Tidal boundary forcing (set_tides.F, SSH_TIDES / UV_TIDES; roms_hip_set_tides, k_set_tides.hip).  The harmonic
+// constants live on the device as STRIPS: per edge e (W, E, S, N) the two lines of rho-points the edge loads read --
+// line 0 outside the edge (Istr-1, Iend+1, Jstr-1, Jend+1), line 1 the first one inside (Istr, Iend, Jstr, Jend) -- each
+// over the whole allocated extent along the edge (LBj:UBj or LBi:UBi), so that consecutive threads read consecutive
+// doubles on every edge.  Element (e, line, a) of a strip plane sits at off[e] + line * len[e] + (a - lb[e]); a
+// constituent plane has `tot` doubles.  umask / vmask: one line per edge (the u- / v-points the edge vectors sit at),
+// element (e, a) at off[e] / 2 + (a - lb[e]).
+#define ROMS_MAXTC 32  // most tidal constituents (NTC) the constant block holds periods for
+struct RomsTides {
+  int ntc;                    // NTC; 0 = no tides
+  int ssh, uv;                // SSH_TIDES, UV_TIDES
+  int ssh_only;               // ssh && !uv: Flather / Shchepetkin take the reduced-physics bry_val (k_edge_bc)
+  int ramp, add_fs, add_m2;   // RAMP_TIDES, ADD_FSOBC, ADD_M2OBC
+  int lb[4], len[4];
+  long off[4], tot;
+  double tide_start, dstart;  // days
+  double Tperiod[ROMS_MAXTC];
+  const double *amp, *eph;                    // [ntc * tot] SSH_Tamp, SSH_Tphase
+  const double *ang, *uph, *maj, *mnr;        // [ntc * tot] UV_Tangle, UV_Tphase, UV_Tmajor, UV_Tminor
+  const double *angler;                       // [tot]
+  const double *rmask;                        // [tot]; nullptr without MASKING
+  const double *umask, *vmask;                // [tot / 2]
+  const double *zeta_base, *ubar_base, *vbar_base;   // [nij] sub-tidal boundary data of the ADD options
+};
+
 // AVERAGES (roms_hip_set_averages, roms_hip_set_avg): the columns of include/roms_avg.def and the library-owned arrays.
 enum { AVS_2D = 0, AVS_N, AVS_W, AVS_NT };
 enum { RNG_RR = 0, RNG_UR, RNG_VR, RNG_II, RNG_UI, RNG_VI };
@@ -86,6 +111,7 @@ struct RomsDev {
   const double *rowm;   // row table of the i-uniform metric arrays (k_step2d_mom.hip), or nullptr
   RomsSrc src;          // point sources (LuvSrc), n = 0 without
   RomsClima clima;      // climatology nudging, all flags zero without
+  RomsTides tides;      // tidal boundary forcing, ntc = 0 without
 };
 
 struct RomsCtx {
@@ -366,6 +392,7 @@ void halo_batch_begin();                  // record the exchanges that follow ..
 int halo_batch_end();                     // ... and run them as one message per neighbour and phase
 int halo_allreduce_sum(double *A, long n); // mp_collect: SUM over all tiles of a device array, in place (halo.hip)
 void floats_release();                    // k_floats.hip: frees what roms_hip_set_floats allocated
+void tides_release();                     // k_set_tides.hip: frees what roms_hip_set_tides allocated
 // lateral boundary conditions on the S/N edges (k_base.hip); s = the barotropic time indices (Chapman, Flather),
 // nstp = the time level the radiation condition compares with
 int bc_zeta(int kout, const roms_step_idx_t *s);

@@ -387,6 +387,23 @@ MODULE roms_hip_mod
       REAL(c_double), VALUE :: time
       INTEGER(c_int), INTENT(in) :: nfl(5)
     END FUNCTION
+    !  SSH_TIDES / UV_TIDES: TIDES(ng) handed over once after roms_hip_set_params and the registration of the masks
+    !  (C_LOC of the arrays of mod_tides.F; C_NULL_PTR for the group the application does not define, for angler = 0 and
+    !  for a sub-tidal base that keeps its copy); MERGE(1, 0, ...) for RAMP_TIDES, ADD_FSOBC, ADD_M2OBC.  set_tides
+    !  (main3d.F:396) with time(ng).
+    INTEGER(c_int) FUNCTION roms_hip_set_tides (NTC, MTC, Tperiod, SSH_Tamp, SSH_Tphase, UV_Tangle, UV_Tphase,       &
+   &                        UV_Tmajor, UV_Tminor, angler, tide_start, ramp_tides, dstart, add_fsobc, zeta_base,      &
+   &                        add_m2obc, ubar_base, vbar_base) BIND(C, name='roms_hip_set_tides')
+      IMPORT :: c_int, c_double, c_ptr
+      INTEGER(c_int), VALUE :: NTC, MTC, ramp_tides, add_fsobc, add_m2obc
+      TYPE(c_ptr), VALUE :: Tperiod, SSH_Tamp, SSH_Tphase, UV_Tangle, UV_Tphase, UV_Tmajor, UV_Tminor, angler
+      TYPE(c_ptr), VALUE :: zeta_base, ubar_base, vbar_base
+      REAL(c_double), VALUE :: tide_start, dstart
+    END FUNCTION
+    INTEGER(c_int) FUNCTION roms_hip_tides (time) BIND(C, name='roms_hip_tides')
+      IMPORT :: c_int, c_double
+      REAL(c_double), VALUE :: time
+    END FUNCTION
     !  GLS_MIXING: gls_prestep (main3d.F:567) and gls_corstep (main3d.F:793)
     INTEGER(c_int) FUNCTION roms_hip_gls_prestep (s) BIND(C, name='roms_hip_gls_prestep')
       IMPORT :: c_int, roms_step_idx_t
@@ -417,6 +434,7 @@ MODULE roms_hip_mod
   PUBLIC :: roms_hip_set_sources, roms_hip_set_clima
   PUBLIC :: roms_hip_set_averages, roms_hip_set_avg, roms_hip_get_average, roms_hip_average_device_ptr, roms_hip_avg_phase
   PUBLIC :: roms_hip_set_floats, roms_hip_floats_put, roms_hip_floats_get, roms_hip_step_floats
+  PUBLIC :: roms_hip_set_tides, roms_hip_tides
   PUBLIC :: roms_hip_entry, roms_hip_make_idx, roms_hip_status
 
 CONTAINS

@@ -44,7 +44,7 @@ DECLARED_SYMBOLS = (
      "roms_hip_graph_exchanges", "roms_hip_graph_exchanges_state", "roms_hip_set_sources",
      "roms_hip_set_clima", "roms_hip_set_averages", "roms_hip_get_average", "roms_hip_average_device_ptr",
      "roms_hip_avg_phase", "roms_hip_set_floats", "roms_hip_floats_put", "roms_hip_floats_get",
-     "roms_hip_step_floats"] + ["roms_hip_" + e for e in ENTRIES])
+     "roms_hip_step_floats", "roms_hip_set_tides", "roms_hip_tides"] + ["roms_hip_" + e for e in ENTRIES])
 
 
 _DP = C.POINTER(C.c_double)
@@ -97,6 +97,9 @@ def load():
     lib.roms_hip_floats_put.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_long]
     lib.roms_hip_floats_get.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_long]
     lib.roms_hip_step_floats.argtypes = [C.POINTER(abi.StepIdx), C.c_double, _ip]
+    lib.roms_hip_set_tides.argtypes = ([C.c_int, C.c_int] + [_DP] * 8 + [C.c_double, C.c_int, C.c_double, C.c_int, _DP,
+                                        C.c_int, _DP, _DP])
+    lib.roms_hip_tides.argtypes = [C.c_double]
     lib.roms_hip_set_halo_relay.argtypes = [RELAY_FN, C.c_void_p]
     if hasattr(lib, "roms_hip_tile_neighbors"):
         lib.roms_hip_tile_neighbors.argtypes = [C.c_int] * 7 + [C.POINTER(C.c_int)]
@@ -162,6 +165,8 @@ class RomsHip:
                 self.set_sources(state.sources)
             if getattr(state, "clima", None) is not None:
                 self.set_clima(state.clima)
+            if getattr(state, "tides", None) is not None:
+                self.set_tides(state.tides)
         except Exception:
             # a refused set-up (more levels than ROMS_MAXN, say) leaves no half-made context behind: the next
             # RomsHip() would otherwise fail while closing it (check_guards without bounds)
@@ -220,6 +225,17 @@ class RomsHip:
         """step_floats (main3d.F:894) with nfl = (nfm3, nfm2, nfm1, nf, nfp1), roms_hip_step_floats"""
         v = (C.c_int * 5)(*nfl)
         self._chk(self.l.roms_hip_step_floats(C.byref(s), float(time), v), "step_floats")
+
+    def set_tides(self, tides, only=None):
+        """TIDES(ng) (roms_trunk_mgh_amd/tides.py) -> roms_hip_set_tides; None releases the tides (NTC = 0); only = names
+        of the sub-tidal base arrays to hand over again (the others keep their device copy)."""
+        from . import tides as _tides
+        args = tides.c_args(only) if tides is not None else _tides.NO_TIDES
+        self._chk(self.l.roms_hip_set_tides(*args), "set_tides")
+
+    def tides(self, time):
+        """set_tides (main3d.F:396) at time = time(ng): writes zeta_bry, ubar_bry, vbar_bry on the device, roms_hip_tides"""
+        self._chk(self.l.roms_hip_tides(float(time)), "tides")
 
     def _chk(self, rc, what):
         if rc != 0:

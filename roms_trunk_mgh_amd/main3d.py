@@ -12,6 +12,7 @@ against either backend (`hip.RomsHip` = the product, or the CPU oracle in tests)
     main3d.F:307-314  set_massflux, rho_eos, diag      (diag: diagnostics=True, every ninfo steps)
     main3d.F:280      set_data -> ana_srflux           (physics=True, BENCHMARK: shortwave flux of the hour)
     main3d.F:388-394  bulk_flux, set_vbc               (physics=True; else fixed forcing inputs)
+    main3d.F:395-397  set_tides                        (SSH_TIDES / UV_TIDES: tides=...)
     main3d.F:467-475  lmd_vmix (physics=True; else fixed mixing inputs); omega; wvelocity (diagnostics=True)
     main3d.F:489      set_zeta
     main3d.F:494      set_avg                          (AVERAGES: averages=...)
@@ -44,7 +45,7 @@ def host_clock(tdays):
 
 
 class Main3D:
-    def __init__(self, backend, ntstart=1, physics=False, diagnostics=False, ninfo=1, averages=None, floats=None):
+    def __init__(self, backend, ntstart=1, physics=False, diagnostics=False, ninfo=1, averages=None, floats=None, tides=None):
         """physics=True also runs the per-step physics that is on the device:
         bulk_flux and lmd_vmix (BULK_FLUXES / LMD_MIXING applications, i.e. BENCHMARK) and set_vbc, in
         the reference's order;
@@ -58,8 +59,14 @@ class Main3D:
         backend.get_average on the steps where averages.phase(iic) has avg.CLOSE set.
         floats: a floats.Floats (FLOATS applications): handed to the backend here (set_floats); every step issues
         step_floats after step3d_t with time = (iic - ntstart) * dt, the clock before main3d.F:914 advances it, and
-        rotates the five float time levels afterwards (main3d.F:894-903)."""
+        rotates the five float time levels afterwards (main3d.F:894-903).
+        tides: a tides.Tides (SSH_TIDES / UV_TIDES applications): handed to the backend here (set_tides); every step
+        issues tides((iic - ntstart) * dt) at the place of set_tides, directly after set_vbc (main3d.F:395-397) -- with
+        physics=False at the same place in the sequence."""
         self.be = backend
+        self.tides = tides
+        if tides is not None:
+            backend.set_tides(tides)
         self.floats = floats
         if floats is not None:
             backend.set_floats(floats)
@@ -108,16 +115,18 @@ class Main3D:
         be.call("rho_eos", s)
         if self.diagnostics and (self.iic - 1) % self.ninfo == 0:
             self.last_diag = be.diag(s)
+        bench_app = getattr(be.st, "cfg", {}).get("app") == "BENCHMARK"
         if self.physics:
-            bench_app = getattr(be.st, "cfg", {}).get("app") == "BENCHMARK"
             if bench_app:                     # set_data: ANA_SRFLUX with ALBEDO is the time-dependent forcing
                 dt = be.st.p.dt
                 be.ana_srflux(*host_clock((self.iic - self.ntstart) * dt / 86400.0))
             if bench_app:                     # BULK_FLUXES
                 be.call("bulk_flux", s)
             be.call("set_vbc", s)
-            if bench_app:                     # LMD_MIXING
-                be.call("lmd_vmix", s)
+        if self.tides is not None:            # main3d.F:395-397, before the mixing closure (main3d.F:467)
+            be.tides((self.iic - self.ntstart) * be.st.p.dt)
+        if self.physics and bench_app:        # LMD_MIXING
+            be.call("lmd_vmix", s)
         be.call("omega", s)
         if self.diagnostics:
             be.call("wvelocity", s)

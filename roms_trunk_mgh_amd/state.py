@@ -19,6 +19,7 @@ class TileState:
         self.ni = bounds.UBi - bounds.LBi + 1
         self.nj = bounds.UBj - bounds.LBj + 1
         self.clima = None        # a clima.Clima: climatology nudging (the HIP path only)
+        self.tides = None        # a tides.Tides: tidal boundary forcing (the HIP path only)
         self.arr = {}
         for name, kind, _ in abi.FIELDS:
             trail = abi.trailing_shape(kind, bounds.N, bounds.NT, bounds.NAT)
@@ -54,7 +55,7 @@ class TileState:
         other = TileState.__new__(TileState)
         other.b, other.p, other.ni, other.nj = self.b, self.p, self.ni, self.nj
         other.arr = {k: v.copy(order="F") for k, v in self.arr.items()}
-        for extra in ("cfg", "lonr", "latr", "z_r0", "z_w0", "sources", "clima"):
+        for extra in ("cfg", "lonr", "latr", "z_r0", "z_w0", "sources", "clima", "tides"):
             if hasattr(self, extra):
                 setattr(other, extra, getattr(self, extra))
         return other
