@@ -341,6 +341,52 @@ double *roms_hip_average_device_ptr(int avg_id, int itrc);
  * (:1264), 4 = scale, "close" (:2298-2301), 8 = clamp the WET_DRY counters (set_masks.F:466-468: no nAVG = 1 branch);
  * 0 with nAVG = 0.  The one statement of the schedule: roms_hip_set_avg asks it, the tests compare it with a table. */
 int roms_hip_avg_phase(int iic, int nAVG, int ntsAVG, int ntstart, int nrrec);
+/* Tracer budget diagnostics (DIAGNOSTICS_TS): set_diags(ng,tile), ROMS/Utility/set_diags.F:28, called after set_zeta
+ * and before set_avg (main3d.F:490-492), and the DiaTwrk statements of pre_step3d.F:894-904, t3dmix2_s.h:293-296 and
+ * step3d_t.F:868-871, :1199-1205, :1417-1427, :1475-1500, :1598-1611, which roms_hip_pre_step3d, roms_hip_t3dmix2 and
+ * roms_hip_step3d_t carry out while the diagnostics are on.  The terms are those of roms_dia.def; the library owns
+ * DiaTwrk and DiaTrc (LBi:UBi, LBj:UBj, N, NT, NDT), avgzeta (LBi:UBi, LBj:UBj) and with wet_dry rmask_dia.  The momentum
+ * half, DIAGNOSTICS_UV, is not built and has no switch here.
+ *
+ * roms_hip_set_diagnostics hands over the window nDIA, its first step ntsDIA, ntstart and nrrec (mod_scalars.F) and
+ * allocates the arrays zero-filled (mod_diags.F), NDT = 6 without ts_dif2 and 9 with it; an earlier set is released
+ * first.  nDIA = 0 releases everything and the step runs the kernels it runs without diagnostics; roms_hip_set_bounds
+ * drops the arrays.  Refused by name, leaving the library as it was: a call before bounds / params, nDIA < 0, MPDATA or
+ * HSIMT tracers, ts_dif4, rotated mixing (ts_dif2 with mix_geo_ts or mix_iso_ts: iTsdif), point sources.  The entries
+ * above refuse the same when the parameters change afterwards (a change of ts_dif2 asks for a new call).
+ *
+ * roms_hip_set_diags reads s->iic and s->kstp: one launch initialises or accumulates DiaTrc, avgzeta (from
+ * zeta(:,:,kstp)) and the counter over IstrR:IendR, JstrR:JendR (set_diags.F:121-124, :244; the schedule is the
+ * initialise / accumulate part of roms_hip_avg_phase with nDIA, ntsDIA), with wet_dry weighted by rmask_full.  The
+ * scaling by the window length at output time (:374-1010, with wrt_diags) stays with the host.  With nDIA = 0 it
+ * returns 0 and does nothing.  Timer name: "set_diags".
+ *
+ * roms_hip_get_diagnostic copies the plane (LBi:UBi, LBj:UBj, N) of term dia_id and tracer itrc (1-based) to host
+ * memory, DiaTwrk with accumulated = 0 and DiaTrc with accumulated = 1; DIA_avgzeta and DIA_rmask_dia return those 2-D
+ * arrays (itrc, accumulated not looked at).  A term that is not present (the iT?dif without ts_dif2, iTsdif) is refused.
+ * roms_hip_dia_index (host-only, no GPU): the reference's idiag (1-based, mod_scalars.F:4027-4043) of a term for a
+ * build with / without horizontal diffusion and rotated mixing, 0 where the term is not present; dia_id = DIA_COUNT
+ * returns NDT. */
+enum roms_dia_group { DIA_ALWAYS = 0, DIA_HDIF = 1, DIA_ROT = 2 };
+enum roms_dia_id {
+#define ROMS_DIA(name, group, what) DIA_##name,
+#define ROMS_DIA_RESERVED(name, what)
+#include "roms_dia.def"
+#undef ROMS_DIA
+#undef ROMS_DIA_RESERVED
+  DIA_COUNT,
+  DIA_RESERVED_BASE = DIA_COUNT,
+#define ROMS_DIA(name, group, what)
+#define ROMS_DIA_RESERVED(name, what) DIA_##name,
+#include "roms_dia.def"
+#undef ROMS_DIA
+#undef ROMS_DIA_RESERVED
+  DIA_END
+};
+int roms_hip_set_diagnostics(int nDIA, int ntsDIA, int ntstart, int nrrec);
+int roms_hip_set_diags(const roms_step_idx_t *s);
+int roms_hip_get_diagnostic(int dia_id, int itrc, int accumulated, double *host, long n_doubles);
+int roms_hip_dia_index(int dia_id, int hdif, int rotated);
 /* Lagrangian floats (FLOATS): step_floats(ng, Lstr, Lend), ROMS/Nonlinear/step_floats.F:80-1053, with interp_floats
  * (ROMS/Nonlinear/interp_floats.F:56-541), the block at the end of the step (main3d.F:873-906).  Built for SOLVE3D and
  * FLOATS with or without MASKING; not built: FLOAT_VWALK, FLOAT_STICKY, FLOAT_BIOLOGY / FLOAT_OYSTER, the 2-D branch,

@@ -107,7 +107,7 @@ __global__ void k_fill_guard(unsigned long long *p, long n, unsigned long long b
   if (e < n) p[e] = bits;
 }
 
-static int guarded_alloc(double **user, double **base, long n)
+int guarded_alloc(double **user, double **base, long n)
 {
   const long g = g_ctx.guard;
   *user = *base = nullptr;
@@ -124,7 +124,7 @@ static int guarded_alloc(double **user, double **base, long n)
   return 0;
 }
 
-static void guarded_free(double **user, double **base)
+void guarded_free(double **user, double **base)
 {
   if (*base) (void)hipFree(*base);
   *user = *base = nullptr;
@@ -200,6 +200,14 @@ extern "C" int roms_hip_check_guards(void)
     if ((rc = check(k_avg_line[g_avg.arr[q].id].name, -1, g_avg.arr[q].base, g_avg.arr[q].count))) return rc;
   for (int q = 0; q < 4; q++)
     if ((rc = check(k_avg_line[AVG_pmask_avg + q].name, -1, g_avg.cnt_base[q], g_avg.nij))) return rc;
+  {
+    const char *name[4];
+    const double *base[4];
+    long count[4];
+    const int n = dia_arrays(name, base, count);
+    for (int q = 0; q < n; q++)
+      if ((rc = check(name[q], -1, base[q], count[q]))) return rc;
+  }
   for (int q = 0; q < ROMS_NWS3; q++)
     if ((rc = check("ws3", q, g_ctx.ws3_base[q], nij * (b.N + 1)))) return rc;
   for (int q = 0; q < 32; q++)
@@ -288,6 +296,7 @@ extern "C" int roms_hip_finalize(void)
   avg_release();
   floats_release();
   tides_release();
+  dia_release();
   if (g_ctx.devc) (void)hipFree(g_ctx.devc);
   g_ctx.devc = nullptr;
   if (g_ctx.stream) (void)hipStreamDestroy(g_ctx.stream);
@@ -627,6 +636,7 @@ extern "C" int roms_hip_set_bounds(const roms_bounds_t *b)
   avg_release();                           // ... and so have the averages
   floats_release();                        // ... and the floats' coordinate arrays
   tides_release();                         // ... and the tidal strips
+  dia_release();                           // ... and the tracer diagnostics
   halo_bounds_changed();                   // ... and the message plan has the old extents and ghost points
   g_ctx.b = *b;
   g_ctx.hostc.b = *b;

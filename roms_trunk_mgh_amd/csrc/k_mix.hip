@@ -237,7 +237,9 @@ k_t3dmix_geo(const RomsDev *__restrict__ c, int nrhs, int nnew, Lap4 L)
   }
 }
 
-template <bool STAB>
+// DIA (DIAGNOSTICS_TS, t3dmix2_s.h:293-296): the two directions and their sum go to DiaTwrk(iTxdif, iTydif, iThdif)
+// (m Tunits; k_step3d_t_pipe turns them into Tunits)
+template <bool STAB, bool DIA = false>
 __global__ void __launch_bounds__(BLK_X *BLK_Y)
 k_t3dmix2_s(const RomsDev *__restrict__ c, int nrhs, int nnew, int nstp)
 {
@@ -275,7 +277,13 @@ k_t3dmix2_s(const RomsDev *__restrict__ c, int nrhs, int nnew, int nstp)
     if (masking) { FX0 = FX0 * um0; FX1 = FX1 * um1; FE0 = FE0 * vm0; FE1 = FE1 * vm1; }
     const double cff1 = cdt * (FX1 - FX0);
     const double cff2 = cdt * (FE1 - FE0);
-    tn[ck] = tn[ck] + (cff1 + cff2);
+    const double cff3 = cff1 + cff2;
+    tn[ck] = tn[ck] + cff3;
+    if constexpr (DIA) {
+      DIA_PLANE(c, DIA_iTxdif, itrc, n3r)[ck] = cff1;
+      DIA_PLANE(c, DIA_iTydif, itrc, n3r)[ck] = cff2;
+      DIA_PLANE(c, DIA_iThdif, itrc, n3r)[ck] = cff3;
+    }
   }
 }
 
@@ -349,6 +357,9 @@ static int t3dmix2_launch(const roms_step_idx_t *s)
   } else if (g_ctx.p.mix_geo_ts) {
     if (stab) hipLaunchKernelGGL((k_t3dmix_geo<0, false, true>), grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, L);
     else hipLaunchKernelGGL((k_t3dmix_geo<0, false>), grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, L);
+  } else if (g_ctx.p.mix_s_ts && dia_on()) {
+    if (stab) hipLaunchKernelGGL((k_t3dmix2_s<true, true>), grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, s->nstp);
+    else hipLaunchKernelGGL((k_t3dmix2_s<false, true>), grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, s->nstp);
   } else if (g_ctx.p.mix_s_ts) {
     if (stab) hipLaunchKernelGGL(k_t3dmix2_s<true>, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, s->nstp);
     else hipLaunchKernelGGL(k_t3dmix2_s<false>, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, s->nstp);
@@ -362,6 +373,9 @@ extern "C" int roms_hip_t3dmix2(const roms_step_idx_t *s)
 {
   int rc = roms_entry_check("roms_hip_t3dmix2");
   if (rc) return rc;
+  if ((rc = dia_check("roms_hip_t3dmix2"))) return rc;
+  if (dia_on() && !g_ctx.p.ts_dif2)
+    return roms_fail("roms_hip_t3dmix2", "diagnostics: ts_dif2 is off, the iT?dif terms have no planes (NDT = 6)");
   ScopedTimer tm("t3dmix2");
   return t3dmix2_launch(s);
 }
@@ -373,6 +387,7 @@ extern "C" int roms_hip_t3dmix4(const roms_step_idx_t *s)
   const roms_bounds_t &b = g_ctx.b;
   const roms_params_t &p = g_ctx.p;
   if (!p.ts_dif4) return roms_fail("roms_hip_t3dmix4", "TS_DIF4 is not set (roms_params_t.ts_dif4)");
+  if ((rc = dia_check("roms_hip_t3dmix4"))) return rc;
   if (!p.mix_iso_ts && !p.mix_geo_ts && !p.mix_s_ts)
     return roms_fail("roms_hip_t3dmix4", "no tracer mixing option (MIX_ISO_TS / MIX_GEO_TS / MIX_S_TS) selected");
   ScopedTimer tm("t3dmix4");

@@ -22,7 +22,9 @@ int roms_entry_check(const char *name);
 namespace {
 
 // MASK: MASKING applications, first differences times umask / vmask of their face (pre_step3d.F:398, :463)
-template <int HADV, int VADV, int NMAX, bool MASK>
+// DIA (DIAGNOSTICS_TS, pre_step3d.F:899-902): the two summands of the corrector's start go to DiaTwrk(iTrate) and
+// DiaTwrk(iTvdif) (m Tunits; k_step3d_t_pipe turns them into Tunits).  Instantiated at NMAX = ROMS_MAXN only.
+template <int HADV, int VADV, int NMAX, bool MASK, bool DIA = false>
 __global__ void __launch_bounds__(BLK_X *BLK_Y)
 k_pre_t(const RomsDev *__restrict__ c, int nstp, int nnew, int first_step, int itrc0, int ntr)
 {
@@ -123,7 +125,12 @@ k_pre_t(const RomsDev *__restrict__ c, int nstp, int nnew, int first_step, int i
         FDk = FDk + dsrf * swdk;
       }
     }
-    tn[ck] = hz * tk + (FDk - FDprev);
+    const double hzt = hz * tk, dFD = FDk - FDprev;
+    tn[ck] = hzt + dFD;
+    if constexpr (DIA) {
+      DIA_PLANE(c, DIA_iTrate, itrc, n3r)[ck] = hzt;
+      DIA_PLANE(c, DIA_iTvdif, itrc, n3r)[ck] = dFD;
+    }
     FDprev = FDk;
     FCprev = FCk;
     w_km1 = w_k;
@@ -215,6 +222,9 @@ int launch_pre_t(const roms_step_idx_t *s, int itrc0, int ntr)
   if constexpr (HADV != ADV_MPDATA)                    // the upstream predictor of MPDATA / HSIMT has no mask
     if (g_ctx.p.masking)
       kernel = kernel_for_n(b.N, [](auto nm) -> PreKernel { return k_pre_t<HADV, VADV, nm.value, true>; });
+  if constexpr (HADV != ADV_MPDATA && VADV != ADV_MPDATA)   // (dia_check has refused the upstream predictors)
+    if (dia_on())
+      kernel = g_ctx.p.masking ? k_pre_t<HADV, VADV, ROMS_MAXN, true, true> : k_pre_t<HADV, VADV, ROMS_MAXN, false, true>;
   hipLaunchKernelGGL(kernel, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nstp, s->nnew, first, itrc0, ntr);
   KERNEL_CHECK("k_pre_t");
   return 0;
@@ -283,6 +293,7 @@ extern "C" int roms_hip_pre_step3d(const roms_step_idx_t *s)
   if (rc) return rc;
   if ((rc = check_lbc())) return rc;
   if (g_ctx.b.N < 4) return roms_fail("roms_hip_pre_step3d", "needs N >= 4 levels (the vertical stencils of the column read k-1 .. k+2)");
+  if ((rc = dia_check("roms_hip_pre_step3d"))) return rc;
   ScopedTimer tm("pre_step3d");
   // (the reference does the tracers first; the two halves share no output)
   if ((rc = pre_step3d_uv(s))) return rc;

@@ -246,7 +246,13 @@ struct LevelIn {         // (members in the order of the loads: the copy cur = n
 // advected tracer stays thickness-weighted (:1196-1198 is not compiled) and the implicit vertical diffusion is a
 // tridiagonal system for the tracer itself with the layer distances from z_r -- solved after the level loop from the
 // column in LDS.  Instantiated at NMAX = 64 only (one kernel serves every N, not tuned).
-template <int HADV, int VADV, int NMAX, bool MASK, bool SRC = false, bool SPL = true>
+// DIA (DIAGNOSTICS_TS; NMAX = 64 only, not tuned): per level the upward sweep writes DiaTwrk(iTxadv, iTyadv, iThadv,
+// iTvadv) (step3d_t.F:868-871, :1199) and multiplies every term of the level by oHz (:1200-1203) -- those it has just
+// formed in registers, and the planes iTrate, iTvdif and iT?dif that k_pre_t and k_t3dmix2_s wrote earlier in the step,
+// read, scaled and written back; the back substitution adds the implicit increment to iTvdif (:1421-1424, or
+// :1482-1485 / :1495-1498 without SPLINES_VDIFF).  Six (nine with ts_dif2) planes per tracer, each store 64
+// consecutive doubles per wavefront like the tracer's own.
+template <int HADV, int VADV, int NMAX, bool MASK, bool SRC = false, bool SPL = true, bool DIA = false>
 __global__ void __launch_bounds__(BLK_X *BLK_Y)
 k_step3d_t_pipe(const RomsDev *__restrict__ c, int nnew, int itrc0, int ntr)
 {
@@ -279,6 +285,20 @@ k_step3d_t_pipe(const RomsDev *__restrict__ c, int nnew, int itrc0, int ntr)
   // wall rows: the outer stencil point is not used; read a valid address instead
   const long oym2 = wl.s ? 0 : -2 * ni, oyp2 = wl.n ? 0 : 2 * ni;
   const long oxm2 = wl.w ? 0 : -2, oxp2 = wl.e ? 0 : 2;
+  static_assert(!(DIA && SRC), "point sources are refused together with the diagnostics");
+  // the planes of the terms, found once per column (DIA = false: never set, never read)
+  struct { gd_t xadv, yadv, hadv, vadv, rate, vdif, hdif, xdif, ydif; } dp{};
+  bool dia_hdif = false;                                   // ts_dif2: the planes iThdif, iTxdif, iTydif exist
+  if constexpr (DIA) {
+    dp.xadv = DIA_PLANE(c, DIA_iTxadv, itrc, n3r); dp.yadv = DIA_PLANE(c, DIA_iTyadv, itrc, n3r);
+    dp.hadv = DIA_PLANE(c, DIA_iThadv, itrc, n3r); dp.vadv = DIA_PLANE(c, DIA_iTvadv, itrc, n3r);
+    dp.rate = DIA_PLANE(c, DIA_iTrate, itrc, n3r); dp.vdif = DIA_PLANE(c, DIA_iTvdif, itrc, n3r);
+    dia_hdif = c->dia.ndt > 6;
+    if (dia_hdif) {
+      dp.hdif = DIA_PLANE(c, DIA_iThdif, itrc, n3r); dp.xdif = DIA_PLANE(c, DIA_iTxdif, itrc, n3r);
+      dp.ydif = DIA_PLANE(c, DIA_iTydif, itrc, n3r);
+    }
+  }
 
   double CF[NMAX + 1], DC[NMAX + 1];
   CF[0] = 0.0;
@@ -326,14 +346,27 @@ k_step3d_t_pipe(const RomsDev *__restrict__ c, int nnew, int itrc0, int ntr)
       const double hz = cur.hz;
       const double ohz = 1.0 / hz;
       double tv = cur.tv;
-      {
-        const double cff1 = cffdt * (fx.FXip1 - fx.FXi);
-        const double cff2 = cffdt * (fx.FEjp1 - fx.FEj);
-        const double cff3 = cff1 + cff2;
-        tv = tv - cff3;
-      }
-      tv = tv - cffdt * (FCk - FCprev);
+      const double cff1 = cffdt * (fx.FXip1 - fx.FXi);
+      const double cff2 = cffdt * (fx.FEjp1 - fx.FEj);
+      const double cff3 = cff1 + cff2;
+      tv = tv - cff3;
+      const double cffv = cffdt * (FCk - FCprev);
+      tv = tv - cffv;
       if constexpr (SPL) tv = tv * ohz;
+      if constexpr (DIA) {
+        const long ck = c0 + (long)(k - 1) * nij;
+        dp.xadv[ck] = -cff1 * ohz;
+        dp.yadv[ck] = -cff2 * ohz;
+        dp.hadv[ck] = -cff3 * ohz;
+        dp.vadv[ck] = -cffv * ohz;
+        dp.rate[ck] = dp.rate[ck] * ohz;
+        dp.vdif[ck] = dp.vdif[ck] * ohz;
+        if (dia_hdif) {
+          dp.hdif[ck] = dp.hdif[ck] * ohz;
+          dp.xdif[ck] = dp.xdif[ck] * ohz;
+          dp.ydif[ck] = dp.ydif[ck] * ohz;
+        }
+      }
       if constexpr (SRC) tv = src_w_tracer(c, c0, k, itrc, SPL ? cffdt * ohz : cffdt, tk, tv);   // LwSrc, step3d_t.F:1331-1360
       s_tn[(k - 1) * NTH + tid] = tv;
       FCprev = FCk;
@@ -385,6 +418,10 @@ k_step3d_t_pipe(const RomsDev *__restrict__ c, int nnew, int itrc0, int ntr)
         const double v = (k == N) ? DC[k] : DC[k] - CF[k] * up;
         up = v;
         const long ck = c0 + (long)(k - 1) * nij;
+        if constexpr (DIA) {                         // step3d_t.F:1476, :1482-1485 (k = N), :1490, :1495-1498
+          const double cff1 = s_tn[(k - 1) * NTH + tid] * (1.0 / f.Hz[ck]);
+          dp.vdif[ck] = dp.vdif[ck] + v - cff1;
+        }
         if constexpr (MASK) tn_g[ck] = v * GF(rmask)[c0];
         else tn_g[ck] = v;
       }
@@ -412,6 +449,9 @@ k_step3d_t_pipe(const RomsDev *__restrict__ c, int nnew, int itrc0, int ntr)
       const double cff1 = dt * ohz * (dcA_up - dcA);
       if constexpr (MASK) tn_g[ck] = (s_tn[kk * NTH + tid] + cff1) * GF(rmask)[c0];
       else tn_g[ck] = s_tn[kk * NTH + tid] + cff1;
+      if constexpr (DIA) {                           // step3d_t.F:1421-1424
+        dp.vdif[ck] = dp.vdif[ck] + cff1;
+      }
       dcA_up = dcA;
       akA = akB; hzA = hzB; akB = akC; hzB = hzC;
     }
@@ -444,7 +484,12 @@ int launch_pipe(int nnew, int itrc0, int ntr)
   if (b.N > ROMS_MAXN) return roms_fail("roms_hip_step3d_t", "N > 64 not instantiated");
   const bool mask = g_ctx.p.masking != 0, spl = g_ctx.p.splines_vdiff != 0;
   StepKernel kernel;
-  if (!spl)          // without SPLINES_VDIFF: one instantiation for every N
+  if (dia_on())      // DIAGNOSTICS_TS: one instantiation for every N (dia_check has refused point sources)
+    kernel = mask ? (spl ? k_step3d_t_pipe<HADV, VADV, ROMS_MAXN, true, false, true, true>
+                         : k_step3d_t_pipe<HADV, VADV, ROMS_MAXN, true, false, false, true>)
+                  : (spl ? k_step3d_t_pipe<HADV, VADV, ROMS_MAXN, false, false, true, true>
+                         : k_step3d_t_pipe<HADV, VADV, ROMS_MAXN, false, false, false, true>);
+  else if (!spl)     // without SPLINES_VDIFF: one instantiation for every N
     kernel = mask ? k_step3d_t_pipe<HADV, VADV, ROMS_MAXN, true, false, false>
                   : k_step3d_t_pipe<HADV, VADV, ROMS_MAXN, false, false, false>;
   else if (mask)     // land/sea masks applied
@@ -501,6 +546,7 @@ extern "C" int roms_hip_step3d_t(const roms_step_idx_t *s)
   const roms_bounds_t &b = g_ctx.b;
   const roms_params_t &p = g_ctx.p;
   if (b.N < 4) return roms_fail("roms_hip_step3d_t", "needs N >= 4 levels (the vertical stencils of the column read k-1 .. k+2)");
+  if ((rc = dia_check("roms_hip_step3d_t"))) return rc;
   if (!p.splines_vdiff)
     for (int it = 1; it <= b.NT; it++)
       if (p.Hadv[it - 1] == ADV_HSIMT || p.Vadv[it - 1] == ADV_HSIMT)
@@ -555,6 +601,7 @@ extern "C" int roms_hip_step3d_t(const roms_step_idx_t *s)
     hipLaunchKernelGGL(k_t_nudge, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nnew);
     KERNEL_CHECK("k_t_nudge");
   }
+  if (dia_on() && (rc = dia_rate(s->nnew))) return rc;     // step3d_t.F:1598-1611
   const long n3r = (long)(b.UBi - b.LBi + 1) * (b.UBj - b.LBj + 1) * b.N;
   halo_batch_begin();
   for (int it = 1; it <= b.NT; it++)

@@ -101,6 +101,18 @@ struct AvgStore {
 };
 extern AvgStore g_avg;
 
+// DIAGNOSTICS_TS (roms_hip_set_diagnostics, k_set_diags.hip): DiaTwrk(LBi:UBi, LBj:UBj, N, NT, NDT) of mod_diags.F on
+// the device, plane-major like the tracer itself (consecutive lanes along i store consecutive doubles of one term's
+// plane), and the plane of every term of roms_dia.def: ix[id] = idiag - 1, or -1 where the term is not present.
+// wrk == nullptr: diagnostics off, and no kernel reads this block.
+struct RomsDia {
+  double *wrk;
+  int ndt;
+  int ix[DIA_COUNT];
+};
+// DiaTwrk(:,:,:,itrc,idiag) of term `id` (device code; n3r = points of a rho-array)
+#define DIA_PLANE(c, id, itrc, n3r) ((gd_t)((c)->dia.wrk + ((long)(c)->dia.ix[id] * (c)->b.NT + ((itrc) - 1)) * (n3r)))
+
 struct RomsDev {
   roms_bounds_t b;
   roms_params_t p;
@@ -112,6 +124,7 @@ struct RomsDev {
   RomsSrc src;          // point sources (LuvSrc), n = 0 without
   RomsClima clima;      // climatology nudging, all flags zero without
   RomsTides tides;      // tidal boundary forcing, ntc = 0 without
+  RomsDia dia;          // tracer diagnostics, wrk = nullptr without
 };
 
 struct RomsCtx {
@@ -393,6 +406,13 @@ int halo_batch_end();                     // ... and run them as one message per
 int halo_allreduce_sum(double *A, long n); // mp_collect: SUM over all tiles of a device array, in place (halo.hip)
 void floats_release();                    // k_floats.hip: frees what roms_hip_set_floats allocated
 void tides_release();                     // k_set_tides.hip: frees what roms_hip_set_tides allocated
+int guarded_alloc(double **user, double **base, long n);   // capi.hip: n zeroed doubles between two guard bands
+void guarded_free(double **user, double **base);
+void dia_release();                       // k_set_diags.hip: frees what roms_hip_set_diagnostics allocated
+bool dia_on();                            // ... diagnostics are switched on (the DIA instantiations run)
+int dia_check(const char *where);         // ... and what they are not built with, refused by name (0 when off)
+int dia_rate(int nnew);                   // ... step3d_t.F:1598-1611 on IstrR:IendR, JstrR:JendR (k_dia_rate)
+int dia_arrays(const char *name[4], const double *base[4], long count[4]);   // ... its arrays, for roms_hip_check_guards
 // lateral boundary conditions on the S/N edges (k_base.hip); s = the barotropic time indices (Chapman, Flather),
 // nstp = the time level the radiation condition compares with
 int bc_zeta(int kout, const roms_step_idx_t *s);

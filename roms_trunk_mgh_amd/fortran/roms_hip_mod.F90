@@ -358,6 +358,29 @@ MODULE roms_hip_mod
       IMPORT :: c_int
       INTEGER(c_int), VALUE :: iic, nAVG, ntsAVG, ntstart, nrrec
     END FUNCTION
+    !  DIAGNOSTICS_TS: the window after roms_hip_set_params (nDIA = 0 switches the diagnostics off); set_diags(ng,tile)
+    !  (main3d.F:491); the D->H copy of one term's plane for wrt_diags (dia_id: the order of include/roms_dia.def from 0,
+    !  accumulated = 0 DiaTwrk, 1 DiaTrc); the reference's idiag of a term (0 = not present)
+    INTEGER(c_int) FUNCTION roms_hip_set_diagnostics (nDIA, ntsDIA, ntstart, nrrec)                                  &
+   &                        BIND(C, name='roms_hip_set_diagnostics')
+      IMPORT :: c_int
+      INTEGER(c_int), VALUE :: nDIA, ntsDIA, ntstart, nrrec
+    END FUNCTION
+    INTEGER(c_int) FUNCTION roms_hip_set_diags (s) BIND(C, name='roms_hip_set_diags')
+      IMPORT :: c_int, roms_step_idx_t
+      TYPE(roms_step_idx_t), INTENT(in) :: s
+    END FUNCTION
+    INTEGER(c_int) FUNCTION roms_hip_get_diagnostic (dia_id, itrc, accumulated, host, n_doubles)                     &
+   &                        BIND(C, name='roms_hip_get_diagnostic')
+      IMPORT :: c_int, c_long, c_ptr
+      INTEGER(c_int), VALUE :: dia_id, itrc, accumulated
+      TYPE(c_ptr), VALUE :: host
+      INTEGER(c_long), VALUE :: n_doubles
+    END FUNCTION
+    INTEGER(c_int) FUNCTION roms_hip_dia_index (dia_id, hdif, rotated) BIND(C, name='roms_hip_dia_index')
+      IMPORT :: c_int
+      INTEGER(c_int), VALUE :: dia_id, hdif, rotated
+    END FUNCTION
     !  FLOATS: DRIFTER(ng) handed over once after roms_hip_set_params (Ftype, Tinfo(0:izrhs,Nfloats), Fz0 and the two
     !  coordinate arrays iflon / iflat are interpolated from: lonr, latr or xr, yr); track and bounded to and from the
     !  device (restart, wrt_floats); step_floats (main3d.F:894) with nfl = (/ nfm3, nfm2, nfm1, nf, nfp1 /) and
@@ -433,6 +456,7 @@ MODULE roms_hip_mod
   PUBLIC :: roms_hip_ini_zeta, roms_hip_ini_fields, roms_hip_gls_prestep, roms_hip_gls_corstep, roms_hip_wetdry
   PUBLIC :: roms_hip_set_sources, roms_hip_set_clima
   PUBLIC :: roms_hip_set_averages, roms_hip_set_avg, roms_hip_get_average, roms_hip_average_device_ptr, roms_hip_avg_phase
+  PUBLIC :: roms_hip_set_diagnostics, roms_hip_set_diags, roms_hip_get_diagnostic, roms_hip_dia_index
   PUBLIC :: roms_hip_set_floats, roms_hip_floats_put, roms_hip_floats_get, roms_hip_step_floats
   PUBLIC :: roms_hip_set_tides, roms_hip_tides
   PUBLIC :: roms_hip_entry, roms_hip_make_idx, roms_hip_status

@@ -29,7 +29,7 @@ def use_library(path):
 ENTRIES = ["set_massflux", "rho_eos", "omega", "set_zeta", "set_depth", "rhs3d",
            "pre_step3d", "prsgrd", "t3dmix2", "rhs3d_tile", "uv3dmix2", "step2d",
            "step3d_uv", "step3d_t", "bulk_flux", "set_vbc", "lmd_vmix", "wvelocity", "ini_zeta", "ini_fields",
-           "t3dmix4", "uv3dmix4", "gls_prestep", "gls_corstep", "wetdry", "set_avg"]
+           "t3dmix4", "uv3dmix4", "gls_prestep", "gls_corstep", "wetdry", "set_avg", "set_diags"]
 
 # every symbol include/roms_hip.h declares
 DECLARED_SYMBOLS = (
@@ -44,7 +44,8 @@ DECLARED_SYMBOLS = (
      "roms_hip_graph_exchanges", "roms_hip_graph_exchanges_state", "roms_hip_set_sources",
      "roms_hip_set_clima", "roms_hip_set_averages", "roms_hip_get_average", "roms_hip_average_device_ptr",
      "roms_hip_avg_phase", "roms_hip_set_floats", "roms_hip_floats_put", "roms_hip_floats_get",
-     "roms_hip_step_floats", "roms_hip_set_tides", "roms_hip_tides"] + ["roms_hip_" + e for e in ENTRIES])
+     "roms_hip_step_floats", "roms_hip_set_tides", "roms_hip_tides", "roms_hip_set_diagnostics",
+     "roms_hip_get_diagnostic", "roms_hip_dia_index"] + ["roms_hip_" + e for e in ENTRIES])
 
 
 _DP = C.POINTER(C.c_double)
@@ -100,6 +101,9 @@ def load():
     lib.roms_hip_set_tides.argtypes = ([C.c_int, C.c_int] + [_DP] * 8 + [C.c_double, C.c_int, C.c_double, C.c_int, _DP,
                                         C.c_int, _DP, _DP])
     lib.roms_hip_tides.argtypes = [C.c_double]
+    lib.roms_hip_set_diagnostics.argtypes = [C.c_int] * 4
+    lib.roms_hip_get_diagnostic.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long]
+    lib.roms_hip_dia_index.argtypes = [C.c_int] * 3
     lib.roms_hip_set_halo_relay.argtypes = [RELAY_FN, C.c_void_p]
     if hasattr(lib, "roms_hip_tile_neighbors"):
         lib.roms_hip_tile_neighbors.argtypes = [C.c_int] * 7 + [C.POINTER(C.c_int)]
@@ -198,6 +202,28 @@ class RomsHip:
             raise RuntimeError("roms_hip get_average: no averages selected (set_averages)")
         out = np.zeros(self.averages.shape(name), dtype=np.float64, order="F")
         self._chk(self.l.roms_hip_get_average(avg.AVG_ID[name], int(itrc), out.ctypes.data, out.size), "get_average " + name)
+        return out
+
+    def set_diagnostics(self, diags):
+        """nDIA / ntsDIA of the tracer budget diagnostics (roms_trunk_mgh_amd/diags.py) -> roms_hip_set_diagnostics; None
+        switches them off (nDIA = 0) and releases the arrays."""
+        args = diags.c_args() if diags is not None else (0, 0, 0, 0)
+        self._chk(self.l.roms_hip_set_diagnostics(*args), "set_diagnostics")      # (refused: the set in force stays)
+        self.diags = diags
+
+    def set_diags(self, s):
+        """set_diags (main3d.F:491): initialise or accumulate DiaTrc, avgzeta and the counter, roms_hip_set_diags"""
+        self.call("set_diags", s)
+
+    def get_diagnostic(self, name, itrc=1, accumulated=False):
+        """The plane (LBi:UBi, LBj:UBj, N) of term `name` of roms_dia.def and tracer itrc (1-based), DiaTwrk or with
+        accumulated DiaTrc; "avgzeta" / "rmask_dia": those 2-D arrays (roms_hip_get_diagnostic)."""
+        from . import diags as _diags
+        if getattr(self, "diags", None) is None:
+            raise RuntimeError("roms_hip get_diagnostic: diagnostics are off (set_diagnostics)")
+        out = np.zeros(self.diags.shape(name), dtype=np.float64, order="F")
+        self._chk(self.l.roms_hip_get_diagnostic(_diags.DIA_ID[name], int(itrc), int(bool(accumulated)), out.ctypes.data,
+                                                 out.size), "get_diagnostic " + name)
         return out
 
     def set_floats(self, floats):

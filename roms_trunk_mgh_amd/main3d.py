@@ -15,6 +15,7 @@ against either backend (`hip.RomsHip` = the product, or the CPU oracle in tests)
     main3d.F:395-397  set_tides                        (SSH_TIDES / UV_TIDES: tides=...)
     main3d.F:467-475  lmd_vmix (physics=True; else fixed mixing inputs); omega; wvelocity (diagnostics=True)
     main3d.F:489      set_zeta
+    main3d.F:491      set_diags                        (DIAGNOSTICS_TS: diags=...)
     main3d.F:494      set_avg                          (AVERAGES: averages=...)
     main3d.F:563      rhs3d
     main3d.F:567      gls_prestep                      (GLS_MIXING applications)
@@ -45,7 +46,8 @@ def host_clock(tdays):
 
 
 class Main3D:
-    def __init__(self, backend, ntstart=1, physics=False, diagnostics=False, ninfo=1, averages=None, floats=None, tides=None):
+    def __init__(self, backend, ntstart=1, physics=False, diagnostics=False, ninfo=1, averages=None, floats=None, tides=None,
+                 diags=None):
         """physics=True also runs the per-step physics that is on the device:
         bulk_flux and lmd_vmix (BULK_FLUXES / LMD_MIXING applications, i.e. BENCHMARK) and set_vbc, in
         the reference's order;
@@ -62,7 +64,10 @@ class Main3D:
         rotates the five float time levels afterwards (main3d.F:894-903).
         tides: a tides.Tides (SSH_TIDES / UV_TIDES applications): handed to the backend here (set_tides); every step
         issues tides((iic - ntstart) * dt) at the place of set_tides, directly after set_vbc (main3d.F:395-397) -- with
-        physics=False at the same place in the sequence."""
+        physics=False at the same place in the sequence.
+        diags: a diags.Diags (DIAGNOSTICS_TS applications): handed to the backend here (set_diagnostics); every step issues
+        set_diags after set_zeta and before set_avg (main3d.F:490-492), and pre_step3d, t3dmix2 and step3d_t write the
+        budget terms; the host fetches them with backend.get_diagnostic."""
         self.be = backend
         self.tides = tides
         if tides is not None:
@@ -70,6 +75,9 @@ class Main3D:
         self.floats = floats
         if floats is not None:
             backend.set_floats(floats)
+        self.diags = diags
+        if diags is not None:
+            backend.set_diagnostics(diags)
         self.averages = averages
         if averages is not None:
             backend.set_averages(averages)
@@ -131,6 +139,8 @@ class Main3D:
         if self.diagnostics:
             be.call("wvelocity", s)
         be.call("set_zeta", s)
+        if self.diags is not None:
+            be.call("set_diags", s)
         if self.averages is not None:
             be.call("set_avg", s)
         be.call("rhs3d", s)

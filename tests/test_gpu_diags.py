@@ -1,0 +1,431 @@
+"""-m gpu: the tracer budget diagnostics on the device (DIAGNOSTICS_TS: roms_hip_set_diagnostics, roms_hip_set_diags,
+roms_hip_get_diagnostic; the DIA instantiations of k_pre_t, k_t3dmix2_s, k_step3d_t_pipe and csrc/k_set_diags.hip).
+
+The oracle has no diagnostic lines: the expected terms are recovered from its per-routine entry points by
+tests/diags_util.py (stage differences, one transport zeroed at a time), whose closure tests/test_diags.py checks
+without a GPU, within the bound stated there.  Bit-equality claims get no tolerance.
+  1. every term of one pre_step3d / t3dmix2 / step3d_t sequence: the seven scheme pairs, with and without
+     SPLINES_VDIFF, MASKING and TS_DIF2, at N = 17 and N = 64 (the two ends of the NMAX = 64 instantiation), on a grid two
+     workgroups wide in x and in y
+  2. closure in whole steps; the state is untouched by the diagnostics
+  3. accumulation (set_diags) against the numpy restatement, bit for bit; the boundary recurrence of iTrate; 2 x 1 tiles
+     against one tile, bit for bit on owned points
+  4. the refusals"""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import diags_util as du
+import util
+from roms_trunk_mgh_amd import abi, ana, diags, hip, main3d
+from test_diags import SHAPE, _state
+from test_gpu_multitile import HERE, _free_port
+
+pytestmark = pytest.mark.gpu
+
+PAIRS = [("U3", "C4"), ("A4", "A4"), ("C4", "C4"), ("C2", "C2"), ("U3", "SPLINES"), ("C4", "SPLINES"), ("A4", "SPLINES")]
+ADV = ("iThadv", "iTxadv", "iTyadv", "iTvadv")
+
+
+def _names(st):
+    ix = diags.indices(st.p.ts_dif2)
+    return [n for n in ix if n != "NDT"]
+
+
+def _fetch(be, st, accumulated=False):
+    """{term: (ni, nj, N, NT)} of every present term"""
+    return {n: np.stack([be.get_diagnostic(n, it, accumulated) for it in range(1, st.b.NT + 1)], axis=-1) for n in _names(st)}
+
+
+def _sequence(st0, s, zero=(), zero_mix=()):
+    """pre_step3d, t3dmix2 (with ts_dif2), step3d_t on the device with the diagnostics on; `zero`: transports zeroed
+    between the first two and step3d_t (the predictor has then seen the whole flow); `zero_mix`: face metrics zeroed
+    for t3dmix2 alone (neither of the other two reads them).  Returns (terms, state)."""
+    st = st0.copy()
+    be = hip.RomsHip(st)
+    try:
+        be.set_diagnostics(diags.Diags(st.b, 1))
+        be.call("pre_step3d", s)
+        if st.p.ts_dif2:
+            for name in zero_mix:
+                st[name][:] = 0.0
+            if zero_mix:
+                be.to_device(list(zero_mix))
+            be.call("t3dmix2", s)
+        for name in zero:
+            st[name][:] = 0.0
+        if zero:
+            be.to_device(list(zero))
+        be.call("step3d_t", s)
+        got = _fetch(be, st)
+        be.to_host()
+        be.check_guards()
+    finally:
+        be.close()
+    return got, st
+
+
+def _check_terms(st0, uniform):
+    s = util.step_idx()
+    r = du.recover(st0, s)
+    got, st = _sequence(st0, s)
+    w = np.broadcast_to(du.water(st0), got["iTrate"].shape)
+    assert set(got) == set(_names(st0)) and len(got) == (9 if st0.p.ts_dif2 else 6)
+    for name in got:
+        ex = du.within(got[name], r[name], w)
+        print(f"{name}: excess over the bound {ex:.3e}, largest |term| {np.abs(got[name][w]).max():.3e}")
+        assert ex <= 0.0, (name, ex)
+        assert np.abs(got[name][w]).max() > 0.0, name
+    # one transport zeroed: the other directions' terms do not move by a bit
+    gx, _ = _sequence(st0, s, zero=("Hvom",))
+    gy, _ = _sequence(st0, s, zero=("Huon",))
+    assert np.array_equal(got["iTxadv"], gx["iTxadv"]) and np.array_equal(got["iTyadv"], gy["iTyadv"])
+    assert np.array_equal(got["iTvadv"], gx["iTvadv"]) and np.array_equal(got["iTvadv"], gy["iTvadv"])
+    assert not gx["iTyadv"][w].any() and not gy["iTxadv"][w].any()
+    assert np.array_equal(gx["iTxadv"], gx["iThadv"]) and np.array_equal(gy["iTyadv"], gy["iThadv"])
+    if st0.p.ts_dif2:
+        # one direction's face metric zeroed: the other direction's term does not move by a bit
+        dx, _ = _sequence(st0, s, zero_mix=("pnom_v",))
+        dy, _ = _sequence(st0, s, zero_mix=("pmon_u",))
+        assert np.array_equal(got["iTxdif"], dx["iTxdif"]) and np.array_equal(got["iTydif"], dy["iTydif"])
+        assert not dx["iTydif"][w].any() and not dy["iTxdif"][w].any()
+        assert np.array_equal(dx["iTxdif"], dx["iThdif"]) and np.array_equal(dy["iTydif"], dy["iThdif"])
+    if uniform and st0.p.ts_dif2:
+        for axis, whole, none in (("y", "iTxdif", "iTydif"), ("x", "iTydif", "iTxdif")):
+            v = du.uniform_along(st0, axis)
+            ru = du.recover(v, s)
+            gu, _ = _sequence(v, s)
+            ex = du.within(gu[whole], ru["iThdif"], w)
+            print(f"{whole} (uniform in {axis}): excess over the bound {ex:.3e}")
+            assert ex <= 0.0, (whole, ex)
+            assert not gu[none][w].any() and np.array_equal(gu[whole], gu["iThdif"])
+            assert np.abs(gu[whole][w]).max() > 0.0
+
+
+@pytest.mark.parametrize("N", [17, 64])
+@pytest.mark.parametrize("hadv,vadv", PAIRS, ids=[f"{h}-{v}" for h, v in PAIRS])
+def test_every_term_of_every_scheme_pair(hadv, vadv, N):
+    _check_terms(_state(N, {"Hadv": hadv, "Vadv": vadv}), uniform=False)
+
+
+@pytest.mark.parametrize("N", [17, 64])
+@pytest.mark.parametrize("ov,mask", [({"splines_vdiff": 0}, None), ({}, "island"), ({"splines_vdiff": 0}, "island"),
+                                     ({"ts_dif2": 0}, None), ({}, None)],
+                         ids=["classic", "masked", "classic-masked", "ndt6", "plain"])
+def test_every_term_of_every_option(ov, mask, N):
+    st = _state(N, ov, mask)
+    assert (mask is None) or (st["rmask"][du.interior(st)] == 0.0).any()
+    _check_terms(st, uniform=True)
+
+
+# --------------------------------------------------------------------------------------------- 2. whole steps --
+class _Tap:
+    """forwards every call of main3d; keeps Hz and t(nstp) as rhs3d meets them and Hz as step3d_t meets it"""
+
+    def __init__(self, be, pull):
+        self._be, self._pull, self.kept = be, pull, {}
+
+    def __getattr__(self, name):
+        return getattr(self._be, name)
+
+    def call(self, kernel, s):
+        if kernel in ("rhs3d", "step3d_t"):
+            if self._pull:
+                self._be.to_host(["Hz", "t"])
+            st = self._be.st
+            self.kept[kernel] = (st["Hz"].copy(), st["t"][:, :, :, s.nstp - 1, :].copy())
+        self._be.call(kernel, s)
+
+
+@pytest.mark.parametrize("config,ov", [("UPWELLING", {}), ("BENCHMARK_TINY", {"ts_dif2": 0})], ids=["UPWELLING", "BENCHMARK"])
+def test_closure_in_a_whole_step(config, ov):
+    """Akt != 0, lmd_nonlocal / solar_source as the application sets them: the terms sum to iTrate within
+    8 eps max(|t(nnew)|, |Hz_old t(nstp) oHz_new|) (the chain of roundings from Hz*t(nstp) to t(nnew), each of the size
+    of the tracer, and the storing of the terms), and iTrate is t(nnew) - Hz_old*t(nstp)*oHz_new of the oracle's own
+    step within that bound plus the 1e-12 max|t| to which the parity tests pin t(nnew) itself."""
+    import oracle
+    st0 = ana.make_tile(config, perturb=1.0, overrides=dict(SHAPE, N=17, **ov))
+    if st0.p.ts_dif2:
+        st0["diff2"][:] = 40.0
+    assert (st0["Akt"] != 0.0).any()
+    st_o, st_h = st0.copy(), st0.copy()
+    tap_o = _Tap(oracle.Oracle(st_o), False)
+    mo = main3d.Main3D(tap_o)
+    mo.initial()
+    mo.run(2)
+    be = hip.RomsHip(st_h)
+    try:
+        tap_h = _Tap(be, True)
+        mh = main3d.Main3D(tap_h, diags=diags.Diags(st_h.b, 1))
+        mh.initial()
+        mh.run(2)
+        got = _fetch(be, st_h)
+        be.to_host()
+        be.check_guards()
+    finally:
+        be.close()
+    nnew = mo.s.nnew
+    w = np.broadcast_to(du.water(st0), got["iTrate"].shape)
+    t_new = st_h["t"][:, :, :, nnew - 1, :]
+    hz_old, t_stp = tap_o.kept["rhs3d"]
+    hz_new = tap_o.kept["step3d_t"][0]
+    b0 = (hz_old[:, :, :, None] * t_stp) * (1.0 / np.where(hz_new > 0.0, hz_new, 1.0))[:, :, :, None]
+    bound = 8.0 * du.EPS * np.maximum(np.abs(t_new), np.abs(b0))
+    total = got["iThadv"] + got["iTvadv"] + got["iTvdif"] + (got["iThdif"] if st0.p.ts_dif2 else 0.0)
+    ex = (np.abs(total - got["iTrate"]) - bound)[w].max()
+    print(f"closure: excess over the bound {ex:.3e}")
+    assert ex <= 0.0, ex
+    # iTrate against the device's own t(nnew), Hz and t(nstp): the statement of k_dia_rate restated, within the tight bound
+    hz_old_h, t_stp_h = tap_h.kept["rhs3d"]
+    hz_new_h = tap_h.kept["step3d_t"][0]
+    b0_h = (hz_old_h[:, :, :, None] * t_stp_h) * (1.0 / np.where(hz_new_h > 0.0, hz_new_h, 1.0))[:, :, :, None]
+    ex = du.within(got["iTrate"], du.diff(t_new, b0_h), w)
+    print(f"iTrate against the device's own fields: excess over the bound {ex:.3e}")
+    assert ex <= 0.0, ex
+    # ... and, as the link to the oracle, against its step: looser by what the parity tests allow t(nnew) itself
+    t_o = st_o["t"][:, :, :, nnew - 1, :]
+    ex = (np.abs(got["iTrate"] - (t_o - b0)) - (bound + 1e-12 * np.abs(t_o).max()))[w].max()
+    print(f"iTrate against the oracle's step: excess over the bound {ex:.3e}")
+    assert ex <= 0.0, ex
+    assert np.abs(got["iTrate"][w]).max() > 0.0 and np.abs(got["iTvdif"][w]).max() > 0.0
+
+
+def test_the_state_is_untouched():
+    st0 = ana.make_tile("UPWELLING", perturb=1.0, overrides=dict(SHAPE, N=17))
+    st0["diff2"][:] = 40.0
+    out = {}
+    for key in ("with", "without"):
+        st = st0.copy()
+        be = hip.RomsHip(st)
+        try:
+            m = main3d.Main3D(be, diags=diags.Diags(st.b, 3) if key == "with" else None)
+            m.initial()
+            m.run(10)
+            be.to_host()
+            be.check_guards()
+        finally:
+            be.close()
+        out[key] = st
+    for name, _, _ in abi.FIELDS:
+        assert np.array_equal(out["with"][name], out["without"][name], equal_nan=True), name
+    assert not np.array_equal(out["with"]["t"], st0["t"])
+
+
+# ------------------------------------------------------------------------------ 3. accumulation, boundaries --
+class _Acc:
+    """forwards every call; around set_diags it feeds the numpy restatement with the planes the device holds"""
+
+    def __init__(self, be, ref, wet):
+        self._be, self._ref, self._wet, self.seen = be, ref, wet, ""
+
+    def __getattr__(self, name):
+        return getattr(self._be, name)
+
+    def call(self, kernel, s):
+        be, st = self._be, self._be.st
+        if kernel != "set_diags":
+            return be.call(kernel, s)
+        wrk = _fetch(be, st)
+        be.to_host(["zeta"] + (["rmask_full"] if self._wet else []))
+        be.call(kernel, s)
+        planes = {(n, it): wrk[n][:, :, :, it - 1] for n in wrk for it in range(1, st.b.NT + 1)}
+        ini, acc = self._ref.set_diags(s.iic, planes, st["zeta"][:, :, s.kstp - 1], st["rmask_full"] if self._wet else None)
+        self.seen += "I" if ini else "A" if acc else "-"
+        trc = _fetch(be, st, accumulated=True)
+        for (n, it), want in self._ref.trc.items():
+            assert np.array_equal(trc[n][:, :, :, it - 1], want), (s.iic, n, it)
+        assert np.array_equal(be.get_diagnostic("avgzeta"), self._ref.avgzeta), s.iic
+        if self._wet:
+            assert np.array_equal(be.get_diagnostic("rmask_dia"), self._ref.cnt), s.iic
+
+
+@pytest.mark.parametrize("ntsDIA,wet,seen", [(0, False, "AIAAIAA"), (2, False, "--AAIAA"), (0, True, "AIAAIAA")],
+                         ids=["nts0", "nts2", "wet"])
+def test_seven_steps_accumulate_as_the_restatement(ntsDIA, wet, seen):
+    kw = dict(mask="island", wet=True) if wet else {}
+    st = util.prepared_state("UPWELLING", overrides=dict(SHAPE, N=17), **kw)
+    st["diff2"][:] = 40.0
+    be = hip.RomsHip(st)
+    try:
+        ref = du.DiaRef(st.b, wet, 3, ntsDIA)
+        acc = _Acc(be, ref, wet)
+        if not wet:
+            m = main3d.Main3D(acc, diags=diags.Diags(st.b, 3, ntsDIA))
+            m.initial()
+            m.run(7)
+        else:
+            # seven times set_diags and the tracer sequence by hand, on fields that differ from call to call (the synthetic
+            # wet/dry masks are not a state the whole step could run from)
+            be.set_diagnostics(diags.Diags(st.b, 3, ntsDIA))
+            rng = np.random.default_rng(11)
+            for k, iic in enumerate(range(1, 8)):
+                st["zeta"][:] = 0.1 * rng.standard_normal(st["zeta"].shape)
+                st["t"][:, :, :, 0, :] *= 1.0 + 1e-3 * rng.standard_normal(st["t"][:, :, :, 0, :].shape)
+                be.to_device(["zeta", "t"])
+                acc.call("set_diags", util.step_idx(iic=iic, kstp=1 + k % 3))
+                for kernel in ("pre_step3d", "t3dmix2", "step3d_t"):
+                    be.call(kernel, util.step_idx(iic=3))
+        be.check_guards()
+    finally:
+        be.close()
+    assert acc.seen == seen
+    assert any(np.abs(a).max() > 0.0 for a in ref.trc.values()) and np.abs(ref.avgzeta).max() > 0.0
+    assert not wet or (ref.cnt.max() == 3.0 and (ref.cnt == 0.0).any())
+
+
+def test_boundary_points_of_a_closed_basin_follow_the_recurrence():
+    """nothing rewrites iTrate at the points of a physical boundary between steps: step3d_t.F:1598-1611 as written
+    leaves t(nnew) minus the previous step's value there (zero before the first step)"""
+    st = ana.make_tile("UPWELLING", perturb=1.0, overrides=dict(SHAPE, N=17, EWperiodic=False))
+    b = st.b
+    assert not b.EWperiodic and b.IstrR == 0 and b.IendR == b.Lm + 1
+    edge = np.zeros((st.ni, st.nj), dtype=bool)
+    edge[st.I(b.IstrR, b.IendR), st.J(b.JstrR, b.JendR)] = True
+    edge[st.I(b.Istr, b.Iend), st.J(b.Jstr, b.Jend)] = False
+    be = hip.RomsHip(st)
+    try:
+        m = main3d.Main3D(be, diags=diags.Diags(b, 1))
+        m.initial()
+        prev = np.zeros((st.ni, st.nj, b.N, b.NT))
+        for _ in range(3):
+            m.step()
+            be.to_host(["t"])
+            rate = _fetch(be, st)["iTrate"]
+            want = st["t"][:, :, :, m.s.nnew - 1, :] - prev
+            assert np.array_equal(rate[edge], want[edge])
+            assert np.abs(rate[edge]).max() > 0.0
+            prev = rate
+        be.check_guards()
+    finally:
+        be.close()
+
+
+@pytest.mark.parametrize("variant", ["", "basin"], ids=["channel", "basin"])
+def test_two_tiles_equal_one_tile_on_owned_points(tmp_path, variant):
+    """2 x 1 tiles over the relay: every plane of DiaTwrk and DiaTrc and avgzeta, bit for bit on IstrR:IendR, JstrR:JendR of
+    each tile (the planes take no exchange; the basin has the iTrate recurrence at the physical edges only)"""
+    import mp_gpu_diags_worker as worker
+    world, ntI, ntJ = 2, 2, 1
+    st = worker.tiled_state(variant)
+    be = hip.RomsHip(st)
+    try:
+        want = worker.run(be, st)
+    finally:
+        be.close()
+    assert len(want) == 1 + 2 * 9 * st.b.NT and all(np.abs(a).max() > 0.0 for a in want.values())
+    port = _free_port()
+    env = dict(os.environ, OMP_NUM_THREADS="1")
+    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "mp_gpu_diags_worker.py"), str(r), str(world), str(ntI),
+                               str(ntJ), str(port), str(tmp_path), variant], env=env) for r in range(world)]
+    try:
+        for p in procs:
+            assert p.wait(timeout=600) == 0
+    finally:
+        for p in procs:
+            if p.poll() is None:
+                p.kill()
+    gb = st.b
+    seen = 0
+    for r in range(world):
+        d = np.load(os.path.join(tmp_path, f"tile{r}.npz"))
+        IstrR, IendR, JstrR, JendR, LBi, LBj, UBi = [int(x) for x in d["bounds"]]
+        seen += (IendR - IstrR + 1) * (JendR - JstrR + 1)
+        for key, glob in want.items():
+            own = d[key][IstrR - LBi:IendR - LBi + 1, JstrR - LBj:JendR - LBj + 1]
+            assert np.array_equal(own, glob[IstrR - gb.LBi:IendR - gb.LBi + 1, JstrR - gb.LBj:JendR - gb.LBj + 1]), (key, r)
+    assert seen == (gb.IendR - gb.IstrR + 1) * (gb.JendR - gb.JstrR + 1)          # the tiles' owned points cover the grid
+
+
+# ---------------------------------------------------------------------------------------------- 4. refusals --
+def _with(st, **kw):
+    st = st.copy()
+    st.p = type(st.p).from_buffer_copy(st.p)
+    for k, v in kw.items():
+        if k in ("Hadv", "Vadv"):
+            for it in range(st.b.NT):
+                getattr(st.p, k)[it] = abi.ADV[v]
+        else:
+            setattr(st.p, k, v)
+    return st
+
+
+def test_refusals_name_the_option_and_leave_the_library_usable():
+    lib = hip.load()
+    st0 = _state(17)
+    s = util.step_idx()
+    cases = [(dict(Hadv="MPDATA", Vadv="MPDATA"), b"MPDATA"), (dict(Hadv="HSIMT", Vadv="HSIMT"), b"HSIMT"),
+             (dict(ts_dif4=1), b"TS_DIF4"), (dict(mix_s_ts=0, mix_geo_ts=1), b"rotated"), (dict(mix_s_ts=0, mix_iso_ts=1), b"rotated"),
+             (dict(point_sources=1), b"point sources"), (dict(point_sources=2), b"point sources")]
+    for kw, word in cases:
+        be = hip.RomsHip(_with(st0, **kw))
+        try:
+            assert lib.roms_hip_set_diagnostics(3, 1, 1, 0) != 0
+            msg = lib.roms_hip_last_error()
+            assert word in msg and b"diagnostics" in msg, msg
+            buf = np.zeros(st0.ni * st0.nj * st0.b.N)
+            assert lib.roms_hip_get_diagnostic(0, 1, 0, buf.ctypes.data, buf.size) != 0      # nothing was allocated
+            be.call("set_diags", s)                                                          # off: returns 0
+            be.check_guards()
+        finally:
+            be.close()
+    # the parameters change after the diagnostics were switched on: refused at the step
+    st = st0.copy()
+    be = hip.RomsHip(st)
+    try:
+        be.set_diagnostics(diags.Diags(st.b, 3))
+        bad = _with(st, ts_dif4=1)
+        assert lib.roms_hip_set_params(C.byref(bad.p)) == 0
+        with pytest.raises(RuntimeError, match="TS_DIF4"):
+            be.call("pre_step3d", s)
+        with pytest.raises(RuntimeError, match="TS_DIF4"):
+            be.call("step3d_t", s)
+        ndt6 = _with(st, ts_dif2=0)
+        assert lib.roms_hip_set_params(C.byref(ndt6.p)) == 0
+        with pytest.raises(RuntimeError, match="NDT"):
+            be.call("step3d_t", s)
+        assert lib.roms_hip_set_params(C.byref(st.p)) == 0
+        # ids: a term of another NDT, a bad id, a wrong size
+        be.set_diagnostics(None)
+        assert lib.roms_hip_set_params(C.byref(ndt6.p)) == 0
+        be.set_diagnostics(diags.Diags(st.b, 3))
+        with pytest.raises(RuntimeError, match="iTxdif is not a term"):
+            be.get_diagnostic("iTxdif")
+        buf = np.zeros(5)
+        assert lib.roms_hip_get_diagnostic(diags.DIA_ID["iTrate"], 1, 0, buf.ctypes.data, buf.size) != 0
+        assert b"doubles" in lib.roms_hip_last_error() and not buf.any()
+        assert lib.roms_hip_get_diagnostic(diags.DIA_COUNT, 1, 0, buf.ctypes.data, buf.size) != 0
+        assert lib.roms_hip_get_diagnostic(99, 1, 0, buf.ctypes.data, buf.size) != 0
+        with pytest.raises(RuntimeError, match="wet_dry"):
+            be.get_diagnostic("rmask_dia")
+        assert lib.roms_hip_set_diagnostics(-1, 1, 1, 0) != 0 and b"nDIA < 0" in lib.roms_hip_last_error()
+        kept = be.diags
+        with pytest.raises(RuntimeError, match="nDIA < 0"):
+            be.set_diagnostics(diags.Diags(st.b, -1))
+        assert be.diags is kept                                                              # the Python side agrees
+        assert be.get_diagnostic("iTrate").shape == (st.ni, st.nj, st.b.N)                   # the set in force stays
+        assert lib.roms_hip_set_params(C.byref(st.p)) == 0
+    finally:
+        be.close()
+    # nDIA = 0 releases the arrays; the next step runs the kernels of a context that never had diagnostics
+    util.hz_weighted_tnew(st0)
+    out = {}
+    for key in ("released", "never"):
+        st = st0.copy()
+        be = hip.RomsHip(st)
+        try:
+            if key == "released":
+                be.set_diagnostics(diags.Diags(st.b, 3))
+                be.set_diagnostics(None)
+                assert lib.roms_hip_get_diagnostic(0, 1, 0, None, 0) != 0 and b"not switched on" in lib.roms_hip_last_error()
+            be.call("step3d_t", s)
+            be.to_host()
+            be.check_guards()
+        finally:
+            be.close()
+        out[key] = st
+    assert np.array_equal(out["released"]["t"], out["never"]["t"])
+    assert not np.array_equal(out["never"]["t"], st0["t"])
