@@ -4,7 +4,7 @@
 //   flux formulas     hflux<>, vflux<>
 //   column frame      tile_column(), column_walls(), tracer_level(), column_fields(), tracer_akt()
 //   whole column      a4_slopes<>(), spline_w<>()
-//   one level         cell_faces<>(), vflux_level<>(), thomas_row()
+//   one level         cell_faces<>(), vflux_level<>(), vstart_flux<>(), thomas_row()
 //   host              adv_pair(), adv_run_length(), kernel_for_n()
 // The device functions take loaded values: which load is issued when stays the kernel's business.
 #pragma once
@@ -228,6 +228,78 @@ __device__ __forceinline__ double vflux_level(int k, int N, double Wk, double tk
     return vflux<VADV>(k, N, Wk, tkm1, tk, tkp1, tkp2, cfk, cfk1);
   }
 }
+// The explicit vertical flux of the corrector's start, pre_step3d.F:837-890: FC(0) = dt*btflx, FC(N) = dt*stflx,
+// between them cff3 * Akt * dt/dz (cff3 = dt*(1-lambda)), the KPP non-local term and the solar term (lmd_swfrac.F:6)
+// with dt*srflx [*rmask_wet under WET_DRY, :876-878] formed first, left to right.  t(nnew) = Hz*t(nstp) + (FC(k) -
+// FC(k-1)) (:894-898) is then the caller's: k_pre_t stores it, k_t3dmix_geo<0, ISO, false, true> adds its own term first.
+struct VStart {
+  double dt, cff3, dsrf, zwN, fac1, fac2, fac3;
+  bool nonlocal, solar;
+  gcd_t Akt, AktN, ghats, z_r, z_w;
+  int itrc;
+};
+// the column's constants; c0 = index of (i,j,1)
+__device__ __forceinline__ VStart vstart_column(const RomsDev *__restrict__ c, int itrc, long c0, long nij, long n3w)
+{
+  const roms_params_t &p = c->p;
+  const roms_bounds_t &b = c->b;
+  VStart v;
+  v.dt = p.dt;
+  v.cff3 = p.dt * (1.0 - p.lambda);
+  v.nonlocal = p.lmd_nonlocal && itrc <= b.NAT;
+  v.solar = p.solar_source && itrc == 1;
+  v.Akt = tracer_akt(c, itrc, n3w);
+  v.ghats = (gcd_t)(c->F.ghats + (long)((itrc <= b.NAT ? itrc : 1) - 1) * n3w);
+  v.AktN = (gcd_t)(c->F.Akt + (long)((itrc <= b.NAT ? itrc : 1) - 1) * n3w);   // Akt(..,itrc) of the non-local term
+  v.z_r = (gcd_t)(c->F.z_r);
+  v.z_w = (gcd_t)(c->F.z_w);
+  const double srf = GF(srflx)[c0];
+  v.dsrf = p.wet_dry ? (p.dt * srf) * GF(rmask_wet)[c0] : p.dt * srf;
+  v.zwN = v.z_w[c0 + (long)b.N * nij];
+  v.fac1 = -1.0 / p.swfrac_mu1; v.fac2 = -1.0 / p.swfrac_mu2; v.fac3 = p.swfrac_r1;
+  v.itrc = itrc;
+  return v;
+}
+// what FC(k), k < N, reads at W-level k (cku = index of (i,j,k+1)): Akt and ghats of the non-local term, z_w of the
+// solar term -- loaded values, so that a kernel may issue the loads a level ahead
+struct VStartIn { double akn, gh, zwk; };
+__device__ __forceinline__ VStartIn vstart_load(const VStart &v, long cku)
+{
+  VStartIn r{0.0, 0.0, 0.0};
+  if (v.nonlocal) { r.akn = v.AktN[cku]; r.gh = v.ghats[cku]; }
+  if (v.solar) r.zwk = v.z_w[cku];
+  return r;
+}
+// FC(0), and FC(k), k = 1..N; cku = index of (i,j,k+1), in = vstart_load() of the level (unused at k = N), tk / tkp1 = t(nstp) of levels k and k+1, zr_k = z_r(k) carried by the
+// caller (set to z_r(1) before the sweep when v.cff3 != 0).  EXPL = false: the caller has checked lambda = 1, where
+// cff3 * (...) = +-0 -- z_r, the division and (without the non-local term) Akt are not read
+__device__ __forceinline__ double vstart_bottom(const RomsDev *__restrict__ c, const VStart &v, long c0, long nij)
+{
+  return v.dt * GF(btflx)[c0 + (long)(v.itrc - 1) * nij];
+}
+template <bool EXPL>
+__device__ __forceinline__ double vstart_flux(const RomsDev *__restrict__ c, const VStart &v, int k, int N, long c0, long nij,
+                                              long cku, const VStartIn &in, double tk, double tkp1, double &zr_k)
+{
+  if (k == N) return v.dt * GF(stflx)[c0 + (long)(v.itrc - 1) * nij];
+  double FDk = 0.0;
+  if constexpr (EXPL) {
+    if (v.cff3 != 0.0) {
+      const double zr_k1 = v.z_r[cku];
+      const double cz = 1.0 / (zr_k1 - zr_k);
+      FDk = v.cff3 * cz * v.Akt[cku] * (tkp1 - tk);
+      zr_k = zr_k1;
+    }
+  }
+  if (v.nonlocal) FDk = FDk - v.dt * in.akn * in.gh;
+  if (v.solar) {
+    const double Z = v.zwN - in.zwk;
+    const double swdk = exp(Z * v.fac1) * v.fac3 + exp(Z * v.fac2) * (1.0 - v.fac3);
+    FDk = FDk + v.dsrf * swdk;
+  }
+  return FDk;
+}
+
 // Row k-1 of the forward elimination of the implicit vertical diffusion in spline form, step3d_t.F:1376-1410, formed
 // while the upward sweep is at level k: *_m1 = level k-1, akt_m2 / akt_m1 / akt_0 = Akt(k-2) / Akt(k-1) / Akt(k),
 // t_m1 / t_0 = the advected tracer of the two levels, CFm / DCm = CF(k-2) / DC(k-2); sets CF(k-1), DC(k-1).

@@ -10,8 +10,10 @@
 // One thread per (i,j) column sweeping k upward.  The reference's two-slab
 // buffers (level k and k+1 of dZdx,dTdx,dZde,dTde, W-levels k-1 and k of dTdz,
 // FS) become register sliding windows, so the rotated operator needs one read
-// of t(nrhs), z_r, Hz and one read-modify-write of t(nnew) per tracer.
+// of t(nrhs), z_r, Hz and one read-modify-write of t(nnew) per tracer -- inside roms_hip_rhs3d (START) one write of
+// t(nnew) and no read: the kernel forms the start of the corrector that k_pre_t would have stored.
 #include "roms_dev.h"
+#include "advect.h"
 
 int roms_entry_check(const char *name);
 
@@ -62,10 +64,15 @@ __device__ __forceinline__ void lap4_store(const roms_bounds_t &b, const Lap4 &L
 // of the potential density in the place of those of z_r, the vertical tracer difference scaled by
 // -1 / MAX(pden(k) - pden(k+1), eps), MIN and MAX exchanged, and the vertical flux times that scale times dz.
 // STAB (MODE 0 / 1): TS_MIX_STABILITY -- t(nstp) is read beside t(nrhs) and every tracer difference is tdiff<true>.
-template <int MODE, bool ISO, bool STAB = false>
+// START (MODE 0 without STAB, inside roms_hip_rhs3d: rhs3d_fuses_tstart()): the kernel behind k_pre_t<.., DEFER>.  With
+// nrhs = nstp and lambda = 1 it forms the start of the corrector itself, pre_step3d.F:837-898 -- Hz*t(nstp) from the T0
+// and hz0 it holds, the explicit vertical flux from vstart_flux() of advect.h -- and stores (hzt + dFD) + cff4, the
+// sums t3dmix2_geo.h:408 forms, without loading t(nnew).
+template <int MODE, bool ISO, bool STAB = false, bool START = false>
 __global__ void __launch_bounds__(BLK_X *BLK_Y)
 k_t3dmix_geo(const RomsDev *__restrict__ c, int nrhs, int nnew, Lap4 L)
 {
+  static_assert(!START || (MODE == 0 && !STAB), "the corrector's start goes with t3dmix2 alone");
   DEV_PROLOGUE(c)
   const int ilo = MODE == 1 ? L.i0 : b.Istr, ihi = MODE == 1 ? L.i1 : b.Iend;
   const int jlo = MODE == 1 ? L.j0 : b.Jstr, jhi = MODE == 1 ? L.j1 : b.Jend;
@@ -118,12 +125,16 @@ k_t3dmix_geo(const RomsDev *__restrict__ c, int nrhs, int nnew, Lap4 L)
   double dzm_b, dz0_b, dzp_b, dzs_b, dzn_b;
   double FS_a = 0.0, FS_b;
   double fsf_b = 0.0;                      // ISO: FS(i,j,k2) = scale * dz before the flux is formed (:303)
-  // Software pipeline (cf. k_step3d_t_pipe): the 16 loads an iteration consumes -- T and z_r of level
+  // Software pipeline (cf. k_step3d_t_pipe): the 16 loads an iteration consumes (START: up to 3 more) -- T and z_r of level
   // k+1 at the five columns, Hz of level k at the five columns, t(nnew) of level k -- are issued one
   // iteration ahead, so their latency overlaps the arithmetic of the previous level.
+  VStart vs{};                               // START: the explicit vertical flux of the corrector's start
+  double FDprev = 0.0, zr_unused = 0.0;
+  if constexpr (START) { vs = vstart_column(c, itrc, c0, nij, n3w); FDprev = vstart_bottom(c, vs, c0, nij); }
   struct LvIn { double Tm1, T01, Tp1, Ts1, Tn1, Zm1, Z01, Zp1, Zs1, Zn1, hz0, hzm, hzp, hzs, hzn, tn, zz1;
                 double Sm1, S01, Sp1, Ss1, Sn1;
-                double zzm1, zzp1, zzs1, zzn1; };          // TS_MIX_MIN_STRAT: z_r of the four neighbour columns
+                double zzm1, zzp1, zzs1, zzn1;             // TS_MIX_MIN_STRAT: z_r of the four neighbour columns
+                double akn, gh, zwk; };                    // START: what FC(k) of the explicit vertical flux reads (VStartIn)
   const gcd_t gT = (gcd_t)T, gS = (gcd_t)S, gZ = (gcd_t)z_r, gHz = (gcd_t)Hz;
   const gd_t gtn = (gd_t)tn;
   auto load_level = [&](int k) {
@@ -135,7 +146,10 @@ k_t3dmix_geo(const RomsDev *__restrict__ c, int nrhs, int nnew, Lap4 L)
     else L.Sm1 = L.S01 = L.Sp1 = L.Ss1 = L.Sn1 = 0.0;
     L.Zm1 = gZ[cu - 1]; L.Z01 = gZ[cu]; L.Zp1 = gZ[cu + 1]; L.Zs1 = gZ[cu - ni]; L.Zn1 = gZ[cu + ni];
     L.hz0 = gHz[ck]; L.hzm = gHz[ck - 1]; L.hzp = gHz[ck + 1]; L.hzs = gHz[ck - ni]; L.hzn = gHz[ck + ni];
-    L.tn = gtn[ck];
+    if constexpr (START) L.tn = 0.0; else L.tn = gtn[ck];
+    L.akn = L.gh = L.zwk = 0.0;
+    if constexpr (START)
+      if (k < N) { const VStartIn in = vstart_load(vs, ck + nij); L.akn = in.akn; L.gh = in.gh; L.zwk = in.zwk; }
     if constexpr (ISO) L.zz1 = ((gcd_t)zz)[cu]; else L.zz1 = 0.0;
     L.zzm1 = L.zzp1 = L.zzs1 = L.zzn1 = 0.0;
     if (minstrat) {
@@ -160,6 +174,7 @@ k_t3dmix_geo(const RomsDev *__restrict__ c, int nrhs, int nnew, Lap4 L)
   LvIn cur = load_level(1);
   for (int k = 1; k <= N; k++) {
     const long ck = c0 + (long)(k - 1) * nij;
+    const double Tk = T0;                    // t(nrhs) of the own cell at level k
     LvIn nxt = cur;
     if (k < N) nxt = load_level(k + 1);
     zx0_a = zx0_b; zx1_a = zx1_b; tx0_a = tx0_b; tx1_a = tx1_b;
@@ -228,7 +243,13 @@ k_t3dmix_geo(const RomsDev *__restrict__ c, int nrhs, int nnew, Lap4 L)
       const double cff2 = cdt * (FE1 - FE0);
       const double cff3 = dt * (FS_b - FS_a);
       const double cff4 = cff1 + cff2 + cff3;
-      if constexpr (MODE == 0) gtn[ck] = cur.tn + cff4;
+      if constexpr (START) {
+        const VStartIn in{cur.akn, cur.gh, cur.zwk};
+        const double FDk = vstart_flux<false>(c, vs, k, N, c0, nij, ck + nij, in, Tk, 0.0, zr_unused);
+        const double hzt = hz0 * Tk, dFD = FDk - FDprev;
+        gtn[ck] = (hzt + dFD) + cff4;
+        FDprev = FDk;
+      } else if constexpr (MODE == 0) gtn[ck] = cur.tn + cff4;
       else gtn[ck] = cur.tn - cff4;            // t3dmix4_geo.h:767
     }
     cur = nxt;
@@ -344,14 +365,19 @@ k_t3dmix4_s(const RomsDev *__restrict__ c, int nrhs, int nnew, Lap4 L)
 
 }  // namespace
 
-static int t3dmix2_launch(const roms_step_idx_t *s)
+static int t3dmix2_launch(const roms_step_idx_t *s, bool fused)
 {
   const roms_bounds_t &b = g_ctx.b;
   const dim3 grid = grid_tile_tracer(b.Iend - b.Istr + 1, b.Jend - b.Jstr + 1, b.NT);
   const bool stab = g_ctx.p.ts_mix_stability != 0;       // TS_MIX_STABILITY
   Lap4 L{};
   L.nstp = s->nstp;
-  if (g_ctx.p.mix_iso_ts) {
+  if (fused) {                                           // rhs3d_fuses_tstart(): rotated mixing, no STAB, no diagnostics
+    if (stab || dia_on() || !(g_ctx.p.mix_iso_ts || g_ctx.p.mix_geo_ts))
+      return roms_fail("roms_hip_t3dmix2", "internal: the fused start of t(nnew) was asked for where it is not built");
+    if (g_ctx.p.mix_iso_ts) hipLaunchKernelGGL((k_t3dmix_geo<0, true, false, true>), grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, L);
+    else hipLaunchKernelGGL((k_t3dmix_geo<0, false, false, true>), grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, L);
+  } else if (g_ctx.p.mix_iso_ts) {
     if (stab) hipLaunchKernelGGL((k_t3dmix_geo<0, true, true>), grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, L);
     else hipLaunchKernelGGL((k_t3dmix_geo<0, true>), grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, L);
   } else if (g_ctx.p.mix_geo_ts) {
@@ -369,7 +395,7 @@ static int t3dmix2_launch(const roms_step_idx_t *s)
   return 0;
 }
 
-extern "C" int roms_hip_t3dmix2(const roms_step_idx_t *s)
+int t3dmix2_entry(const roms_step_idx_t *s, bool fused)
 {
   int rc = roms_entry_check("roms_hip_t3dmix2");
   if (rc) return rc;
@@ -377,8 +403,10 @@ extern "C" int roms_hip_t3dmix2(const roms_step_idx_t *s)
   if (dia_on() && !g_ctx.p.ts_dif2)
     return roms_fail("roms_hip_t3dmix2", "diagnostics: ts_dif2 is off, the iT?dif terms have no planes (NDT = 6)");
   ScopedTimer tm("t3dmix2");
-  return t3dmix2_launch(s);
+  return t3dmix2_launch(s, fused);
 }
+
+extern "C" int roms_hip_t3dmix2(const roms_step_idx_t *s) { return t3dmix2_entry(s, false); }
 
 extern "C" int roms_hip_t3dmix4(const roms_step_idx_t *s)
 {

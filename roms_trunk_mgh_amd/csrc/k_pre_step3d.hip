@@ -11,9 +11,11 @@
 //   k_pre_uv  one thread per column: start of u,v(nnew) with the AB3 terms
 //             5/12 ru(nrhs) - 16/12 ru(3-nrhs) and surface/bottom stress
 //             (:1012-1120).
-// Algorithmic traffic (BENCHMARK, NT=2): per tracer read t(nstp), t(nnew), Akt,
-// ghats; write t(3), t(nnew) = 48 B; shared Huon,Hvom,W,Hz,z_r,z_w = 48 B; momentum
+// Algorithmic traffic (BENCHMARK, NT=2), the entry on its own: per tracer read t(nstp), t(nnew), Akt,
+// ghats; write t(3), t(nnew) = 48 B; shared Huon,Hvom,W,Hz,z_r,z_w = 48 B, read once per tracer; momentum
 // part reads u,v(nstp), ru,rv x2, Akv, writes u,v(nnew) = 72 B.
+// Inside roms_hip_rhs3d with rotated mixing (DEFER, NTR = 2): per tracer read t(nstp), t(nnew), write t(3) = 24 B;
+// shared Huon,Hvom,W,Hz = 32 B read once per pair of tracers; Akt, ghats, z_w and the write of t(nnew) are k_t3dmix_geo's.
 #include "roms_dev.h"
 #include "advect.h"
 
@@ -24,23 +26,27 @@ namespace {
 // MASK: MASKING applications, first differences times umask / vmask of their face (pre_step3d.F:398, :463)
 // DIA (DIAGNOSTICS_TS, pre_step3d.F:899-902): the two summands of the corrector's start go to DiaTwrk(iTrate) and
 // DiaTwrk(iTvdif) (m Tunits; k_step3d_t_pipe turns them into Tunits).  Instantiated at NMAX = ROMS_MAXN only.
-template <int HADV, int VADV, int NMAX, bool MASK, bool DIA = false>
+// DEFER (inside roms_hip_rhs3d, rhs3d_fuses_tstart()): the start of the corrector is left to k_t3dmix_geo<0, ISO, false,
+// true>, which stores it together with its own term -- t(nnew) is read here (the cff2 term of t(3)) and not written; Akt,
+// ghats, z_w and the surface / bottom fluxes are not read.  Both loops cover Istr:Iend, Jstr:Jend on every tile
+// (pre_step3d.F:837-898, t3dmix2_geo.h:401-408), and t3dbc_tile / the exchanges at the end of the predictor work on
+// level 3 alone (pre_step3d.F:1131-1149).
+// NTR = 2: the thread carries the tracers itrc and itrc + 1 of one column; Huon, Hvom, W, Hz of a level are loaded and
+// the artificial-continuity reciprocal DC is formed once for both.  For the schemes without whole-column arrays.
+template <int HADV, int VADV, int NMAX, bool MASK, bool DIA = false, bool DEFER = false, int NTR = 1>
 __global__ void __launch_bounds__(BLK_X *BLK_Y)
 k_pre_t(const RomsDev *__restrict__ c, int nstp, int nnew, int first_step, int itrc0, int ntr)
 {
+  static_assert(NTR == 1 || (VADV != ADV_A4 && VADV != ADV_SPLINES && !DIA), "pairs: no whole-column arrays, no diagnostics");
+  static_assert(!(DIA && DEFER), "diagnostics keep the two kernels");
   DEV_PROLOGUE(c)
   const TileCol tc = tile_column(b, itrc0, ntr);
   if (!tc.valid) return;
-  const int i = tc.i, j = tc.j, itrc = tc.itrc;
+  const int i = tc.i, j = tc.j;
+  const int itrc1 = itrc0 + NTR * (tc.itrc - itrc0);       // the first tracer of the thread
   const roms_params_t &p = c->p;
   const double dt = p.dt;
-  const gcd_t ts = (gcd_t)tracer_level(c, nstp, itrc, n3r);
-  const gd_t t3 = (gd_t)tracer_level(c, 3, itrc, n3r);
-  const gd_t tn = (gd_t)tracer_level(c, nnew, itrc, n3r);
   const ColFields f = column_fields(c);
-  const gcd_t z_r = (gcd_t)(c->F.z_r);
-  const gcd_t z_w = (gcd_t)(c->F.z_w);
-  const gcd_t Akt = tracer_akt(c, itrc, n3w);
   const long c0 = I2(i, j);
   const Walls wl = column_walls(c, i, j);
   // time-stepping weights, pre_step3d.F:586-600
@@ -54,87 +60,90 @@ k_pre_t(const RomsDev *__restrict__ c, int nstp, int nnew, int first_step, int i
   else { cff = (1.0 - Gamma) * dt; cff1 = 0.5 + Gamma; cff2 = 0.5 - Gamma; }
   const double cpp = cff * GF(pm)[c0] * GF(pn)[c0];
   const double cppv = (first_step ? 0.5 * dt : (1.0 - GammaV) * dt) * GF(pm)[c0] * GF(pn)[c0];
-  // explicit vertical flux pieces
-  const double cff3 = dt * (1.0 - p.lambda);
-  const bool nonlocal = p.lmd_nonlocal && itrc <= b.NAT;
-  const bool solar = p.solar_source && itrc == 1;
-  const gcd_t ghats = (gcd_t)(c->F.ghats + (long)((itrc <= b.NAT ? itrc : 1) - 1) * n3w);
-  const gcd_t AktN = (gcd_t)(c->F.Akt + (long)((itrc <= b.NAT ? itrc : 1) - 1) * n3w);   // Akt(..,itrc) of the non-local term
-  const double srf = GF(srflx)[c0];
-  // dt*srflx [*rmask_wet under WET_DRY, pre_step3d.F:873-878] -- the product the reference forms first, left to right
-  const double dsrf = c->p.wet_dry ? (dt * srf) * GF(rmask_wet)[c0] : dt * srf;
-  const double zwN = z_w[c0 + (long)N * nij];
-  const double fac1 = -1.0 / p.swfrac_mu1, fac2 = -1.0 / p.swfrac_mu2, fac3 = p.swfrac_r1;
 
+  // per tracer: the three time levels, the explicit vertical flux of the corrector's start (advect.h) and the k-window
+  gcd_t ts[NTR];
+  gd_t t3[NTR], tn[NTR];
+  VStart vs[NTR];
+  double zr_k[NTR], FDprev[NTR];                              // z_r(k) of the explicit flux; diffusive FC(k-1)
+  double tkm1[NTR], tk[NTR], tkp1[NTR], tkp2[NTR];
+  double FCprev[NTR];                                         // advective FC(k-1)
   // vertical schemes that need the whole column first
   double a4cf[(VADV == ADV_A4) ? NMAX + 2 : 1];
   double spl[(VADV == ADV_SPLINES) ? NMAX + 1 : 1];
-  if constexpr (VADV == ADV_A4) a4_slopes<NMAX>(ts, c0, nij, N, a4cf);
-  if constexpr (VADV == ADV_SPLINES) spline_w<true, NMAX>(ts, f.Hz, f.W, c0, nij, N, spl);
+#pragma unroll
+  for (int q = 0; q < NTR; q++) {
+    ts[q] = (gcd_t)tracer_level(c, nstp, itrc1 + q, n3r);
+    t3[q] = (gd_t)tracer_level(c, 3, itrc1 + q, n3r);
+    tn[q] = (gd_t)tracer_level(c, nnew, itrc1 + q, n3r);
+    if constexpr (!DEFER) {
+      vs[q] = vstart_column(c, itrc1 + q, c0, nij, n3w);
+      FDprev[q] = vstart_bottom(c, vs[q], c0, nij);
+      zr_k[q] = (vs[q].cff3 != 0.0) ? vs[q].z_r[c0] : 0.0;
+    }
+    tkm1[q] = 0.0; tk[q] = ts[q][c0]; tkp1[q] = (N >= 2) ? ts[q][c0 + nij] : 0.0;
+    FCprev[q] = 0.0;
+  }
+  if constexpr (VADV == ADV_A4) a4_slopes<NMAX>(ts[0], c0, nij, N, a4cf);
+  if constexpr (VADV == ADV_SPLINES) spline_w<true, NMAX>(ts[0], f.Hz, f.W, c0, nij, N, spl);
 
   const bool src_cell = c->src.n > 0 && src_cell_any(c, c0, ni);      // LuvSrc: a face of this cell is a source face
-  double tkm1 = 0.0, tk = ts[c0], tkp1 = (N >= 2) ? ts[c0 + nij] : 0.0, tkp2;
-  double FCprev = 0.0;                                        // advective FC(k-1)
-  double FDprev = dt * GF(btflx)[c0 + (long)(itrc - 1) * nij]; // diffusive FC(0)
   double w_km1 = f.W[c0];
-  double zr_k = (cff3 != 0.0) ? z_r[c0] : 0.0;
   for (int k = 1; k <= N; k++) {
     const long ck = c0 + (long)(k - 1) * nij;
-    tkp2 = (k + 2 <= N) ? ts[ck + 2 * nij] : 0.0;
-    // ---- horizontal fluxes of t(nstp) ----
-    HStencil s;
-    s.xm1 = ts[ck - 1]; s.xp1 = ts[ck + 1];
-    s.xm2 = wl.w ? 0.0 : ts[ck - 2];
-    s.xp2 = wl.e ? 0.0 : ts[ck + 2];
-    s.ym1 = ts[ck - ni]; s.yp1 = ts[ck + ni];
-    s.ym2 = wl.s ? 0.0 : ts[ck - 2 * ni];
-    s.yp2 = wl.n ? 0.0 : ts[ck + 2 * ni];
-    s.hu0 = f.Huon[ck]; s.hu1 = f.Huon[ck + 1];
-    s.hv0 = f.Hvom[ck]; s.hv1 = f.Hvom[ck + ni];
-    Faces fx = cell_faces<HADV, MASK>(tk, s, wl, c, c0, ni);
-    if (src_cell)                                    // LuvSrc, pre_step3d.F:530-553
-      src_cell_fluxes<true>(c, c0, ck, ni, k, itrc, nullptr, fx.FXi, fx.FXip1, fx.FEj, fx.FEjp1);
-    const double hz = f.Hz[ck];
-    const double tnn = tn[ck];
-    double t3v = hz * (cff1 * tk + cff2 * tnn) - cpp * (fx.FXip1 - fx.FXi + fx.FEjp1 - fx.FEj);
-    // ---- vertical advective flux through the top face ----
-    const double w_k = f.W[ck + nij];
-    const double FCk = vflux_level<VADV>(k, N, w_k, tkm1, tk, tkp1, tkp2, spl, a4cf);
-    // ---- artificial continuity, pre_step3d.F:893-915 ----
-    const double DCk = 1.0 / (hz - cppv * (s.hu1 - s.hu0 + s.hv1 - s.hv0 + (w_k - w_km1)));
-    t3v = DCk * (t3v - cppv * (FCk - FCprev));
-    t3[ck] = t3v;
-    // ---- start of the corrector: explicit vertical flux, pre_step3d.F:917-1010 ----
-    double FDk;
-    if (k == N) FDk = dt * GF(stflx)[c0 + (long)(itrc - 1) * nij];
-    else {
-      if (cff3 != 0.0) {
-        const double zr_k1 = z_r[ck + nij];
-        const double cz = 1.0 / (zr_k1 - zr_k);
-        FDk = cff3 * cz * Akt[ck + nij] * (tkp1 - tk);
-        zr_k = zr_k1;
-      } else {
-        // lambda = 1 (fully implicit vertical diffusion, every shipped application): the explicit flux is
-        // cff3 * (...) = +-0; z_r, the division and (without the non-local term) Akt are not needed
-        FDk = 0.0;
-      }
-      if (nonlocal) FDk = FDk - dt * AktN[ck + nij] * ghats[ck + nij];
-      if (solar) {
-        const double Z = zwN - z_w[ck + nij];
-        const double swdk = exp(Z * fac1) * fac3 + exp(Z * fac2) * (1.0 - fac3);
-        FDk = FDk + dsrf * swdk;
-      }
+    // ---- the loads of the level: with two tracers both tracers' before the first store.  (The tracer-independent
+    // loads and t(nnew) of a single tracer stay where the one-tracer kernel has always had them, in the first pass of
+    // the loop below: issued up here they cost it 24 VGPRs and a wave.) ----
+    HStencil s[NTR];
+    double tnn[NTR];
+#pragma unroll
+    for (int q = 0; q < NTR; q++) {
+      const gcd_t t = ts[q];
+      tkp2[q] = (k + 2 <= N) ? t[ck + 2 * nij] : 0.0;
+      s[q].xm1 = t[ck - 1]; s[q].xp1 = t[ck + 1];
+      s[q].xm2 = wl.w ? 0.0 : t[ck - 2];
+      s[q].xp2 = wl.e ? 0.0 : t[ck + 2];
+      s[q].ym1 = t[ck - ni]; s[q].yp1 = t[ck + ni];
+      s[q].ym2 = wl.s ? 0.0 : t[ck - 2 * ni];
+      s[q].yp2 = wl.n ? 0.0 : t[ck + 2 * ni];
+      if constexpr (NTR > 1) tnn[q] = tn[q][ck];
     }
-    const double hzt = hz * tk, dFD = FDk - FDprev;
-    tn[ck] = hzt + dFD;
-    if constexpr (DIA) {
-      DIA_PLANE(c, DIA_iTrate, itrc, n3r)[ck] = hzt;
-      DIA_PLANE(c, DIA_iTvdif, itrc, n3r)[ck] = dFD;
+    const double hu0 = f.Huon[ck], hu1 = f.Huon[ck + 1], hv0 = f.Hvom[ck], hv1 = f.Hvom[ck + ni];
+    double hz, w_k, DCk;
+#pragma unroll
+    for (int q = 0; q < NTR; q++) {
+      const int itrc = itrc1 + q;
+      // ---- horizontal fluxes of t(nstp) ----
+      s[q].hu0 = hu0; s[q].hu1 = hu1; s[q].hv0 = hv0; s[q].hv1 = hv1;
+      Faces fx = cell_faces<HADV, MASK>(tk[q], s[q], wl, c, c0, ni);
+      if (src_cell)                                    // LuvSrc, pre_step3d.F:530-553
+        src_cell_fluxes<true>(c, c0, ck, ni, k, itrc, nullptr, fx.FXi, fx.FXip1, fx.FEj, fx.FEjp1);
+      if (q == 0) hz = f.Hz[ck];
+      if constexpr (NTR == 1) tnn[q] = tn[q][ck];
+      double t3v = hz * (cff1 * tk[q] + cff2 * tnn[q]) - cpp * (fx.FXip1 - fx.FXi + fx.FEjp1 - fx.FEj);
+      // ---- vertical advective flux through the top face ----
+      if (q == 0) w_k = f.W[ck + nij];
+      const double FCk = vflux_level<VADV>(k, N, w_k, tkm1[q], tk[q], tkp1[q], tkp2[q], spl, a4cf);
+      // ---- artificial continuity, pre_step3d.F:893-915 ----
+      if (q == 0) DCk = 1.0 / (hz - cppv * (hu1 - hu0 + hv1 - hv0 + (w_k - w_km1)));
+      t3v = DCk * (t3v - cppv * (FCk - FCprev[q]));
+      t3[q][ck] = t3v;
+      // ---- start of the corrector: explicit vertical flux, pre_step3d.F:837-898 ----
+      if constexpr (!DEFER) {
+        const VStartIn in = (k < N) ? vstart_load(vs[q], ck + nij) : VStartIn{0.0, 0.0, 0.0};
+        const double FDk = vstart_flux<true>(c, vs[q], k, N, c0, nij, ck + nij, in, tk[q], tkp1[q], zr_k[q]);
+        const double hzt = hz * tk[q], dFD = FDk - FDprev[q];
+        tn[q][ck] = hzt + dFD;
+        if constexpr (DIA) {
+          DIA_PLANE(c, DIA_iTrate, itrc, n3r)[ck] = hzt;
+          DIA_PLANE(c, DIA_iTvdif, itrc, n3r)[ck] = dFD;
+        }
+        FDprev[q] = FDk;
+      }
+      FCprev[q] = FCk;
+      tkm1[q] = tk[q]; tk[q] = tkp1[q]; tkp1[q] = tkp2[q];
     }
-    FDprev = FDk;
-    FCprev = FCk;
     w_km1 = w_k;
-    tkm1 = tk; tk = tkp1; tkp1 = tkp2;
   }
 }
 
@@ -210,31 +219,66 @@ k_pre_uv(const RomsDev *__restrict__ c, int nstp, int nnew, int nrhs, int stage)
   }
 }
 
-template <int HADV, int VADV>
-int launch_pre_t(const roms_step_idx_t *s, int itrc0, int ntr)
+// One launch of k_pre_t<HADV, VADV, ., ., ., DEFER, NTR> over nthr tracers (NTR = 1) or pairs of tracers (NTR = 2)
+// from tracer itrc0 on
+template <int HADV, int VADV, bool DEFER, int NTR>
+int launch_pre_t_n(const roms_step_idx_t *s, int itrc0, int nthr)
 {
   typedef void (*PreKernel)(const RomsDev *, int, int, int, int, int);
   const roms_bounds_t &b = g_ctx.b;
-  const dim3 grid = grid_tile_tracer(b.Iend - b.Istr + 1, b.Jend - b.Jstr + 1, ntr);
+  const dim3 grid = grid_tile_tracer(b.Iend - b.Istr + 1, b.Jend - b.Jstr + 1, nthr);
   const int first = s->iic == s->ntfirst;
   if (b.N > ROMS_MAXN) return roms_fail("roms_hip_pre_step3d", "N > 64 not instantiated");
-  PreKernel kernel = kernel_for_n(b.N, [](auto nm) -> PreKernel { return k_pre_t<HADV, VADV, nm.value, false>; });
-  if constexpr (HADV != ADV_MPDATA)                    // the upstream predictor of MPDATA / HSIMT has no mask
-    if (g_ctx.p.masking)
-      kernel = kernel_for_n(b.N, [](auto nm) -> PreKernel { return k_pre_t<HADV, VADV, nm.value, true>; });
-  if constexpr (HADV != ADV_MPDATA && VADV != ADV_MPDATA)   // (dia_check has refused the upstream predictors)
-    if (dia_on())
-      kernel = g_ctx.p.masking ? k_pre_t<HADV, VADV, ROMS_MAXN, true, true> : k_pre_t<HADV, VADV, ROMS_MAXN, false, true>;
-  hipLaunchKernelGGL(kernel, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nstp, s->nnew, first, itrc0, ntr);
+  PreKernel kernel;
+  if constexpr (NTR == 2) {                              // no whole-column arrays: NMAX is not used
+    kernel = k_pre_t<HADV, VADV, ROMS_MAXN, false, false, DEFER, 2>;
+    if constexpr (HADV != ADV_MPDATA)
+      if (g_ctx.p.masking) kernel = k_pre_t<HADV, VADV, ROMS_MAXN, true, false, DEFER, 2>;
+  } else {
+    kernel = kernel_for_n(b.N, [](auto nm) -> PreKernel { return k_pre_t<HADV, VADV, nm.value, false, false, DEFER>; });
+    if constexpr (HADV != ADV_MPDATA)                    // the upstream predictor of MPDATA / HSIMT has no mask
+      if (g_ctx.p.masking)
+        kernel = kernel_for_n(b.N, [](auto nm) -> PreKernel { return k_pre_t<HADV, VADV, nm.value, true, false, DEFER>; });
+    if constexpr (HADV != ADV_MPDATA && VADV != ADV_MPDATA && !DEFER)   // (dia_check has refused the upstream predictors)
+      if (dia_on())
+        kernel = g_ctx.p.masking ? k_pre_t<HADV, VADV, ROMS_MAXN, true, true> : k_pre_t<HADV, VADV, ROMS_MAXN, false, true>;
+  }
+  hipLaunchKernelGGL(kernel, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nstp, s->nnew, first, itrc0, nthr);
   KERNEL_CHECK("k_pre_t");
   return 0;
+}
+
+// the scheme pairs built with two tracers per thread
+constexpr bool pre_t_pairs(int ha, int va)
+{
+  return (ha == ADV_U3 && va == ADV_C4) || (ha == ADV_C4 && va == ADV_C4) || (ha == ADV_C2 && va == ADV_C2) ||
+         (ha == ADV_MPDATA && va == ADV_MPDATA);
+}
+
+// A run of ntr tracers of one scheme pair from tracer itrc0 on.  fused (see pre_step3d_entry()): pairs of tracers where
+// the pair is built, one single-tracer launch for the rest.  Otherwise single tracers, as ever: with the corrector's
+// start in the kernel a pair needs 210 VGPRs (U3 / C4: 2 waves per SIMD) and has not been measured.
+template <int HADV, int VADV>
+int launch_pre_t(const roms_step_idx_t *s, int itrc0, int ntr, bool fused)
+{
+  int rc = 0;
+  if constexpr (pre_t_pairs(HADV, VADV))
+    if (fused && ntr >= 2) {
+      const int np = ntr / 2;
+      rc = launch_pre_t_n<HADV, VADV, true, 2>(s, itrc0, np);
+      if (rc) return rc;
+      itrc0 += 2 * np;
+      ntr -= 2 * np;
+    }
+  if (ntr == 0) return 0;
+  return fused ? launch_pre_t_n<HADV, VADV, true, 1>(s, itrc0, ntr) : launch_pre_t_n<HADV, VADV, false, 1>(s, itrc0, ntr);
 }
 
 }  // namespace
 
 // The tracer half of pre_step3d_tile (pre_step3d.F:342-915 and the tracer part of :917-1145): t(3), t(nnew),
 // then t3dbc_tile(nout = 3) and the periodic wrap / mp_exchange4d of t(3).
-static int pre_step3d_tracers(const roms_step_idx_t *s)
+static int pre_step3d_tracers(const roms_step_idx_t *s, bool fused)
 {
   const roms_bounds_t &b = g_ctx.b;
   const roms_params_t &p = g_ctx.p;
@@ -244,22 +288,22 @@ static int pre_step3d_tracers(const roms_step_idx_t *s)
     while (it <= b.NT) {
       const int n = adv_run_length(p, b.NT, it);
       switch (adv_pair(p.Hadv[it - 1], p.Vadv[it - 1])) {
-      case ADV_U3 * 16 + ADV_C4:   rc = launch_pre_t<ADV_U3, ADV_C4>(s, it, n); break;
-      case ADV_A4 * 16 + ADV_A4:   rc = launch_pre_t<ADV_A4, ADV_A4>(s, it, n); break;
-      case ADV_C4 * 16 + ADV_C4:   rc = launch_pre_t<ADV_C4, ADV_C4>(s, it, n); break;
-      case ADV_C2 * 16 + ADV_C2:   rc = launch_pre_t<ADV_C2, ADV_C2>(s, it, n); break;
-      case ADV_U3 * 16 + ADV_SPLINES: rc = launch_pre_t<ADV_U3, ADV_SPLINES>(s, it, n); break;
-      case ADV_C4 * 16 + ADV_SPLINES: rc = launch_pre_t<ADV_C4, ADV_SPLINES>(s, it, n); break;
-      case ADV_A4 * 16 + ADV_SPLINES: rc = launch_pre_t<ADV_A4, ADV_SPLINES>(s, it, n); break;
-      case ADV_MPDATA * 16 + ADV_MPDATA: rc = launch_pre_t<ADV_MPDATA, ADV_MPDATA>(s, it, n); break;
+      case ADV_U3 * 16 + ADV_C4:   rc = launch_pre_t<ADV_U3, ADV_C4>(s, it, n, fused); break;
+      case ADV_A4 * 16 + ADV_A4:   rc = launch_pre_t<ADV_A4, ADV_A4>(s, it, n, fused); break;
+      case ADV_C4 * 16 + ADV_C4:   rc = launch_pre_t<ADV_C4, ADV_C4>(s, it, n, fused); break;
+      case ADV_C2 * 16 + ADV_C2:   rc = launch_pre_t<ADV_C2, ADV_C2>(s, it, n, fused); break;
+      case ADV_U3 * 16 + ADV_SPLINES: rc = launch_pre_t<ADV_U3, ADV_SPLINES>(s, it, n, fused); break;
+      case ADV_C4 * 16 + ADV_SPLINES: rc = launch_pre_t<ADV_C4, ADV_SPLINES>(s, it, n, fused); break;
+      case ADV_A4 * 16 + ADV_SPLINES: rc = launch_pre_t<ADV_A4, ADV_SPLINES>(s, it, n, fused); break;
+      case ADV_MPDATA * 16 + ADV_MPDATA: rc = launch_pre_t<ADV_MPDATA, ADV_MPDATA>(s, it, n, fused); break;
       // HSIMT: the predictor is the same first-order upstream step with Gamma = 1/2 (pre_step3d.F:364, :558, :730, :794)
-      case ADV_HSIMT * 16 + ADV_HSIMT: rc = launch_pre_t<ADV_MPDATA, ADV_MPDATA>(s, it, n); break;
+      case ADV_HSIMT * 16 + ADV_HSIMT: rc = launch_pre_t<ADV_MPDATA, ADV_MPDATA>(s, it, n, fused); break;
       // HSIMT vertically with another scheme horizontally (the one working one-sided pair of the reference): the
       // vertical predictor is the upstream step (:729-748, Gamma = 1/2 :793-799), the horizontal one the scheme's own
-      case ADV_U3 * 16 + ADV_HSIMT: rc = launch_pre_t<ADV_U3, ADV_MPDATA>(s, it, n); break;
-      case ADV_C4 * 16 + ADV_HSIMT: rc = launch_pre_t<ADV_C4, ADV_MPDATA>(s, it, n); break;
-      case ADV_A4 * 16 + ADV_HSIMT: rc = launch_pre_t<ADV_A4, ADV_MPDATA>(s, it, n); break;
-      case ADV_C2 * 16 + ADV_HSIMT: rc = launch_pre_t<ADV_C2, ADV_MPDATA>(s, it, n); break;
+      case ADV_U3 * 16 + ADV_HSIMT: rc = launch_pre_t<ADV_U3, ADV_MPDATA>(s, it, n, fused); break;
+      case ADV_C4 * 16 + ADV_HSIMT: rc = launch_pre_t<ADV_C4, ADV_MPDATA>(s, it, n, fused); break;
+      case ADV_A4 * 16 + ADV_HSIMT: rc = launch_pre_t<ADV_A4, ADV_MPDATA>(s, it, n, fused); break;
+      case ADV_C2 * 16 + ADV_HSIMT: rc = launch_pre_t<ADV_C2, ADV_MPDATA>(s, it, n, fused); break;
       default:
         return roms_fail("roms_hip_pre_step3d", "advection scheme pair not implemented (MPDATA and HSIMT only as H+V pairs)");
       }
@@ -287,7 +331,8 @@ static int pre_step3d_uv(const roms_step_idx_t *s)
   return 0;
 }
 
-extern "C" int roms_hip_pre_step3d(const roms_step_idx_t *s)
+// fused (roms_hip_rhs3d alone, roms_dev.h): t(nnew) is left to the mixing kernel that follows
+int pre_step3d_entry(const roms_step_idx_t *s, bool fused)
 {
   int rc = roms_entry_check("roms_hip_pre_step3d");
   if (rc) return rc;
@@ -297,5 +342,7 @@ extern "C" int roms_hip_pre_step3d(const roms_step_idx_t *s)
   ScopedTimer tm("pre_step3d");
   // (the reference does the tracers first; the two halves share no output)
   if ((rc = pre_step3d_uv(s))) return rc;
-  return pre_step3d_tracers(s);
+  return pre_step3d_tracers(s, fused);
 }
+
+extern "C" int roms_hip_pre_step3d(const roms_step_idx_t *s) { return pre_step3d_entry(s, false); }

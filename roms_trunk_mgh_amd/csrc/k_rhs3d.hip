@@ -472,15 +472,29 @@ extern "C" int roms_hip_rhs3d_tile(const roms_step_idx_t *s)
   return 0;
 }
 
+// Inside roms_hip_rhs3d the start of the corrector t(nnew) = Hz*t(nstp) + explicit vertical flux divergence moves from
+// k_pre_t into the rotated harmonic mixing kernel (k_mix.hip, k_t3dmix_geo<0, ISO, false, true>), which otherwise loads the
+// value just stored, adds its term and stores it again: nothing between the two touches t(nnew) (prsgrd reads no
+// tracer; t3dbc_tile and the exchanges at the end of the predictor work on level 3, pre_step3d.F:1131-1149).  Where the
+// mixing kernel cannot form the start -- along s-surfaces, with TS_MIX_STABILITY, diagnostics, an explicit part of the
+// vertical diffusion (lambda < 1) or nrhs /= nstp -- the two entries run as they do on their own.
+static bool rhs3d_fuses_tstart(const roms_step_idx_t *s)
+{
+  const roms_params_t &p = g_ctx.p;
+  return p.ts_dif2 && (p.mix_geo_ts || p.mix_iso_ts) && !p.ts_mix_stability && p.lambda == 1.0 && !dia_on() &&
+         s->nrhs == s->nstp;
+}
+
 // rhs3d(ng,tile) -- rhs3d.F:25-170: pre_step3d, prsgrd, t3dmix2, t3dmix4, rhs3d_tile, uv3dmix2, uv3dmix4
 extern "C" int roms_hip_rhs3d(const roms_step_idx_t *s)
 {
   int rc = roms_entry_check("roms_hip_rhs3d");
   if (rc) return rc;
   if ((rc = roms_uv_adv_check("roms_hip_rhs3d"))) return rc;          // before the first piece has changed anything
-  if ((rc = roms_hip_pre_step3d(s))) return rc;
+  const bool fused = rhs3d_fuses_tstart(s);
+  if ((rc = pre_step3d_entry(s, fused))) return rc;
   if ((rc = roms_hip_prsgrd(s))) return rc;
-  if (g_ctx.p.ts_dif2 && (rc = roms_hip_t3dmix2(s))) return rc;
+  if (g_ctx.p.ts_dif2 && (rc = t3dmix2_entry(s, fused))) return rc;
   if (g_ctx.p.ts_dif4 && (rc = roms_hip_t3dmix4(s))) return rc;
   if ((rc = roms_hip_rhs3d_tile(s))) return rc;
   if (g_ctx.p.uv_vis2 && (rc = roms_hip_uv3dmix2(s))) return rc;

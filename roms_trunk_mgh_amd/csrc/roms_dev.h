@@ -429,6 +429,11 @@ void snapshot_release();                  // snapshot.hip: waits for and frees a
 void snapshot_forget(int field_id);       // snapshot.hip: the same for one field (before it is re-registered)
 void diag_release();                      // k_diag.hip: frees the buffers of roms_hip_diag
 int check_lbc();
+// roms_hip_pre_step3d / roms_hip_t3dmix2 as roms_hip_rhs3d runs them.  fused (k_rhs3d.hip: rhs3d_fuses_tstart()): the
+// predictor leaves t(nnew) alone and the rotated mixing kernel stores Hz*t(nstp) + the explicit vertical flux
+// divergence + its own term in one write; the two extern "C" entries pass false.
+int pre_step3d_entry(const roms_step_idx_t *s, bool fused);   // k_pre_step3d.hip
+int t3dmix2_entry(const roms_step_idx_t *s, bool fused);      // k_mix.hip
 int roms_rowm_prepare();               // k_step2d_mom.hip: examine the metric arrays if needed (synchronises once)
 void roms_rowm_invalidate();            // a metric array may have changed
 bool roms_rowm_is_table_field(int id);  // is field `id` one of the arrays the row table is built from?
