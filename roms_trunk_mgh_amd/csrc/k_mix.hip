@@ -12,51 +12,16 @@
 // FS) become register sliding windows, so the rotated operator needs one read
 // of t(nrhs), z_r, Hz and one read-modify-write of t(nnew) per tracer -- inside roms_hip_rhs3d (START) one write of
 // t(nnew) and no read: the kernel forms the start of the corrector that k_pre_t would have stored.
+// Two kernels, k_t3dmix_geo<MODE, ISO, STAB, START> (rotated) and k_t3dmix_s<MODE, STAB, DIA> (along s-surfaces); what they
+// share -- the thread's column, the pointers, face coefficients and masks, tdiff, Lap4, the bracket of the vertical
+// flux -- is in tmix.h.  The host side picks an instantiation from one table, mix_kernel(), and launches it.
 #include "roms_dev.h"
 #include "advect.h"
+#include "tmix.h"
 
 int roms_entry_check(const char *name);
 
 namespace {
-
-__device__ __forceinline__ double dmin0(double a) { return a < 0.0 ? a : 0.0; }   // MIN(a,0)
-__device__ __forceinline__ double dmax0(double a) { return a > 0.0 ? a : 0.0; }   // MAX(a,0)
-
-// The tracer difference a - b of the operators' first application; STAB (TS_MIX_STABILITY, t3dmix2_s.h:212-218,
-// t3dmix2_geo.h:236 / :268 / :301 and the like sites of t3dmix2_iso.h and of the first operator of t3dmix4_*.h): 3/4 of
-// it plus 1/4 of the same difference a2 - b2 of t(nstp)
-template <bool STAB>
-__device__ __forceinline__ double tdiff(double a, double b, double a2, double b2)
-{
-  if constexpr (STAB) return 0.75 * (a - b) + 0.25 * (a2 - b2);
-  else return a - b;
-}
-
-// The range and the edge rule of the first biharmonic operator (t3dmix4_s.h:262-275, :347-405): one point beyond the
-// tile inside the grid; outside a physical edge LapT is zero where the tracer's condition is closed, a copy of the
-// first inside value otherwise.  (The corner values the reference also sets are never read by the second operator.)
-struct Lap4 {
-  double *lap;                  // LapT of one tracer, module extents
-  int i0, i1, j0, j1;           // Imin:Imax, Jmin:Jmax
-  int closed[4];                // [LBS_WEST .. LBS_NORTH]
-  int itrc;
-  int nstp;                     // STAB kernels: the time level of the 1/4 part
-};
-
-template <int MODE>
-__device__ __forceinline__ void lap4_store(const roms_bounds_t &b, const Lap4 &L, long ni, int i, int j, long a, double val)
-{
-  const gd_t lap = (gd_t)L.lap;
-  lap[a] = val;
-  if (!b.EWperiodic) {
-    if (b.west_edge && i == b.Istr) lap[a - 1] = L.closed[LBS_WEST] ? 0.0 : val;
-    if (b.east_edge && i == b.Iend) lap[a + 1] = L.closed[LBS_EAST] ? 0.0 : val;
-  }
-  if (!b.NSperiodic) {
-    if (b.south_edge && j == b.Jstr) lap[a - ni] = L.closed[LBS_SOUTH] ? 0.0 : val;
-    if (b.north_edge && j == b.Jend) lap[a + ni] = L.closed[LBS_NORTH] ? 0.0 : val;
-  }
-}
 
 // MODE 0: t3dmix2_geo (all tracers of the launch).  MODE 1 / 2: first / second operator of t3dmix4_geo for tracer
 // L.itrc -- the arithmetic of the three blocks of the reference is the same.
@@ -74,19 +39,12 @@ k_t3dmix_geo(const RomsDev *__restrict__ c, int nrhs, int nnew, Lap4 L)
 {
   static_assert(!START || (MODE == 0 && !STAB), "the corrector's start goes with t3dmix2 alone");
   DEV_PROLOGUE(c)
-  const int ilo = MODE == 1 ? L.i0 : b.Istr, ihi = MODE == 1 ? L.i1 : b.Iend;
-  const int jlo = MODE == 1 ? L.j0 : b.Jstr, jhi = MODE == 1 ? L.j1 : b.Jend;
-  const TileTr tt = decode_tile_tracer(ihi - ilo + 1, jhi - jlo + 1, MODE == 0 ? b.NT : 1);
-  if (!tt.valid) return;
-  const int i = ilo + tt.bx * BLK_X + threadIdx.x;
-  const int j = jlo + tt.by * BLK_Y + threadIdx.y;
-  const int itrc = MODE == 0 ? 1 + tt.itr : L.itrc;
-  if (i > ihi || j > jhi) return;
+  const MixCol col = mix_column<MODE>(b, L);
+  if (!col.valid) return;
+  const int i = col.i, j = col.j, itrc = col.itrc;
   const double dt = c->p.dt;
-  const double *__restrict__ T = MODE == 2 ? L.lap : c->F.t + ((long)(nrhs - 1) + 3L * (itrc - 1)) * n3r;
-  static_assert(!(STAB && MODE == 2), "the second biharmonic operator acts on LapT alone");
-  const double *__restrict__ S = STAB ? c->F.t + ((long)(L.nstp - 1) + 3L * (itrc - 1)) * n3r : T;
-  double *__restrict__ tn = c->F.t + ((long)(nnew - 1) + 3L * (itrc - 1)) * n3r;
+  const MixPtr P = mix_pointers<MODE, STAB>(c, nrhs, nnew, L, itrc, n3r);
+  const double *__restrict__ T = P.T, *__restrict__ S = P.S;
   const double *__restrict__ z_r = ISO ? c->F.pden : c->F.z_r;      // the field whose horizontal differences give the slopes
   const double *__restrict__ zz = c->F.z_r;                          // ISO: depths of the own column
   const double *__restrict__ Hz = c->F.Hz;
@@ -107,14 +65,11 @@ k_t3dmix_geo(const RomsDev *__restrict__ c, int nrhs, int nnew, Lap4 L)
   // face metrics: xi faces i and i+1, eta faces j and j+1
   double mx0 = 0.5 * (pm[c0] + pm[c0 - 1]), mx1 = 0.5 * (pm[c0 + 1] + pm[c0]);
   double my0 = 0.5 * (pn[c0] + pn[c0 - ni]), my1 = 0.5 * (pn[c0 + ni] + pn[c0]);
-  if (c->p.masking) {                                     // MASKING, t3dmix2_geo.h:228, :260
-    mx0 = mx0 * umaskw(c, c0); mx1 = mx1 * umaskw(c, c0 + 1);          // (+ WET_DRY, :231, :263)
-    my0 = my0 * vmaskw(c, c0); my1 = my1 * vmaskw(c, c0 + ni);
+  if (c->p.masking) {                                     // MASKING, t3dmix2_geo.h:228, :260 (+ WET_DRY, :231, :263)
+    const Face4 fm = face_mask(c, c0, ni);
+    mx0 = mx0 * fm.x0; mx1 = mx1 * fm.x1; my0 = my0 * fm.e0; my1 = my1 * fm.e1;
   }
-  const double cfx0 = 0.25 * (d2[c0] + d2[c0 - 1]) * c->F.on_u[c0];
-  const double cfx1 = 0.25 * (d2[c0 + 1] + d2[c0]) * c->F.on_u[c0 + 1];
-  const double cfe0 = 0.25 * (d2[c0] + d2[c0 - ni]) * c->F.om_v[c0];
-  const double cfe1 = 0.25 * (d2[c0 + ni] + d2[c0]) * c->F.om_v[c0 + ni];
+  const Face4 cf = face_coef(d2, c->F.on_u, c->F.om_v, c0, ni);
   const double cfs = 0.5 * d2[c0];
   const double cdt = dt * pm[c0] * pn[c0];
   // level-k ("k1") and level-(k+1) ("k2") slabs at faces i, i+1, j, j+1
@@ -136,7 +91,7 @@ k_t3dmix_geo(const RomsDev *__restrict__ c, int nrhs, int nnew, Lap4 L)
                 double zzm1, zzp1, zzs1, zzn1;             // TS_MIX_MIN_STRAT: z_r of the four neighbour columns
                 double akn, gh, zwk; };                    // START: what FC(k) of the explicit vertical flux reads (VStartIn)
   const gcd_t gT = (gcd_t)T, gS = (gcd_t)S, gZ = (gcd_t)z_r, gHz = (gcd_t)Hz;
-  const gd_t gtn = (gd_t)tn;
+  const gd_t gtn = (gd_t)P.tn;
   auto load_level = [&](int k) {
     LvIn L;
     const long ck = c0 + (long)(k - 1) * nij;
@@ -202,42 +157,30 @@ k_t3dmix_geo(const RomsDev *__restrict__ c, int nrhs, int nnew, Lap4 L)
     }
     const double hz0 = cur.hz0, hzm = cur.hzm, hzp = cur.hzp, hzs = cur.hzs, hzn = cur.hzn;
     // FX(i), FX(i+1), FE(j), FE(j+1): t3dmix2_geo.h:268-310
-    const double FX0 = cfx0 * (hz0 + hzm) *
+    const double FX0 = cf.x0 * (hz0 + hzm) *
         (tx0_a - 0.5 * (f1(zx0_a) * (dzm_a + dz0_b) + f2(zx0_a) * (dzm_b + dz0_a)));
-    const double FX1 = cfx1 * (hzp + hz0) *
+    const double FX1 = cf.x1 * (hzp + hz0) *
         (tx1_a - 0.5 * (f1(zx1_a) * (dz0_a + dzp_b) + f2(zx1_a) * (dz0_b + dzp_a)));
-    const double FE0 = cfe0 * (hz0 + hzs) *
+    const double FE0 = cf.e0 * (hz0 + hzs) *
         (te0_a - 0.5 * (f1(ze0_a) * (dzs_a + dz0_b) + f2(ze0_a) * (dzs_b + dz0_a)));
-    const double FE1 = cfe1 * (hzn + hz0) *
+    const double FE1 = cf.e1 * (hzn + hz0) *
         (te1_a - 0.5 * (f1(ze1_a) * (dz0_a + dzn_b) + f2(ze1_a) * (dz0_b + dzn_a)));
-    if (k < N) {
-      double c1 = f1(zx0_a), c2 = f1(zx1_b), c3 = f2(zx0_b), c4 = f2(zx1_a);
-      if constexpr (!ISO) {
-        FS_b = cfs * (c1 * (c1 * dz0_b - tx0_a) + c2 * (c2 * dz0_b - tx1_b) +
-                      c3 * (c3 * dz0_b - tx0_b) + c4 * (c4 * dz0_b - tx1_a));
-        c1 = f1(ze0_a); c2 = f1(ze1_b); c3 = f2(ze0_b); c4 = f2(ze1_a);
-        FS_b = FS_b + cfs * (c1 * (c1 * dz0_b - te0_a) + c2 * (c2 * dz0_b - te1_b) +
-                             c3 * (c3 * dz0_b - te0_b) + c4 * (c4 * dz0_b - te1_a));
-      } else if constexpr (MODE == 0) {          // t3dmix2_iso.h:395-417: one running sum, then 0.5 * cff * diff2 * FS
-        double cff = c1 * (c1 * dz0_b - tx0_a) + c2 * (c2 * dz0_b - tx1_b) +
-                     c3 * (c3 * dz0_b - tx0_b) + c4 * (c4 * dz0_b - tx1_a);
-        c1 = f1(ze0_a); c2 = f1(ze1_b); c3 = f2(ze0_b); c4 = f2(ze1_a);
-        cff = cff + c1 * (c1 * dz0_b - te0_a) + c2 * (c2 * dz0_b - te1_b) +
-              c3 * (c3 * dz0_b - te0_b) + c4 * (c4 * dz0_b - te1_a);
+    if (k < N) {                               // FS(k2): the xi bracket, then the eta one
+      const double bx = fs_bracket(f1(zx0_a), f1(zx1_b), f2(zx0_b), f2(zx1_a), dz0_b, tx0_a, tx1_b, tx0_b, tx1_a);
+      const double c1 = f1(ze0_a), c2 = f1(ze1_b), c3 = f2(ze0_b), c4 = f2(ze1_a);
+      if constexpr (ISO && MODE == 0) {          // t3dmix2_iso.h:395-417: one running sum, then 0.5 * cff * diff2 * FS
+        const double cff = bx + c1 * (c1 * dz0_b - te0_a) + c2 * (c2 * dz0_b - te1_b) +      // (the eta terms join the sum one
+                           c3 * (c3 * dz0_b - te0_b) + c4 * (c4 * dz0_b - te1_a);            // by one: not fs_bracket's order)
         FS_b = 0.5 * cff * d2[c0] * fsf_b;
-      } else {                                   // t3dmix4_iso.h:443-480: each direction times 0.5 * diff4
-        double cff = cfs * (c1 * (c1 * dz0_b - tx0_a) + c2 * (c2 * dz0_b - tx1_b) +
-                            c3 * (c3 * dz0_b - tx0_b) + c4 * (c4 * dz0_b - tx1_a));
-        c1 = f1(ze0_a); c2 = f1(ze1_b); c3 = f2(ze0_b); c4 = f2(ze1_a);
-        cff = cff + cfs * (c1 * (c1 * dz0_b - te0_a) + c2 * (c2 * dz0_b - te1_b) +
-                           c3 * (c3 * dz0_b - te0_b) + c4 * (c4 * dz0_b - te1_a));
-        FS_b = cff * fsf_b;
+      } else {                                   // each direction times 0.5 * diff; t3dmix4_iso.h:443-480: the sum times FS
+        FS_b = cfs * bx + cfs * fs_bracket(c1, c2, c3, c4, dz0_b, te0_a, te1_b, te0_b, te1_a);
+        if constexpr (ISO) FS_b = FS_b * fsf_b;
       }
     } else FS_b = 0.0;
     if constexpr (MODE == 1) {                 // t3dmix4_geo.h:445-455
       const double cff = pm[c0] * pn[c0];
       const double cff1 = 1.0 / hz0;
-      lap4_store<MODE>(b, L, ni, i, j, ck, cff1 * (cff * (FX1 - FX0 + FE1 - FE0) + (FS_b - FS_a)));
+      lap4_store(b, L, ni, i, j, ck, cff1 * (cff * (FX1 - FX0 + FE1 - FE0) + (FS_b - FS_a)));
     } else {
       const double cff1 = cdt * (FX1 - FX0);
       const double cff2 = cdt * (FE1 - FE0);
@@ -258,87 +201,27 @@ k_t3dmix_geo(const RomsDev *__restrict__ c, int nrhs, int nnew, Lap4 L)
   }
 }
 
+// Along s-surfaces.  MODE 0: t3dmix2_s_tile (diff2, all tracers, t(nnew) + the two directions); MODE 1 / 2: t3dmix4_s_tile,
+// first operator (:281-345) and second operator with the time step (:407-475), coefficient diff4.
 // DIA (DIAGNOSTICS_TS, t3dmix2_s.h:293-296): the two directions and their sum go to DiaTwrk(iTxdif, iTydif, iThdif)
 // (m Tunits; k_step3d_t_pipe turns them into Tunits)
-template <bool STAB, bool DIA = false>
+template <int MODE, bool STAB = false, bool DIA = false>
 __global__ void __launch_bounds__(BLK_X *BLK_Y)
-k_t3dmix2_s(const RomsDev *__restrict__ c, int nrhs, int nnew, int nstp)
+k_t3dmix_s(const RomsDev *__restrict__ c, int nrhs, int nnew, Lap4 L)
 {
+  static_assert((!DIA || MODE == 0) && !(STAB && MODE == 2), "diagnostics: harmonic only; t(nstp): never beside LapT");
   DEV_PROLOGUE(c)
-  const TileTr tt = decode_tile_tracer(b.Iend - b.Istr + 1, b.Jend - b.Jstr + 1, b.NT);
-  if (!tt.valid) return;
-  const int i = b.Istr + tt.bx * BLK_X + threadIdx.x;
-  const int j = b.Jstr + tt.by * BLK_Y + threadIdx.y;
-  const int itrc = 1 + tt.itr;
-  if (i > b.Iend || j > b.Jend) return;
-  const double *__restrict__ T = c->F.t + ((long)(nrhs - 1) + 3L * (itrc - 1)) * n3r;
-  const double *__restrict__ S = STAB ? c->F.t + ((long)(nstp - 1) + 3L * (itrc - 1)) * n3r : T;   // TS_MIX_STABILITY
-  double *__restrict__ tn = c->F.t + ((long)(nnew - 1) + 3L * (itrc - 1)) * n3r;
-  const double *__restrict__ Hz = c->F.Hz;
-  const double *__restrict__ d2 = c->F.diff2 + (long)(itrc - 1) * nij;
+  const MixCol col = mix_column<MODE>(b, L);
+  if (!col.valid) return;
+  const int i = col.i, j = col.j, itrc = col.itrc;
+  const MixPtr P = mix_pointers<MODE, STAB>(c, nrhs, nnew, L, itrc, n3r);
+  const double *__restrict__ T = P.T, *__restrict__ S = P.S, *__restrict__ Hz = c->F.Hz;
   const long c0 = I2(i, j);
-  const double cfx0 = 0.25 * (d2[c0] + d2[c0 - 1]) * c->F.pmon_u[c0];
-  const double cfx1 = 0.25 * (d2[c0 + 1] + d2[c0]) * c->F.pmon_u[c0 + 1];
-  const double cfe0 = 0.25 * (d2[c0] + d2[c0 - ni]) * c->F.pnom_v[c0];
-  const double cfe1 = 0.25 * (d2[c0 + ni] + d2[c0]) * c->F.pnom_v[c0 + ni];
-  const double cdt = c->p.dt * c->F.pm[c0] * c->F.pn[c0];
-  const bool masking = c->p.masking != 0;                 // MASKING, t3dmix2_s.h:235, :275
-  // (WET_DRY: times the wet/dry mask of the face, the block after each MASKING block of t3dmix2_s.h / t3dmix4_s.h)
-  const double um0 = masking ? umaskw(c, c0) : 1.0, um1 = masking ? umaskw(c, c0 + 1) : 1.0;
-  const double vm0 = masking ? vmaskw(c, c0) : 1.0, vm1 = masking ? vmaskw(c, c0 + ni) : 1.0;
-  for (int k = 1; k <= N; k++) {
-    const long ck = c0 + (long)(k - 1) * nij;
-    const double t0 = T[ck], h0 = Hz[ck];
-    double s0 = 0.0, sm = 0.0, sp = 0.0, ss = 0.0, sn = 0.0;
-    if constexpr (STAB) { s0 = S[ck]; sm = S[ck - 1]; sp = S[ck + 1]; ss = S[ck - ni]; sn = S[ck + ni]; }
-    double FX0 = cfx0 * (h0 + Hz[ck - 1]) * tdiff<STAB>(t0, T[ck - 1], s0, sm);
-    double FX1 = cfx1 * (Hz[ck + 1] + h0) * tdiff<STAB>(T[ck + 1], t0, sp, s0);
-    double FE0 = cfe0 * (h0 + Hz[ck - ni]) * tdiff<STAB>(t0, T[ck - ni], s0, ss);
-    double FE1 = cfe1 * (Hz[ck + ni] + h0) * tdiff<STAB>(T[ck + ni], t0, sn, s0);
-    if (masking) { FX0 = FX0 * um0; FX1 = FX1 * um1; FE0 = FE0 * vm0; FE1 = FE1 * vm1; }
-    const double cff1 = cdt * (FX1 - FX0);
-    const double cff2 = cdt * (FE1 - FE0);
-    const double cff3 = cff1 + cff2;
-    tn[ck] = tn[ck] + cff3;
-    if constexpr (DIA) {
-      DIA_PLANE(c, DIA_iTxdif, itrc, n3r)[ck] = cff1;
-      DIA_PLANE(c, DIA_iTydif, itrc, n3r)[ck] = cff2;
-      DIA_PLANE(c, DIA_iThdif, itrc, n3r)[ck] = cff3;
-    }
-  }
-}
-
-// t3dmix4_s_tile, first operator (MODE 1, :281-345) and second operator with the time step (MODE 2, :407-475)
-template <int MODE, bool STAB = false>
-__global__ void __launch_bounds__(BLK_X *BLK_Y)
-k_t3dmix4_s(const RomsDev *__restrict__ c, int nrhs, int nnew, Lap4 L)
-{
-  DEV_PROLOGUE(c)
-  const int ilo = MODE == 1 ? L.i0 : b.Istr, ihi = MODE == 1 ? L.i1 : b.Iend;
-  const int jlo = MODE == 1 ? L.j0 : b.Jstr, jhi = MODE == 1 ? L.j1 : b.Jend;
-  const TileTr tt = decode_tile_tracer(ihi - ilo + 1, jhi - jlo + 1, 1);
-  if (!tt.valid) return;
-  const int i = ilo + tt.bx * BLK_X + threadIdx.x;
-  const int j = jlo + tt.by * BLK_Y + threadIdx.y;
-  const int itrc = L.itrc;
-  if (i > ihi || j > jhi) return;
-  const double *__restrict__ T = MODE == 2 ? L.lap : c->F.t + ((long)(nrhs - 1) + 3L * (itrc - 1)) * n3r;
-  static_assert(!(STAB && MODE == 2), "the second biharmonic operator acts on LapT alone");
-  const double *__restrict__ S = STAB ? c->F.t + ((long)(L.nstp - 1) + 3L * (itrc - 1)) * n3r : T;   // TS_MIX_STABILITY
-  double *__restrict__ tn = c->F.t + ((long)(nnew - 1) + 3L * (itrc - 1)) * n3r;
-  const double *__restrict__ Hz = c->F.Hz;
-  const double *__restrict__ d4 = c->F.diff4 + (long)(itrc - 1) * nij;
-  const long c0 = I2(i, j);
-  double cfx0 = 0.25 * (d4[c0] + d4[c0 - 1]) * c->F.pmon_u[c0];
-  double cfx1 = 0.25 * (d4[c0 + 1] + d4[c0]) * c->F.pmon_u[c0 + 1];
-  double cfe0 = 0.25 * (d4[c0] + d4[c0 - ni]) * c->F.pnom_v[c0];
-  double cfe1 = 0.25 * (d4[c0 + ni] + d4[c0]) * c->F.pnom_v[c0 + ni];
+  Face4 cf = face_coef((MODE == 0 ? c->F.diff2 : c->F.diff4) + (long)(itrc - 1) * nij, c->F.pmon_u, c->F.pnom_v, c0, ni);
   const bool masking = c->p.masking != 0;
-  // (WET_DRY: times the wet/dry mask of the face, the block after each MASKING block of t3dmix2_s.h / t3dmix4_s.h)
-  const double um0 = masking ? umaskw(c, c0) : 1.0, um1 = masking ? umaskw(c, c0 + 1) : 1.0;
-  const double vm0 = masking ? vmaskw(c, c0) : 1.0, vm1 = masking ? vmaskw(c, c0 + ni) : 1.0;
-  if (MODE == 1 && masking) {                            // the first operator masks the coefficient, :296, :326
-    cfx0 = cfx0 * um0; cfx1 = cfx1 * um1; cfe0 = cfe0 * vm0; cfe1 = cfe1 * vm1;
+  const Face4 fm = face_mask(c, c0, ni);
+  if (MODE == 1 && masking) {                            // the first operator masks the coefficient, t3dmix4_s.h:296, :326
+    cf.x0 = cf.x0 * fm.x0; cf.x1 = cf.x1 * fm.x1; cf.e0 = cf.e0 * fm.e0; cf.e1 = cf.e1 * fm.e1;
   }
   const double pmn = c->F.pm[c0] * c->F.pn[c0];
   const double cdt = c->p.dt * c->F.pm[c0] * c->F.pn[c0];
@@ -347,21 +230,61 @@ k_t3dmix4_s(const RomsDev *__restrict__ c, int nrhs, int nnew, Lap4 L)
     const double t0 = T[ck], h0 = Hz[ck];
     double s0 = 0.0, sm = 0.0, sp = 0.0, ss = 0.0, sn = 0.0;
     if constexpr (STAB) { s0 = S[ck]; sm = S[ck - 1]; sp = S[ck + 1]; ss = S[ck - ni]; sn = S[ck + ni]; }
-    double FX0 = cfx0 * (h0 + Hz[ck - 1]) * tdiff<STAB>(t0, T[ck - 1], s0, sm);
-    double FX1 = cfx1 * (Hz[ck + 1] + h0) * tdiff<STAB>(T[ck + 1], t0, sp, s0);
-    double FE0 = cfe0 * (h0 + Hz[ck - ni]) * tdiff<STAB>(t0, T[ck - ni], s0, ss);
-    double FE1 = cfe1 * (Hz[ck + ni] + h0) * tdiff<STAB>(T[ck + ni], t0, sn, s0);
+    double FX0 = cf.x0 * (h0 + Hz[ck - 1]) * tdiff<STAB>(t0, T[ck - 1], s0, sm);
+    double FX1 = cf.x1 * (Hz[ck + 1] + h0) * tdiff<STAB>(T[ck + 1], t0, sp, s0);
+    double FE0 = cf.e0 * (h0 + Hz[ck - ni]) * tdiff<STAB>(t0, T[ck - ni], s0, ss);
+    double FE1 = cf.e1 * (Hz[ck + ni] + h0) * tdiff<STAB>(T[ck + ni], t0, sn, s0);
     if constexpr (MODE == 1) {
       const double cff = 1.0 / h0;
-      lap4_store<MODE>(b, L, ni, i, j, ck, pmn * cff * (FX1 - FX0 + FE1 - FE0));
-    } else {
-      if (masking) { FX0 = FX0 * um0; FX1 = FX1 * um1; FE0 = FE0 * vm0; FE1 = FE1 * vm1; }   // the second the flux, :425, :446
+      lap4_store(b, L, ni, i, j, ck, pmn * cff * (FX1 - FX0 + FE1 - FE0));
+    } else {                                             // the others mask the flux, t3dmix2_s.h:235, :275, t3dmix4_s.h:425, :446
+      if (masking) { FX0 = FX0 * fm.x0; FX1 = FX1 * fm.x1; FE0 = FE0 * fm.e0; FE1 = FE1 * fm.e1; }
       const double cff1 = cdt * (FX1 - FX0);
       const double cff2 = cdt * (FE1 - FE0);
-      tn[ck] = tn[ck] - (cff1 + cff2);
+      const double cff3 = cff1 + cff2;
+      if constexpr (MODE == 2) P.tn[ck] = P.tn[ck] - cff3;   // t3dmix4_s.h:466
+      else P.tn[ck] = P.tn[ck] + cff3;
+      if constexpr (DIA) {
+        DIA_PLANE(c, DIA_iTxdif, itrc, n3r)[ck] = cff1;
+        DIA_PLANE(c, DIA_iTydif, itrc, n3r)[ck] = cff2;
+        DIA_PLANE(c, DIA_iThdif, itrc, n3r)[ck] = cff3;
+      }
     }
   }
 }
+
+// The instantiation for an operator (mode 0 / 1 / 2) along a surface, with TS_MIX_STABILITY, the fused start of
+// t(nnew) and the diagnostics; nullptr where none is built
+using MixKernel = void (*)(const RomsDev *, int, int, Lap4);
+enum { SURF_S, SURF_GEO, SURF_ISO };
+constexpr int mix_key(int mode, int surf, bool stab = false, bool start = false, bool dia = false)
+{ return (((mode * 3 + surf) * 2 + stab) * 2 + start) * 2 + dia; }
+MixKernel mix_kernel(int mode, int surf, bool stab, bool start, bool dia)
+{
+  switch (mix_key(mode, surf, stab, start, dia)) {
+    case mix_key(0, SURF_S):                     return k_t3dmix_s<0>;
+    case mix_key(0, SURF_S, true):               return k_t3dmix_s<0, true>;
+    case mix_key(0, SURF_S, false, false, true): return k_t3dmix_s<0, false, true>;
+    case mix_key(0, SURF_S, true, false, true):  return k_t3dmix_s<0, true, true>;
+    case mix_key(1, SURF_S):                     return k_t3dmix_s<1>;
+    case mix_key(1, SURF_S, true):               return k_t3dmix_s<1, true>;
+    case mix_key(2, SURF_S):                     return k_t3dmix_s<2>;
+    case mix_key(0, SURF_GEO):                   return k_t3dmix_geo<0, false>;
+    case mix_key(0, SURF_GEO, true):             return k_t3dmix_geo<0, false, true>;
+    case mix_key(0, SURF_GEO, false, true):      return k_t3dmix_geo<0, false, false, true>;
+    case mix_key(1, SURF_GEO):                   return k_t3dmix_geo<1, false>;
+    case mix_key(1, SURF_GEO, true):             return k_t3dmix_geo<1, false, true>;
+    case mix_key(2, SURF_GEO):                   return k_t3dmix_geo<2, false>;
+    case mix_key(0, SURF_ISO):                   return k_t3dmix_geo<0, true>;
+    case mix_key(0, SURF_ISO, true):             return k_t3dmix_geo<0, true, true>;
+    case mix_key(0, SURF_ISO, false, true):      return k_t3dmix_geo<0, true, false, true>;
+    case mix_key(1, SURF_ISO):                   return k_t3dmix_geo<1, true>;
+    case mix_key(1, SURF_ISO, true):             return k_t3dmix_geo<1, true, true>;
+    case mix_key(2, SURF_ISO):                   return k_t3dmix_geo<2, true>;
+  }
+  return nullptr;
+}
+int mix_surface(const roms_params_t &p) { return p.mix_iso_ts ? SURF_ISO : p.mix_geo_ts ? SURF_GEO : p.mix_s_ts ? SURF_S : -1; }
 
 }  // namespace
 
@@ -370,27 +293,14 @@ static int t3dmix2_launch(const roms_step_idx_t *s, bool fused)
   const roms_bounds_t &b = g_ctx.b;
   const dim3 grid = grid_tile_tracer(b.Iend - b.Istr + 1, b.Jend - b.Jstr + 1, b.NT);
   const bool stab = g_ctx.p.ts_mix_stability != 0;       // TS_MIX_STABILITY
+  const int surf = mix_surface(g_ctx.p);
+  if (fused && (stab || dia_on() || surf < SURF_GEO))    // rhs3d_fuses_tstart(): rotated mixing, no STAB, no diagnostics
+    return roms_fail("roms_hip_t3dmix2", "internal: the fused start of t(nnew) was asked for where it is not built");
+  if (surf < 0) return roms_fail("roms_hip_t3dmix2", "no tracer mixing option (MIX_ISO_TS / MIX_GEO_TS / MIX_S_TS) selected");
   Lap4 L{};
   L.nstp = s->nstp;
-  if (fused) {                                           // rhs3d_fuses_tstart(): rotated mixing, no STAB, no diagnostics
-    if (stab || dia_on() || !(g_ctx.p.mix_iso_ts || g_ctx.p.mix_geo_ts))
-      return roms_fail("roms_hip_t3dmix2", "internal: the fused start of t(nnew) was asked for where it is not built");
-    if (g_ctx.p.mix_iso_ts) hipLaunchKernelGGL((k_t3dmix_geo<0, true, false, true>), grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, L);
-    else hipLaunchKernelGGL((k_t3dmix_geo<0, false, false, true>), grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, L);
-  } else if (g_ctx.p.mix_iso_ts) {
-    if (stab) hipLaunchKernelGGL((k_t3dmix_geo<0, true, true>), grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, L);
-    else hipLaunchKernelGGL((k_t3dmix_geo<0, true>), grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, L);
-  } else if (g_ctx.p.mix_geo_ts) {
-    if (stab) hipLaunchKernelGGL((k_t3dmix_geo<0, false, true>), grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, L);
-    else hipLaunchKernelGGL((k_t3dmix_geo<0, false>), grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, L);
-  } else if (g_ctx.p.mix_s_ts && dia_on()) {
-    if (stab) hipLaunchKernelGGL((k_t3dmix2_s<true, true>), grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, s->nstp);
-    else hipLaunchKernelGGL((k_t3dmix2_s<false, true>), grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, s->nstp);
-  } else if (g_ctx.p.mix_s_ts) {
-    if (stab) hipLaunchKernelGGL(k_t3dmix2_s<true>, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, s->nstp);
-    else hipLaunchKernelGGL(k_t3dmix2_s<false>, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, s->nstp);
-  } else
-    return roms_fail("roms_hip_t3dmix2", "no tracer mixing option (MIX_ISO_TS / MIX_GEO_TS / MIX_S_TS) selected");
+  const MixKernel kernel = mix_kernel(0, surf, stab, fused, surf == SURF_S && dia_on());
+  hipLaunchKernelGGL(kernel, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, L);
   KERNEL_CHECK("k_t3dmix2");
   return 0;
 }
@@ -416,10 +326,11 @@ extern "C" int roms_hip_t3dmix4(const roms_step_idx_t *s)
   const roms_params_t &p = g_ctx.p;
   if (!p.ts_dif4) return roms_fail("roms_hip_t3dmix4", "TS_DIF4 is not set (roms_params_t.ts_dif4)");
   if ((rc = dia_check("roms_hip_t3dmix4"))) return rc;
-  if (!p.mix_iso_ts && !p.mix_geo_ts && !p.mix_s_ts)
-    return roms_fail("roms_hip_t3dmix4", "no tracer mixing option (MIX_ISO_TS / MIX_GEO_TS / MIX_S_TS) selected");
+  const int surf = mix_surface(p);
+  if (surf < 0) return roms_fail("roms_hip_t3dmix4", "no tracer mixing option (MIX_ISO_TS / MIX_GEO_TS / MIX_S_TS) selected");
   ScopedTimer tm("t3dmix4");
-  const bool stab = p.ts_mix_stability != 0;             // TS_MIX_STABILITY: in the first operator only
+  // TS_MIX_STABILITY: in the first operator only
+  const MixKernel first = mix_kernel(1, surf, p.ts_mix_stability != 0, false, false), second = mix_kernel(2, surf, false, false, false);
   Lap4 L;
   L.lap = g_ctx.hostc.ws3[1];
   L.nstp = s->nstp;
@@ -432,19 +343,8 @@ extern "C" int roms_hip_t3dmix4(const roms_step_idx_t *s)
   const dim3 g2 = grid_tile_tracer(b.Iend - b.Istr + 1, b.Jend - b.Jstr + 1, 1);
   for (int itrc = 1; itrc <= b.NT; itrc++) {
     L.itrc = itrc;
-    if (p.mix_iso_ts) {
-      if (stab) hipLaunchKernelGGL((k_t3dmix_geo<1, true, true>), g1, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, L);
-      else hipLaunchKernelGGL((k_t3dmix_geo<1, true>), g1, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, L);
-      hipLaunchKernelGGL((k_t3dmix_geo<2, true>), g2, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, L);
-    } else if (p.mix_geo_ts) {
-      if (stab) hipLaunchKernelGGL((k_t3dmix_geo<1, false, true>), g1, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, L);
-      else hipLaunchKernelGGL((k_t3dmix_geo<1, false>), g1, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, L);
-      hipLaunchKernelGGL((k_t3dmix_geo<2, false>), g2, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, L);
-    } else {
-      if (stab) hipLaunchKernelGGL((k_t3dmix4_s<1, true>), g1, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, L);
-      else hipLaunchKernelGGL(k_t3dmix4_s<1>, g1, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, L);
-      hipLaunchKernelGGL(k_t3dmix4_s<2>, g2, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, L);
-    }
+    hipLaunchKernelGGL(first, g1, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, L);
+    hipLaunchKernelGGL(second, g2, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs, s->nnew, L);
     KERNEL_CHECK("k_t3dmix4");
   }
   return 0;

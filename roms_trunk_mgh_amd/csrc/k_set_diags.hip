@@ -3,7 +3,7 @@
 // library-owned arrays DiaTwrk, DiaTrc, avgzeta and rmask_dia (mod_diags.F, mod_grid.F).
 //
 // The other DiaTwrk statements sit inside the fused tracer kernels, in their DIA instantiations: k_pre_t
-// (pre_step3d.F:894-904), k_t3dmix2_s (t3dmix2_s.h:293-296), k_step3d_t_pipe (step3d_t.F:868-871, :1199-1205,
+// (pre_step3d.F:894-904), k_t3dmix_s (t3dmix2_s.h:293-296), k_step3d_t_pipe (step3d_t.F:868-871, :1199-1205,
 // :1417-1427, :1475-1500).  DiaTwrk and DiaTrc take no halo exchange: a tile owns its IstrR:IendR, JstrR:JendR.
 //
 // Both kernels here are pure streaming, one thread per point, consecutive lanes along i, blockIdx.z over level x plane

@@ -248,7 +248,7 @@ struct LevelIn {         // (members in the order of the loads: the copy cur = n
 // column in LDS.  Instantiated at NMAX = 64 only (one kernel serves every N, not tuned).
 // DIA (DIAGNOSTICS_TS; NMAX = 64 only, not tuned): per level the upward sweep writes DiaTwrk(iTxadv, iTyadv, iThadv,
 // iTvadv) (step3d_t.F:868-871, :1199) and multiplies every term of the level by oHz (:1200-1203) -- those it has just
-// formed in registers, and the planes iTrate, iTvdif and iT?dif that k_pre_t and k_t3dmix2_s wrote earlier in the step,
+// formed in registers, and the planes iTrate, iTvdif and iT?dif that k_pre_t and k_t3dmix_s wrote earlier in the step,
 // read, scaled and written back; the back substitution adds the implicit increment to iTvdif (:1421-1424, or
 // :1482-1485 / :1495-1498 without SPLINES_VDIFF).  Six (nine with ts_dif2) planes per tracer, each store 64
 // consecutive doubles per wavefront like the tracer's own.

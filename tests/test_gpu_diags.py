@@ -1,5 +1,5 @@
 """-m gpu: the tracer budget diagnostics on the device (DIAGNOSTICS_TS: roms_hip_set_diagnostics, roms_hip_set_diags,
-roms_hip_get_diagnostic; the DIA instantiations of k_pre_t, k_t3dmix2_s, k_step3d_t_pipe and csrc/k_set_diags.hip).
+roms_hip_get_diagnostic; the DIA instantiations of k_pre_t, k_t3dmix_s, k_step3d_t_pipe and csrc/k_set_diags.hip).
 
 The oracle has no diagnostic lines: the expected terms are recovered from its per-routine entry points by
 tests/diags_util.py (stage differences, one transport zeroed at a time), whose closure tests/test_diags.py checks
@@ -41,14 +41,16 @@ def _fetch(be, st, accumulated=False):
     return {n: np.stack([be.get_diagnostic(n, it, accumulated) for it in range(1, st.b.NT + 1)], axis=-1) for n in _names(st)}
 
 
-def _sequence(st0, s, zero=(), zero_mix=()):
+def _sequence(st0, s, zero=(), zero_mix=(), dia=True, step3d_t=True):
     """pre_step3d, t3dmix2 (with ts_dif2), step3d_t on the device with the diagnostics on; `zero`: transports zeroed
     between the first two and step3d_t (the predictor has then seen the whole flow); `zero_mix`: face metrics zeroed
-    for t3dmix2 alone (neither of the other two reads them).  Returns (terms, state)."""
+    for t3dmix2 alone (neither of the other two reads them).  Returns (terms, state).  (`dia`, `step3d_t` = False:
+    without the diagnostics -- no terms then -- and stopping after t3dmix2, where the planes hold what it stored.)"""
     st = st0.copy()
     be = hip.RomsHip(st)
     try:
-        be.set_diagnostics(diags.Diags(st.b, 1))
+        if dia:
+            be.set_diagnostics(diags.Diags(st.b, 1))
         be.call("pre_step3d", s)
         if st.p.ts_dif2:
             for name in zero_mix:
@@ -60,8 +62,9 @@ def _sequence(st0, s, zero=(), zero_mix=()):
             st[name][:] = 0.0
         if zero:
             be.to_device(list(zero))
-        be.call("step3d_t", s)
-        got = _fetch(be, st)
+        if step3d_t:
+            be.call("step3d_t", s)
+        got = _fetch(be, st) if dia else None
         be.to_host()
         be.check_guards()
     finally:
@@ -120,6 +123,32 @@ def test_every_term_of_every_option(ov, mask, N):
     st = _state(N, ov, mask)
     assert (mask is None) or (st["rmask"][du.interior(st)] == 0.0).any()
     _check_terms(st, uniform=True)
+
+
+def test_hdif_terms_with_ts_mix_stability():
+    """MIX_S_TS with DIAGNOSTICS_TS and TS_MIX_STABILITY together, the one instantiation of the s-surface mixing kernel
+    no other test runs.  nrhs = 3 and nstp = 1 distinct (as tests/test_gpu_wide.py::_iso), so that the 1/4 part counts.
+    All bit for bit: t(nnew) as without the diagnostics (the kernel test_ts_mix_stability_kernels pins to the oracle);
+    the sum of the two directions; one direction's face metric zeroed; and the terms differ from those without
+    TS_MIX_STABILITY."""
+    s = util.step_idx(iic=5, nstp=1, nnew=2, nrhs=3)
+    st0 = _state(17, {"ts_mix_stability": 1})
+    assert st0.p.mix_s_ts == 1 and st0.p.ts_dif2 == 1 and st0.p.ts_mix_stability == 1
+    got, st = _sequence(st0, s, step3d_t=False)
+    w = np.broadcast_to(du.water(st0), got["iThdif"].shape)
+    t = st["t"]
+    assert (t[:, :, :, s.nstp - 1, :] != t[:, :, :, s.nrhs - 1, :])[w].any()
+    _, plain = _sequence(st0, s, dia=False, step3d_t=False)
+    assert np.array_equal(t[:, :, :, s.nnew - 1, :], plain["t"][:, :, :, s.nnew - 1, :])
+    assert not np.array_equal(t[:, :, :, s.nnew - 1, :], st0["t"][:, :, :, s.nnew - 1, :])
+    assert np.array_equal(got["iThdif"], got["iTxdif"] + got["iTydif"])
+    assert np.abs(got["iTxdif"][w]).max() > 0.0 and np.abs(got["iTydif"][w]).max() > 0.0
+    dx, _ = _sequence(st0, s, zero_mix=("pnom_v",), step3d_t=False)
+    dy, _ = _sequence(st0, s, zero_mix=("pmon_u",), step3d_t=False)
+    assert np.array_equal(got["iTxdif"], dx["iTxdif"]) and np.array_equal(got["iTydif"], dy["iTydif"])
+    assert not dx["iTydif"][w].any() and not dy["iTxdif"][w].any()
+    off, _ = _sequence(_with(st0, ts_mix_stability=0), s, step3d_t=False)
+    assert (got["iThdif"] != off["iThdif"])[w].any()
 
 
 # --------------------------------------------------------------------------------------------- 2. whole steps --
