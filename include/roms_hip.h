@@ -229,7 +229,7 @@ int roms_hip_t3dmix2(const roms_step_idx_t *s);     /* t3dmix2_geo.h:23  */
 int roms_hip_rhs3d_tile(const roms_step_idx_t *s);  /* rhs3d.F:174       */
 int roms_hip_uv3dmix2(const roms_step_idx_t *s);    /* uv3dmix2_s.h:42; with uv_vis2 = 2 uv3dmix2_geo.h:42 */
 int roms_hip_t3dmix4(const roms_step_idx_t *s);     /* t3dmix4_s.h:23, t3dmix4_geo.h:23 (TS_DIF4) */
-int roms_hip_uv3dmix4(const roms_step_idx_t *s);    /* uv3dmix4_s.h:43 (UV_VIS4; three ghost points, inp_par.F:268) */
+int roms_hip_uv3dmix4(const roms_step_idx_t *s);    /* uv3dmix4_s.h:43; with uv_vis4 = 2 uv3dmix4_geo.h:42 (UV_VIS4; three ghost points, inp_par.F:268) */
 /* step2d(ng,tile)                  ROMS/Nonlinear/step2d_LF_AM3.h:18 */
 int roms_hip_step2d(const roms_step_idx_t *s);
 /* step3d_uv(ng,tile)               ROMS/Nonlinear/step3d_uv.F:27     */

@@ -485,12 +485,15 @@ static bool rhs3d_fuses_tstart(const roms_step_idx_t *s)
          s->nrhs == s->nstp;
 }
 
+int roms_uv_mix_check(const char *where);    // k_uv3dmix2.hip
+
 // rhs3d(ng,tile) -- rhs3d.F:25-170: pre_step3d, prsgrd, t3dmix2, t3dmix4, rhs3d_tile, uv3dmix2, uv3dmix4
 extern "C" int roms_hip_rhs3d(const roms_step_idx_t *s)
 {
   int rc = roms_entry_check("roms_hip_rhs3d");
   if (rc) return rc;
   if ((rc = roms_uv_adv_check("roms_hip_rhs3d"))) return rc;          // before the first piece has changed anything
+  if ((rc = roms_uv_mix_check("roms_hip_rhs3d"))) return rc;
   const bool fused = rhs3d_fuses_tstart(s);
   if ((rc = pre_step3d_entry(s, fused))) return rc;
   if ((rc = roms_hip_prsgrd(s))) return rc;

@@ -77,7 +77,7 @@ MODULE roms_hip_mod
     INTEGER(c_int) :: masking, pgf
     INTEGER(c_int) :: lbc(6,4)          ! C: lbc[side][variable]
     REAL(c_double) :: obc_out(6,4), obc_in(6,4)   ! nudging coefficients of RadNud edges (1/s)
-    INTEGER(c_int) :: ts_dif4, uv_vis4            ! TS_DIF4, UV_VIS4 (biharmonic mixing)
+    INTEGER(c_int) :: ts_dif4, uv_vis4            ! TS_DIF4, UV_VIS4 (biharmonic mixing; uv_vis4 as uv_vis2, 1 MIX_S_UV, 2 MIX_GEO_UV)
     INTEGER(c_int) :: mix_iso_ts, radiation_2d    ! MIX_ISO_TS, RADIATION_2D
     REAL(c_double) :: Cdb_min, Cdb_max            ! UV_LOGDRAG limits
     !  GLS_MIXING (gls_prestep.F, gls_corstep.F): switch, stability functions (0 Galperin, 1 KANTHA_CLAYSON,
