@@ -1,15 +1,9 @@
 """Worker of the tiling-invariance test of the tracer budget diagnostics (tests/test_gpu_diags.py): one rank = one tile
-through the HIP library with the diagnostics on, halos over the gloo relay -- the transport of
-tests/mp_gpu_avg_worker.py."""
-import os
+through the HIP library with the diagnostics on, halos over the gloo relay -- the rank harness and transport of
+tests/tiling_util.py."""
 import sys
 
-import numpy as np
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-for path in (os.path.dirname(HERE), HERE):
-    if path not in sys.path:
-        sys.path.insert(0, path)
+import tiling_util
 
 SHAPE = dict(Lm=130, Mm=10, N=5)
 NDIA, NSTEPS = 3, 5                       # set_diags at iic = 1 .. 5: accumulate, initialise, accumulate, accumulate, initialise
@@ -44,29 +38,7 @@ def run(be, st):
     return out
 
 
-def run_rank(rank, world, ntI, ntJ, port, outdir, variant=""):
-    import torch
-    import torch.distributed as dist
-    from roms_trunk_mgh_amd import hip
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    torch.set_num_threads(1)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    st = tiled_state(variant, ntI, ntJ, rank)
-    ndev = torch.cuda.device_count()
-    be = hip.RomsHip(st, rank=rank, device=rank % max(ndev, 1), nccl_unique_id=None)
-    be.set_halo_relay_gloo(dist, torch)
-    try:
-        out = run(be, st)
-    finally:
-        be.close()
-    b = st.b
-    np.savez(os.path.join(outdir, f"tile{rank}.npz"),
-             bounds=np.array([b.IstrR, b.IendR, b.JstrR, b.JendR, b.LBi, b.LBj, b.UBi]), **out)
-    dist.barrier()
-    dist.destroy_process_group()
-
-
 if __name__ == "__main__":
-    a = sys.argv
-    run_rank(int(a[1]), int(a[2]), int(a[3]), int(a[4]), int(a[5]), a[6], a[7] if len(a) > 7 else "")
+    with tiling_util.Rank(sys.argv) as rk:
+        st = tiled_state(rk.args[0], rk.ntI, rk.ntJ, rk.rank)
+        rk.save(st.b, run(rk.hip(st), st))

@@ -1,15 +1,11 @@
 """Worker of the tiling-invariance test of the Lagrangian floats (tests/test_gpu_floats.py): one rank = one tile through
 the HIP library with floats set, halos and the floats' collection over the gloo relay or (variant "...+rccl", one rank)
-through RCCL in loopback -- the transports of tests/mp_gpu_avg_worker.py."""
-import os
+through RCCL in loopback -- the rank harness and transports of tests/tiling_util.py."""
 import sys
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-for path in (os.path.dirname(HERE), HERE):
-    if path not in sys.path:
-        sys.path.insert(0, path)
+import tiling_util
 
 SHAPE = dict(Lm=128, Mm=10, N=5)
 NFLOATS, NSTEPS = 197, 4
@@ -68,38 +64,9 @@ def run(be, st):
     return out
 
 
-def run_rank(rank, world, ntI, ntJ, port, outdir, variant=""):
-    import torch
-    import torch.distributed as dist
-    from roms_trunk_mgh_amd import hip
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    torch.set_num_threads(1)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    opts = set(variant.split("+")) if variant else set()
-    st = tiled_state(variant, ntI, ntJ, rank)
-    ndev = torch.cuda.device_count()
-    if "rccl" in opts:
-        import ctypes
-        assert world <= max(ndev, 1)
-        buf = ctypes.create_string_buffer(128)
-        if rank == 0:
-            assert hip.load().roms_hip_get_unique_id(buf) == 0
-        t = torch.frombuffer(bytearray(buf.raw), dtype=torch.uint8).clone()
-        dist.broadcast(t, src=0)
-        be = hip.RomsHip(st, rank=rank, device=rank, nccl_unique_id=bytes(t.numpy().tobytes()))
-    else:
-        be = hip.RomsHip(st, rank=rank, device=rank % max(ndev, 1), nccl_unique_id=None)
-        be.set_halo_relay_gloo(dist, torch)
-    try:
-        track, bounded = run(be, st)
-    finally:
-        be.close()
-    np.savez(os.path.join(outdir, f"tile{rank}.npz"), track=track, bounded=bounded)
-    dist.barrier()
-    dist.destroy_process_group()
-
-
 if __name__ == "__main__":
-    a = sys.argv
-    run_rank(int(a[1]), int(a[2]), int(a[3]), int(a[4]), int(a[5]), a[6], a[7] if len(a) > 7 else "")
+    with tiling_util.Rank(sys.argv) as rk:
+        variant = rk.args[0]
+        st = tiled_state(variant, rk.ntI, rk.ntJ, rk.rank)
+        track, bounded = run(rk.hip(st, rccl="rccl" in variant.split("+")), st)
+        rk.save(st.b, dict(track=track, bounded=bounded))

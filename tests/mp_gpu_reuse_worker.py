@@ -6,23 +6,11 @@ an RCCL id (loopback: the tile is its own W / E neighbour and every kernel takes
               (scenario 11); saves the three states
     two_ctx   a loopback context with graph_exchanges(1), sources and climatology, closed; then a loopback context that
               asks for nothing (scenario 12); saves its state and both graph_exchanges_state() values"""
-import ctypes
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for q in (ROOT, os.path.join(ROOT, "tests")):
-    if q not in sys.path:
-        sys.path.insert(0, q)
-
-
-def unique_id():
-    from roms_trunk_mgh_amd import hip
-    buf = ctypes.create_string_buffer(128)
-    assert hip.load().roms_hip_get_unique_id(buf) == 0
-    return bytes(buf.raw)
+from tiling_util import rccl_unique_id as unique_id
 
 
 def main(mode, app, out):

@@ -8,17 +8,13 @@ contract multiply-adds.
   2. seven whole steps through main3d; nothing else changes
   3. tiling invariance over the relay, and one tile in RCCL loopback
   4. the refusals"""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import avg_util as au
+import tiling_util
 import util
 from roms_trunk_mgh_amd import abi, ana, avg, hip, main3d
-from test_gpu_multitile import HERE, _free_port
 from test_gpu_wide import SHAPES, seam_dry, seam_land
 
 pytestmark = pytest.mark.gpu
@@ -162,30 +158,16 @@ def _tiles_equal_single(tmp_path, world, ntI, ntJ, variant):
     finally:
         be.close()
     assert all(np.abs(a).max() > 0.0 for a in want.values())
-    port = _free_port()
-    env = dict(os.environ, OMP_NUM_THREADS="1")
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "mp_gpu_avg_worker.py"), str(r), str(world), str(ntI),
-                               str(ntJ), str(port), str(tmp_path), variant], env=env) for r in range(world)]
-    try:
-        for p in procs:
-            assert p.wait(timeout=600) == 0
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
+    tiling_util.spawn_ranks("mp_gpu_avg_worker.py", world, [ntI, ntJ, tmp_path, variant], timeout=600)
     gb = st.b
-    for r in range(world):
-        d = np.load(os.path.join(tmp_path, f"tile{r}.npz"))
-        IstrR, IendR, JstrR, JendR, LBi, LBj, UBi = [int(x) for x in d["bounds"]]
-        J = slice(JstrR - LBj, JendR - LBj + 1)
-        Jg = slice(JstrR - gb.LBj, JendR - gb.LBj + 1)
-        for key, glob in want.items():
-            a = d[key]
-            own = a[IstrR - LBi:IendR - LBi + 1, J]
-            assert np.array_equal(own, glob[IstrR - gb.LBi:IendR - gb.LBi + 1, Jg]), (key, r)
-            if "basin" not in variant:
-                # the periodic ghost columns, filled after the close
-                cols = [i for i in list(range(-2, 1)) + list(range(gb.Lm + 1, gb.Lm + gb.NghostPoints + 1)) if LBi <= i <= UBi]
+    tiling_util.assert_tiles_equal(tmp_path, world, want, gb, list(want), owned="IstrR:IendR")
+    if "basin" not in variant:
+        for r, d, (_, J), (_, Jg) in tiling_util.tiles(tmp_path, world, gb, owned="IstrR:IendR"):
+            LBi, UBi = d["LBi"], d["UBi"]
+            # the periodic ghost columns, filled after the close
+            cols = [i for i in list(range(-2, 1)) + list(range(gb.Lm + 1, gb.Lm + gb.NghostPoints + 1)) if LBi <= i <= UBi]
+            for key, glob in want.items():
+                a = d[key]
                 for i in cols:
                     assert np.array_equal(a[i - LBi, J], glob[i - gb.LBi, Jg]), (key, r, i)
                     assert np.array_equal(a[i - LBi, J], glob[(i - 1) % gb.Lm + 1 - gb.LBi, Jg]), (key, r, i, "image")

@@ -10,17 +10,13 @@ against closed forms:
   4. tiling invariance, owned and ghost points, over the gloo relay and once over RCCL in loopback
   5. exponential relaxation of a uniform tracer, 100 steps
 and the error convention.  Every run ends with check_guards()."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import clima_util as cu
+import tiling_util
 import util
 from roms_trunk_mgh_amd import abi, ana, clima, hip, main3d
-from test_gpu_multitile import HERE, _free_port
 
 pytestmark = pytest.mark.gpu
 
@@ -263,37 +259,18 @@ def test_edges_take_tau_from_the_coefficient_arrays(config):
 # ------------------------------------------------------- 4. tiling invariance --
 def _tiles_equal_single(tmp_path, world, ntI, ntJ, config, variant, nsteps=3):
     import mp_gpu_clima_worker as worker
-    st0 = cu.tiled_state(config, "basin" if "basin" in variant else "")
-    ref = cu.run_hip(st0, steps=nsteps, clima_=st0.clima)
+    st0 = worker.tiled_state(config, variant)
+    ref = st0.copy()
+    be = hip.RomsHip(ref)
+    try:
+        want = worker.run(be, ref, nsteps)
+    finally:
+        be.close()
     plain = cu.run_hip(st0, steps=nsteps)
     assert {"t", "u", "v", "ubar", "vbar"} <= set(cu.differing(ref, plain)), "the sponge made no difference"
-    port = _free_port()
-    env = dict(os.environ, OMP_NUM_THREADS="1")
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "mp_gpu_clima_worker.py"), str(r), str(world), str(ntI),
-                               str(ntJ), config, str(nsteps), str(port), str(tmp_path), variant], env=env)
-             for r in range(world)]
-    try:
-        for p in procs:
-            assert p.wait(timeout=600) == 0
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    rb = ref.b
-    for r in range(world):
-        d = np.load(os.path.join(tmp_path, f"tile{r}.npz"))
-        Istr, Iend, Jstr, Jend, LBi, LBj = [int(x) for x in d["bounds"]]
-        for name in worker.FIELDS:
-            a = d[name]
-            ni, nj = a.shape[0], a.shape[1]
-            i0, j0 = LBi - rb.LBi, LBj - rb.LBj
-            want = ref[name][i0:i0 + ni, j0:j0 + nj]
-            own = (slice(Istr - LBi, Iend - LBi + 1), slice(Jstr - LBj, Jend - LBj + 1))
-            assert np.array_equal(a[own], want[own]), (name, r, float(np.abs(a[own] - want[own]).max()))
-            if name in ("zeta", "t", "Hz", "W"):      # rho-type: every ghost point is defined
-                iv = min(ni, rb.Lm + rb.NghostPoints - LBi + 1)
-                jv = min(nj, rb.Mm + 1 - LBj + 1)
-                assert np.array_equal(a[:iv, :jv], want[:iv, :jv]), (name, r, "ghost points differ")
+    tiling_util.spawn_ranks("mp_gpu_clima_worker.py", world, [ntI, ntJ, tmp_path, config, nsteps, variant], timeout=600)
+    tiling_util.assert_tiles_equal(tmp_path, world, want, ref.b, worker.FIELDS, owned="Istr:Iend",
+                                   rho_ghosts=("zeta", "t", "Hz", "W"))
 
 
 @pytest.mark.parametrize("ntI,ntJ,config,variant", [(2, 1, "BENCHMARK_TINY", ""), (1, 2, "UPWELLING", ""),

@@ -12,18 +12,14 @@ without a GPU, within the bound stated there.  Bit-equality claims get no tolera
      against one tile, bit for bit on owned points
   4. the refusals"""
 import ctypes as C
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import diags_util as du
+import tiling_util
 import util
 from roms_trunk_mgh_amd import abi, ana, diags, hip, main3d
 from test_diags import SHAPE, _state
-from test_gpu_multitile import HERE, _free_port
 
 pytestmark = pytest.mark.gpu
 
@@ -346,26 +342,11 @@ def test_two_tiles_equal_one_tile_on_owned_points(tmp_path, variant):
     finally:
         be.close()
     assert len(want) == 1 + 2 * 9 * st.b.NT and all(np.abs(a).max() > 0.0 for a in want.values())
-    port = _free_port()
-    env = dict(os.environ, OMP_NUM_THREADS="1")
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "mp_gpu_diags_worker.py"), str(r), str(world), str(ntI),
-                               str(ntJ), str(port), str(tmp_path), variant], env=env) for r in range(world)]
-    try:
-        for p in procs:
-            assert p.wait(timeout=600) == 0
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
+    tiling_util.spawn_ranks("mp_gpu_diags_worker.py", world, [ntI, ntJ, tmp_path, variant], timeout=600)
     gb = st.b
-    seen = 0
-    for r in range(world):
-        d = np.load(os.path.join(tmp_path, f"tile{r}.npz"))
-        IstrR, IendR, JstrR, JendR, LBi, LBj, UBi = [int(x) for x in d["bounds"]]
-        seen += (IendR - IstrR + 1) * (JendR - JstrR + 1)
-        for key, glob in want.items():
-            own = d[key][IstrR - LBi:IendR - LBi + 1, JstrR - LBj:JendR - LBj + 1]
-            assert np.array_equal(own, glob[IstrR - gb.LBi:IendR - gb.LBi + 1, JstrR - gb.LBj:JendR - gb.LBj + 1]), (key, r)
+    tiling_util.assert_tiles_equal(tmp_path, world, want, gb, list(want), owned="IstrR:IendR")
+    seen = sum((d["IendR"] - d["IstrR"] + 1) * (d["JendR"] - d["JstrR"] + 1)
+               for _, d, _, _ in tiling_util.tiles(tmp_path, world, gb, owned="IstrR:IendR"))
     assert seen == (gb.IendR - gb.IstrR + 1) * (gb.JendR - gb.JstrR + 1)          # the tiles' owned points cover the grid
 
 

@@ -11,17 +11,13 @@ reference's order and the build does not contract multiply-adds.
      and one tile in RCCL loopback
   4. the refusals"""
 import ctypes as C
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import floats_util as fu
+import tiling_util
 import util
 from roms_trunk_mgh_amd import ana, floats, hip, main3d
-from test_gpu_multitile import HERE, _free_port
 from test_gpu_wide import I0, LAND_ROW, SHAPES, seam_land
 
 pytestmark = pytest.mark.gpu
@@ -231,19 +227,8 @@ def _tiles_equal_single(tmp_path, world, ntI, ntJ, variant):
     finally:
         be.close()
     assert want_b.sum() > NFLOATS // 2 and not want_b.all()
-    port = _free_port()
-    env = dict(os.environ, OMP_NUM_THREADS="1")
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "mp_gpu_floats_worker.py"), str(r), str(world), str(ntI),
-                               str(ntJ), str(port), str(tmp_path), variant], env=env) for r in range(world)]
-    try:
-        for p in procs:
-            assert p.wait(timeout=600) == 0
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    for r in range(world):
-        d = np.load(os.path.join(tmp_path, f"tile{r}.npz"))
+    tiling_util.spawn_ranks("mp_gpu_floats_worker.py", world, [ntI, ntJ, tmp_path, variant], timeout=600)
+    for r, d, _, _ in tiling_util.tiles(tmp_path, world, st.b):     # the tracks are not gridded: every rank holds them all
         assert np.array_equal(d["track"], want_t, equal_nan=True), (r, np.argwhere(d["track"] != want_t)[:5].tolist())
         assert np.array_equal(d["bounded"], want_b), r
 

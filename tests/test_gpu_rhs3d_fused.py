@@ -8,18 +8,13 @@ k_t3dmix_geo<0, ISO, false, START>), and with two tracers per thread in k_pre_t.
 * 2x1 and 2x2 tiles against one tile, bit for bit.
 Every case checks that t(nnew) moved, and that it differs from the result without mixing: the start value and the
 mixing term both reached the one store."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
-import util
-from roms_trunk_mgh_amd import abi, ana, hip
-
 import mp_gpu_rhs3d_worker as worker
-from test_gpu_multitile import HERE, _free_port
+import tiling_util
+import util
+from roms_trunk_mgh_amd import abi, hip
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-12
@@ -195,31 +190,15 @@ def test_other_paths_against_oracle(case):
 def test_tiling_invariance(tmp_path, ntI, ntJ):
     """rhs3d alone after one full step, 2x1 and 2x2 tiles of UPWELLING over the host relay: every owned point equal to
     the one-tile run bit for bit (both loops cover Istr:Iend, Jstr:Jend on every tile)"""
-    ref = worker.rotated_geo(ana.make_tile("UPWELLING", perturb=1.0, overrides=worker.OVERRIDES))
+    ref = worker.tiled_state("UPWELLING")
     t_in = ref["t"].copy()
     be = hip.RomsHip(ref)
     try:
-        s = worker.one_step_then_rhs3d(be)
+        want = worker.run(be, ref)
     finally:
         be.close()
-    assert util.max_rel_diff(ref["t"][:, :, :, s.nnew - 1], t_in[:, :, :, s.nnew - 1]) > 1e-6
-    world, port = ntI * ntJ, _free_port()
-    env = dict(os.environ, OMP_NUM_THREADS="1")
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "mp_gpu_rhs3d_worker.py"), str(r), str(world), str(ntI),
-                               str(ntJ), "UPWELLING", str(port), str(tmp_path)], env=env) for r in range(world)]
-    try:
-        for p in procs:
-            assert p.wait(timeout=300) == 0
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    rb = ref.b
-    for r in range(world):
-        d = np.load(os.path.join(tmp_path, f"tile{r}.npz"))
-        Istr, Iend, Jstr, Jend, LBi, LBj = [int(x) for x in d["bounds"]]
-        own = (slice(Istr - LBi, Iend - LBi + 1), slice(Jstr - LBj, Jend - LBj + 1))
-        for name in worker.FIELDS:
-            a = d[name]
-            want = ref[name][LBi - rb.LBi:LBi - rb.LBi + a.shape[0], LBj - rb.LBj:LBj - rb.LBj + a.shape[1]]
-            assert np.array_equal(a[own], want[own]), (name, r, float(np.abs(a[own] - want[own]).max()))
+    lev = int(want["nnew"]) - 1
+    assert util.max_rel_diff(ref["t"][:, :, :, lev], t_in[:, :, :, lev]) > 1e-6
+    world = ntI * ntJ
+    tiling_util.spawn_ranks("mp_gpu_rhs3d_worker.py", world, [ntI, ntJ, tmp_path, "UPWELLING"], timeout=300)
+    tiling_util.assert_tiles_equal(tmp_path, world, want, ref.b, worker.FIELDS, owned="Istr:Iend")

@@ -15,19 +15,15 @@ restatement tests/tides_util.py, whose known answers tests/test_tides.py checks 
   4. seven steps under Main3D(tides=) against the oracle fed by the restatement each step: 1e-10 on every field
   5. tilings 2x2 and 4x1 over the relay and one tile in RCCL loopback against one tile, bit for bit
   6. the refusals"""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import curv_util as cv
 import tides_util as tu
+import tiling_util
 import util
 from roms_trunk_mgh_amd import abi, ana, hip, main3d, tides
 from test_gpu_kernels import _idx2d
-from test_gpu_multitile import HERE, _free_port
 
 pytestmark = pytest.mark.gpu
 DIMS = dict(Lm=12, Mm=10, N=4, EWperiodic=False)
@@ -246,25 +242,8 @@ def _tiles_equal_single(tmp_path, world, ntI, ntJ, variant):
     finally:
         be.close()
     assert np.abs(want["zeta_bry"]).max() > 0.05 and (("ssh" in variant) != bool(np.abs(want["ubar_bry"]).max() > 0.0))
-    port = _free_port()
-    env = dict(os.environ, OMP_NUM_THREADS="1")
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "mp_gpu_tides_worker.py"), str(r), str(world), str(ntI),
-                               str(ntJ), str(port), str(tmp_path), variant], env=env) for r in range(world)]
-    try:
-        for p in procs:
-            assert p.wait(timeout=600) == 0
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    gb = st.b
-    for r in range(world):
-        d = np.load(os.path.join(tmp_path, f"tile{r}.npz"))
-        IstrR, IendR, JstrR, JendR, LBi, LBj = [int(x) for x in d["bounds"]]
-        own = (slice(IstrR - LBi, IendR - LBi + 1), slice(JstrR - LBj, JendR - LBj + 1))
-        glob = (slice(IstrR - gb.LBi, IendR - gb.LBi + 1), slice(JstrR - gb.LBj, JendR - gb.LBj + 1))
-        for name in worker.FIELDS:
-            assert np.array_equal(d[name][own], want[name][glob]), (name, r)
+    tiling_util.spawn_ranks("mp_gpu_tides_worker.py", world, [ntI, ntJ, tmp_path, variant], timeout=600)
+    tiling_util.assert_tiles_equal(tmp_path, world, want, st.b, worker.FIELDS, owned="IstrR:IendR")
 
 
 @pytest.mark.parametrize("variant", ["uv", "ssh"])

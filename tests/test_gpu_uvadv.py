@@ -7,18 +7,14 @@ tests/test_uvadv.py), known answers where the schemes must coincide, the telesco
 error convention.  Every run ends with check_guards().
 """
 import ctypes as C
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import clima_util as cu
+import tiling_util
 import util
 import uvadv_util as uv
 from roms_trunk_mgh_amd import abi, ana, hip, main3d
-from test_gpu_multitile import HERE, _free_port
 
 pytestmark = pytest.mark.gpu
 
@@ -197,38 +193,18 @@ def test_tiled_runs_equal_the_single_tile_run(tmp_path, ntI, ntJ, h, v):
     points; (C2, C2) takes the deferred-flux 2-D call with the second-order form"""
     import mp_gpu_uvadv_worker as worker
     config, nsteps, world = "BENCHMARK_TINY", 3, ntI * ntJ
-    st0 = ana.make_tile(config, perturb=1.0, overrides={"uv_hadv": h, "uv_vadv": v})
-    assert st0.p.uv_adv == abi.uv_adv(h, v)
-    ref = cu.run_hip(st0, steps=nsteps)
+    ref = worker.tiled_state(config, h, v)
+    assert ref.p.uv_adv == abi.uv_adv(h, v)
+    be = hip.RomsHip(ref)
+    try:
+        want = worker.run(be, ref, nsteps)
+    finally:
+        be.close()
     plain = cu.run_hip(ana.make_tile(config, perturb=1.0), steps=nsteps)
     assert {"u", "v", "ubar", "vbar"} <= set(cu.differing(ref, plain)), "the scheme made no difference"
-    port = _free_port()
-    env = dict(os.environ, OMP_NUM_THREADS="1")
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "mp_gpu_uvadv_worker.py"), str(r), str(world), str(ntI),
-                               str(ntJ), config, str(nsteps), str(port), str(tmp_path), h, v], env=env)
-             for r in range(world)]
-    try:
-        for p in procs:
-            assert p.wait(timeout=600) == 0
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    rb = ref.b
-    for r in range(world):
-        d = np.load(os.path.join(tmp_path, f"tile{r}.npz"))
-        Istr, Iend, Jstr, Jend, LBi, LBj = [int(x) for x in d["bounds"]]
-        for name in worker.FIELDS:
-            a = d[name]
-            ni, nj = a.shape[0], a.shape[1]
-            i0, j0 = LBi - rb.LBi, LBj - rb.LBj
-            want = ref[name][i0:i0 + ni, j0:j0 + nj]
-            own = (slice(Istr - LBi, Iend - LBi + 1), slice(Jstr - LBj, Jend - LBj + 1))
-            assert np.array_equal(a[own], want[own]), (name, r, float(np.abs(a[own] - want[own]).max()))
-            if name in ("zeta", "t", "Hz", "W"):      # rho-type: every ghost point is defined
-                iv = min(ni, rb.Lm + rb.NghostPoints - LBi + 1)
-                jv = min(nj, rb.Mm + 1 - LBj + 1)
-                assert np.array_equal(a[:iv, :jv], want[:iv, :jv]), (name, r, "ghost points differ")
+    tiling_util.spawn_ranks("mp_gpu_uvadv_worker.py", world, [ntI, ntJ, tmp_path, config, nsteps, h, v], timeout=600)
+    tiling_util.assert_tiles_equal(tmp_path, world, want, ref.b, worker.FIELDS, owned="Istr:Iend",
+                                   rho_ghosts=("zeta", "t", "Hz", "W"))
 
 
 # --------------------------------------------------------------- 6. graph --

@@ -3,22 +3,17 @@ roms_params_t.uv_vis4 = 2).  k_uv4_geo_first / k_uv4_geo_second through the C AB
 tests/uvgeo4_util.py (pinned without a GPU in tests/test_uvgeo4.py): the CPU oracle has no uv3dmix4_geo -- with
 uv_vis4 = 2 it computes the s-surface operator -- so no whole step is compared with it here.  The kernels evaluate the
 reference's expressions in the reference's order: the comparisons are for identical bits."""
-import os
-import socket
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import curv_util as cv
 import reuse_util as ru
 import test_gpu_wide as wide
+import tiling_util
 import util
 import uvgeo4_util as G
-from roms_trunk_mgh_amd import abi, ana, hip, main3d
+from roms_trunk_mgh_amd import abi, ana, hip
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 pytestmark = pytest.mark.gpu
 # the viscosities of tests/test_gpu_biharmonic.py; MIX_GEO_UV is one switch for both operators: uv_vis2 = 2 as well
 VIS4 = {"UPWELLING": {"uv_vis2": 2, "uv_vis4": 2, "visc4": 4.0e7},
@@ -106,52 +101,24 @@ def test_workgroup_seams(variant, wet, curv):
     _same(st_h, st_n, st0)
 
 
-def _free_port():
-    q = socket.socket()
-    q.bind(("127.0.0.1", 0))
-    port = q.getsockname()[1]
-    q.close()
-    return port
-
-
 @pytest.mark.parametrize("ntI,ntJ", [(2, 1), (1, 2)])
 def test_tilings(tmp_path, ntI, ntJ):
     """five whole steps with uv_vis2 = 2, uv_vis4 = 2 on masked BENCHMARK_TINY as a closed basin: two tiles against one,
     owned points bit for bit, every field finite"""
     import mp_gpu_uvgeo4_worker as worker
     nsteps = 5
-    ref = worker.make()
+    ref = worker.tiled_state()
     assert ref.p.uv_vis2 == 2 and ref.p.uv_vis4 == 2 and ref.p.masking == 1 and not ref.b.EWperiodic
     be = hip.RomsHip(ref)
     try:
-        m = main3d.Main3D(be)
-        m.initial()
-        m.run(nsteps)
-        be.to_host()
+        want = worker.run(be, ref, nsteps)
     finally:
         be.close()
-    port = _free_port()
-    env = dict(os.environ, OMP_NUM_THREADS="1")
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "mp_gpu_uvgeo4_worker.py"), str(r), "2", str(ntI), str(ntJ),
-                               str(nsteps), str(port), str(tmp_path)], env=env) for r in range(2)]
-    try:
-        for p in procs:
-            assert p.wait(timeout=300) == 0
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    rb = ref.b
-    for r in range(2):
-        d = np.load(os.path.join(tmp_path, f"tile{r}.npz"))
-        Istr, Iend, Jstr, Jend, LBi, LBj = [int(x) for x in d["bounds"]]
+    tiling_util.spawn_ranks("mp_gpu_uvgeo4_worker.py", 2, [ntI, ntJ, tmp_path, nsteps], timeout=300)
+    for r, d, _, _ in tiling_util.tiles(tmp_path, 2, ref.b):
         for name in worker.FIELDS:
-            a = d[name]
-            assert np.isfinite(a).all() and np.isfinite(ref[name]).all(), name
-            i0, j0 = LBi - rb.LBi, LBj - rb.LBj
-            want = ref[name][i0:i0 + a.shape[0], j0:j0 + a.shape[1]]
-            own = (slice(Istr - LBi, Iend - LBi + 1), slice(Jstr - LBj, Jend - LBj + 1))
-            assert np.array_equal(a[own], want[own]), (name, r, float(np.abs(a[own] - want[own]).max()))
+            assert np.isfinite(d[name]).all() and np.isfinite(want[name]).all(), name
+    tiling_util.assert_tiles_equal(tmp_path, 2, want, ref.b, worker.FIELDS, owned="Istr:Iend")
 
 
 def test_the_switch_acts():

@@ -8,18 +8,12 @@ and of HSIMT -- the entries refuse them.)
 CPU: properties of the masked discretisation on the oracle -- land stays land, volume and tracer content are
 conserved around an island and a headland, and every tiling gives the same answer.  GPU (-m gpu): every
 kernel and whole steps, HIP against the oracle on the same masked state."""
-import os
-import socket
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import util
 from roms_trunk_mgh_amd import ana, main3d
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 CONFIGS = ["BENCHMARK_TINY", "UPWELLING", "SEAMOUNT"]
 
 
@@ -70,38 +64,18 @@ def test_oracle_land_stays_land_and_content_is_conserved(config, adv):
     assert abs(content(s.nnew - 1, it) - c0) <= 2e-11 * abs(c0), (content(s.nnew - 1, it), c0)
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def test_oracle_masked_tilings_agree(tmp_path):
     """2x2 tiles of the masked grid (the island straddles a tile corner) = the one-tile run, bit for bit."""
+    import mp_worker as worker
     import oracle
+    import tiling_util
     world, nsteps, config = 4, 3, "BENCHMARK_TINY"
-    port = _free_port()
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "mp_worker.py"), str(r), str(world), "2", "2",
-                               config, str(nsteps), str(port), str(tmp_path), "mask"],
-                              env=dict(os.environ, OMP_NUM_THREADS="1")) for r in range(world)]
-    for p in procs:
-        assert p.wait(timeout=600) == 0
-    ref = ana.make_tile(config, perturb=1.0, mask="island")
-    m = main3d.Main3D(oracle.Oracle(ref))
-    m.initial()
-    m.run(nsteps)
-    rb = ref.b
-    for r in range(world):
-        d = np.load(os.path.join(tmp_path, f"tile{r}.npz"))
-        Istr, Iend, Jstr, Jend, LBi, LBj = [int(x) for x in d["bounds"]]
-        for name in ("zeta", "ubar", "vbar", "u", "v", "t", "Huon", "W", "Hz"):
-            a = d[name]
-            i0, j0 = LBi - rb.LBi, LBj - rb.LBj
-            want = ref[name][i0:i0 + a.shape[0], j0:j0 + a.shape[1]]
-            own = (slice(Istr - LBi, Iend - LBi + 1), slice(Jstr - LBj, Jend - LBj + 1))
-            assert np.array_equal(a[own], want[own]), (name, r, float(np.abs(a[own] - want[own]).max()))
+    tiling_util.spawn_ranks("mp_worker.py", world, [2, 2, tmp_path, config, nsteps, "mask"], timeout=600)
+    ref = worker.tiled_state(config, "mask")
+    assert ref.p.masking == 1
+    want = worker.run(oracle.Oracle(ref), ref, nsteps)
+    tiling_util.assert_tiles_equal(tmp_path, world, want, ref.b, ("zeta", "ubar", "vbar", "u", "v", "t", "Huon", "W", "Hz"),
+                                   owned="Istr:Iend")
 
 
 # ------------------------------------------------------------------------------------------- GPU

@@ -4,56 +4,21 @@ restated in roms_trunk_mgh_amd/halo.py; after 3 full steps every tile's owned
 points AND ghost points must equal the single-tile run bit for bit -- the
 reference's own acceptance rule ("identical results across tilings")."""
 import os
-import socket
 import subprocess
 import sys
 
-import numpy as np
 import pytest
 
-import util
-from roms_trunk_mgh_amd import ana, main3d
+import mp_worker as worker
+import tiling_util
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _single(config, nsteps, variant=""):
     import oracle
-    opts = set(variant.split("+")) if variant else set()
-    kw = dict(NT=6, overrides={"Hadv": "MPDATA", "Vadv": "MPDATA"}) if "mpdata" in opts else {}
-    if "hsimt" in opts:
-        kw = dict(overrides={"Hadv": "HSIMT", "Vadv": "HSIMT"})
-    if "mask" in opts:
-        kw["mask"] = "island"
-    if "dif4" in opts:                   # biharmonic mixing (three ghost points with UV_VIS4)
-        kw.setdefault("overrides", {}).update({"ts_dif4": 1, "uv_vis4": 1, "tnu4": 1.0e10, "visc4": 2.0e10})
-    if "basin" in opts:                  # no periodic direction
-        kw.setdefault("overrides", {})["EWperiodic"] = False
-    if "classic" in opts:                # without SPLINES_VVISC / SPLINES_VDIFF: the tridiagonal systems for u, v, t themselves
-        kw.setdefault("overrides", {}).update({"splines_vdiff": 0, "splines_vvisc": 0})
-    if "gls" in opts:                    # GLS_MIXING (k-epsilon, Kantha-Clayson, N2S2_HORAVG, RI_SPLINES)
-        kw.setdefault("overrides", {})["gls"] = "k-epsilon"
-    if "my25" in opts:                   # MY25_MIXING (Kantha-Clayson, N2S2_HORAVG, RI_SPLINES)
-        kw.setdefault("overrides", {})["gls"] = "my25"
-    if "geouv" in opts:                  # UV_VIS2 with MIX_GEO_UV (uv3dmix2_geo.h)
-        kw.setdefault("overrides", {}).update({"uv_vis2": 2, **({"visc2": 50.0} if config == "SEAMOUNT" else {})})
-    if "wet" in opts:                    # WET_DRY on the beach bathymetry of ana.py (the shoreline crosses tile edges)
-        kw.setdefault("overrides", {}).update({"wet_dry": 1, "beach": 1, "zeta_amp": 0.3})
-    st = ana.make_tile(config, perturb=1.0, **kw)
-    if "river" in opts:                  # point sources (LuvSrc) in the walls and, with a mask, on the island's coast
-        util.river_sources(st, "all" if "wells" in opts else "both" if "mask" in opts else "walls")
-    m = main3d.Main3D(oracle.Oracle(st))
-    m.initial()
-    m.run(nsteps)
-    return st
+    st = worker.tiled_state(config, variant)
+    return st, worker.run(oracle.Oracle(st), st, nsteps)
 
 
 @pytest.mark.parametrize("ntI,ntJ,config,variant", [(2, 1, "UPWELLING", ""), (1, 2, "UPWELLING", ""),
@@ -92,32 +57,10 @@ def _single(config, nsteps, variant=""):
 def test_tiled_equals_single(tmp_path, ntI, ntJ, config, variant):
     nsteps = 3
     world = ntI * ntJ
-    port = _free_port()
-    env = dict(os.environ, OMP_NUM_THREADS="1")
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "mp_worker.py"), str(r), str(world), str(ntI),
-                               str(ntJ), config, str(nsteps), str(port), str(tmp_path), variant], env=env)
-             for r in range(world)]
-    for p in procs:
-        assert p.wait(timeout=600) == 0
-    ref = _single(config, nsteps, variant)
-    rb = ref.b
-    for r in range(world):
-        d = np.load(os.path.join(tmp_path, f"tile{r}.npz"))
-        Istr, Iend, Jstr, Jend, LBi, LBj = [int(x) for x in d["bounds"]]
-        for name in ("zeta", "ubar", "vbar", "u", "v", "t", "Huon", "W", "Hz", "Akv", "tke", "rmask_wet", "umask_wet",
-                     "vmask_wet", "pmask_wet", "rmask_wet_avg"):
-            a = d[name]
-            ni, nj = a.shape[0], a.shape[1]
-            # whole allocated tile (owned + ghost points) against the same index range of the single-tile run
-            i0, j0 = LBi - rb.LBi, LBj - rb.LBj
-            want = ref[name][i0:i0 + ni, j0:j0 + nj]
-            own = (slice(Istr - LBi, Iend - LBi + 1), slice(Jstr - LBj, Jend - LBj + 1))
-            assert np.array_equal(a[own], want[own]), (name, r, float(np.abs(a[own] - want[own]).max()))
-            if name in ("zeta", "t", "Hz", "W", "rmask_wet"):      # rho-type: every ghost point is defined
-                # (not the reference's spare padding column/row of even-sized grids, Im=Lm+1/Jm=Mm+1)
-                iv = min(ni, rb.Lm + rb.NghostPoints - LBi + 1)
-                jv = min(nj, rb.Mm + 1 - LBj + 1)
-                assert np.array_equal(a[:iv, :jv], want[:iv, :jv]), (name, r, "ghost points differ")
+    tiling_util.spawn_ranks("mp_worker.py", world, [ntI, ntJ, tmp_path, config, nsteps, variant], timeout=600)
+    ref, want = _single(config, nsteps, variant)
+    tiling_util.assert_tiles_equal(tmp_path, world, want, ref.b, tiling_util.FIELDS, owned="Istr:Iend",
+                                   rho_ghosts=("zeta", "t", "Hz", "W", "rmask_wet"))
 
 
 MPIEXEC = "/opt/conda/bin/mpiexec"
@@ -135,19 +78,7 @@ def test_mpi_baseline_layer_equals_single(tmp_path, ntI, ntJ, config):
                         config, "2", "0", str(ntI), str(ntJ), str(tmp_path)],
                        env=dict(os.environ, OMP_NUM_THREADS="1", PYTHONPATH=root), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-800:]
-    ref = _single(config, 3)
-    rb = ref.b
-    for q in range(world):
-        d = np.load(os.path.join(tmp_path, f"tile{q}.npz"))
-        Istr, Iend, Jstr, Jend, LBi, LBj = [int(x) for x in d["bounds"]]
-        for name in ("zeta", "ubar", "vbar", "u", "v", "t", "Huon", "W", "Hz", "Akv", "tke"):
-            a = d[name]
-            ni, nj = a.shape[0], a.shape[1]
-            i0, j0 = LBi - rb.LBi, LBj - rb.LBj
-            want = ref[name][i0:i0 + ni, j0:j0 + nj]
-            own = (slice(Istr - LBi, Iend - LBi + 1), slice(Jstr - LBj, Jend - LBj + 1))
-            assert np.array_equal(a[own], want[own]), (name, q, float(np.abs(a[own] - want[own]).max()))
-            if name in ("zeta", "t", "Hz", "W"):
-                iv = min(ni, rb.Lm + rb.NghostPoints - LBi + 1)
-                jv = min(nj, rb.Mm + 1 - LBj + 1)
-                assert np.array_equal(a[:iv, :jv], want[:iv, :jv]), (name, q, "ghost points differ")
+    ref, want = _single(config, 3)
+    tiling_util.assert_tiles_equal(tmp_path, world, want, ref.b,
+                                   ("zeta", "ubar", "vbar", "u", "v", "t", "Huon", "W", "Hz", "Akv", "tke"),
+                                   owned="Istr:Iend", rho_ghosts=("zeta", "t", "Hz", "W"))
