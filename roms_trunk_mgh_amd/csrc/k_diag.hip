@@ -5,7 +5,7 @@
 //                                       maximum speed and density (SOLVE3D branch)
 // diag: the reference sums j first and then i (diag.F:262-290) and finds the Courant maximum in loop order
 // (j ascending, k descending, i ascending; strict ">"): three kernels reproduce both bit for bit --
-// per column, per i (serial in j), one thread (serial in i).  The global reduction over tiles (mp_reduce,
+// per column, per i (serial in j), one wavefront per sum (serial in i).  The global reduction over tiles (mp_reduce,
 // mp_reduce2 MAXLOC; diag.F:398-420) stays with the caller.
 #include "roms_dev.h"
 
@@ -166,11 +166,14 @@ k_diag_rows(const RomsDev *__restrict__ c, DiagScratch w, double *__restrict__ R
   R[R_SPD * nI + o] = mspd; R[R_RHO * nI + o] = mrho;
 }
 
-// diag.F:281-290, one workgroup.  The three sums are serial in i (the reference's order): the partial rows are
-// staged in LDS chunk by chunk and three wavefronts run one chain each, 16 values per round.  The maxima need no
-// order: "first strict maximum in loop order" = the largest C, ties to the smallest j, then the largest k, then
-// the smallest i -- a total order, so all threads scan a share and an LDS tree finishes.
-#define DIAG_CH 512
+// diag.F:281-290, one workgroup of four wavefronts.  The three sums are serial in i (the reference's order): a
+// wavefront per sum brings DIAG_CH partials at a time into LDS (coalesced, all loads in flight at once) and then adds
+// them one at a time in i order, every lane reading the same LDS word: no memory wait inside the chain, and the LDS
+// reads of a run of 64 are issued ahead of its additions.  The maxima need no order: "first strict maximum in loop
+// order" = the largest C, ties to the smallest j, then the largest k, then the smallest i -- a total order, so the
+// fourth wavefront scans a share per lane and finishes with a butterfly, meanwhile.
+#define DIAG_RUN 32
+#define DIAG_CH (64 * DIAG_RUN)
 struct DiagBest { double C, Cu, Cv, Cw; int i, j, k; };
 __device__ __forceinline__ bool diag_better(const DiagBest &x, const DiagBest &y)     // x ahead of y?
 {
@@ -184,61 +187,77 @@ __global__ void __launch_bounds__(256)
 k_diag_final(const RomsDev *__restrict__ c, const double *__restrict__ R, double *__restrict__ out)
 {
   const roms_bounds_t &b = c->b;
-  __shared__ double sR[3 * DIAG_CH];
-  __shared__ DiagBest sB[256];
-  __shared__ double sSpd[256], sRho[256];
+  __shared__ double sR[3][DIAG_CH];
   const int nI = b.Iend - b.Istr + 1;
-  const int tid = threadIdx.x;
-  // ---- maxima ----
-  DiagBest best{0.0, 0.0, 0.0, 0.0, 0, 0, 0};
-  double mspd = 0.0, mrho = -1.0E+37;
-  for (int o = tid; o < nI; o += 256) {
-    DiagBest x{R[R_C * nI + o], R[R_CU * nI + o], R[R_CV * nI + o], R[R_CW * nI + o], b.Istr + o,
-               (int)R[R_CJ * nI + o], (int)R[R_CK * nI + o]};
-    if (diag_better(x, best)) best = x;
-    mspd = fmax(mspd, R[R_SPD * nI + o]);
-    mrho = fmax(mrho, R[R_RHO * nI + o]);
-  }
-  sB[tid] = best; sSpd[tid] = mspd; sRho[tid] = mrho;
-  __syncthreads();
-  for (int st = 128; st >= 1; st >>= 1) {
-    if (tid < st) {
-      if (diag_better(sB[tid + st], sB[tid])) sB[tid] = sB[tid + st];
-      sSpd[tid] = fmax(sSpd[tid], sSpd[tid + st]);
-      sRho[tid] = fmax(sRho[tid], sRho[tid + st]);
-    }
-    __syncthreads();
-  }
-  // ---- sums, serial in i ----
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  // ---- sums, serial in i: wavefront 0 volume, 1 potential, 2 kinetic energy (the fourth only meets the barriers
+  // and goes on to the maxima) ----
+  const int row = wave < 3 ? wave : 0;
+  const double *src = R + (long)(row == 0 ? R_VOL : (row == 1 ? R_PE : R_KE)) * nI;
   double acc = 0.0;
-  const int chain = tid / 64;                         // wavefront 0: volume, 1: potential, 2: kinetic energy
   for (int o0 = 0; o0 < nI; o0 += DIAG_CH) {
     const int n = (nI - o0 < DIAG_CH) ? nI - o0 : DIAG_CH;
-    __syncthreads();
-    for (int e = tid; e < 3 * DIAG_CH; e += 256) {
-      const int r = e / DIAG_CH, q = e % DIAG_CH;
-      sR[e] = (q < n) ? R[(r == 0 ? R_VOL : (r == 1 ? R_PE : R_KE)) * nI + o0 + q] : 0.0;
+    if (o0 > 0) __syncthreads();                                     // the chunk before has been added
+    if (wave < 3) {
+      double v[DIAG_RUN];
+#pragma unroll
+      for (int q = 0; q < DIAG_RUN; q++) {
+        const int e = q * 64 + lane;
+        v[q] = src[o0 + (e < n ? e : n - 1)];                        // clamped: unused beyond n
+      }
+#pragma unroll
+      for (int q = 0; q < DIAG_RUN; q++) sR[row][q * 64 + lane] = v[q];
     }
     __syncthreads();
-    if ((tid & 63) == 0 && chain < 3) {
-      const double *src = sR + chain * DIAG_CH;
-      for (int q0 = 0; q0 < n; q0 += 16) {
-        double t[16];
+    if (wave < 3) {
+      const double *sv = sR[row];
+      int e = 0;
+      for (; e + 64 <= n; e += 64) {                                 // a run: every read issued, then the additions
+        double t[64];
 #pragma unroll
-        for (int q = 0; q < 16; q++) t[q] = src[q0 + q < DIAG_CH ? q0 + q : DIAG_CH - 1];
+        for (int q = 0; q < 64; q++) t[q] = sv[e + q];
 #pragma unroll
-        for (int q = 0; q < 16; q++)
-          if (q0 + q < n) acc = acc + t[q];
+        for (int q = 0; q < 64; q++) acc = acc + t[q];
       }
+      for (; e < n; e++) acc = acc + sv[e];
     }
   }
-  if (tid == 0) out[0] = acc;
-  if (tid == 64) out[2] = acc;
-  if (tid == 128) out[1] = acc;
-  if (tid == 192) {
-    out[3] = sSpd[0]; out[4] = sRho[0];
-    out[5] = sB[0].C; out[6] = sB[0].Cu; out[7] = sB[0].Cv; out[8] = sB[0].Cw;
-    out[9] = (double)sB[0].i; out[10] = (double)sB[0].j; out[11] = (double)sB[0].k;
+  if (wave < 3 && lane == 0) out[row == 0 ? 0 : (row == 1 ? 2 : 1)] = acc;
+  if (wave == 3) {
+    // ---- maxima ----
+    DiagBest best{0.0, 0.0, 0.0, 0.0, 0, 0, 0};
+    double mspd = 0.0, mrho = -1.0E+37;
+    for (int o0 = lane; o0 < nI; o0 += 64 * 8) {                     // eight candidates per lane loaded at once
+      double t[8][8];
+#pragma unroll
+      for (int q = 0; q < 8; q++) {
+        const int o = (o0 + 64 * q < nI) ? o0 + 64 * q : nI - 1;       // clamped: unused beyond nI
+        t[q][0] = R[R_C * nI + o]; t[q][1] = R[R_CU * nI + o]; t[q][2] = R[R_CV * nI + o]; t[q][3] = R[R_CW * nI + o];
+        t[q][4] = R[R_CJ * nI + o]; t[q][5] = R[R_CK * nI + o]; t[q][6] = R[R_SPD * nI + o]; t[q][7] = R[R_RHO * nI + o];
+      }
+#pragma unroll
+      for (int q = 0; q < 8; q++) {
+        const int o = o0 + 64 * q;
+        if (o < nI) {
+          const DiagBest x{t[q][0], t[q][1], t[q][2], t[q][3], b.Istr + o, (int)t[q][4], (int)t[q][5]};
+          if (diag_better(x, best)) best = x;
+          mspd = fmax(mspd, t[q][6]);
+          mrho = fmax(mrho, t[q][7]);
+        }
+      }
+    }
+    for (int m = 32; m >= 1; m >>= 1) {
+      const DiagBest y{__shfl_xor(best.C, m), __shfl_xor(best.Cu, m), __shfl_xor(best.Cv, m), __shfl_xor(best.Cw, m),
+                       __shfl_xor(best.i, m), __shfl_xor(best.j, m), __shfl_xor(best.k, m)};
+      if (diag_better(y, best)) best = y;
+      mspd = fmax(mspd, __shfl_xor(mspd, m));
+      mrho = fmax(mrho, __shfl_xor(mrho, m));
+    }
+    if (lane == 0) {
+      out[3] = mspd; out[4] = mrho;
+      out[5] = best.C; out[6] = best.Cu; out[7] = best.Cv; out[8] = best.Cw;
+      out[9] = (double)best.i; out[10] = (double)best.j; out[11] = (double)best.k;
+    }
   }
 }
 

@@ -200,19 +200,7 @@ k_pre_uv(const RomsDev *__restrict__ c, int nstp, int nnew, int nrhs, int stage)
       }
       const double hzs = Hz[ck] + Hz[ck - off];
       const double d = FCk - FCprev;
-      double out;
-      if (stage == 0) {
-        const double a = vk * 0.5 * hzs;
-        out = a + d;
-      } else if (stage == 1) {
-        const double a = vk * 0.5 * hzs;
-        const double c3 = 0.5 * DC0;
-        out = a - c3 * r2[ck + nij] + d;
-      } else {
-        const double a = vk * 0.5 * hzs;
-        out = a + DC0 * ((5.0 / 12.0) * r1[ck + nij] - (16.0 / 12.0) * r2[ck + nij]) + d;
-      }
-      vnew[ck] = out;
+      vnew[ck] = uv_start(stage, vk, hzs, DC0, r1, r2, ck + nij, d);
       FCprev = FCk;
       vk = vk1;
     }
@@ -331,8 +319,9 @@ static int pre_step3d_uv(const roms_step_idx_t *s)
   return 0;
 }
 
-// fused (roms_hip_rhs3d alone, roms_dev.h): t(nnew) is left to the mixing kernel that follows
-int pre_step3d_entry(const roms_step_idx_t *s, bool fused)
+// fused (roms_hip_rhs3d alone, roms_dev.h): t(nnew) is left to the mixing kernel that follows;
+// uvstart: u, v(nnew) are left to the pressure-gradient kernel that follows
+int pre_step3d_entry(const roms_step_idx_t *s, bool fused, bool uvstart)
 {
   int rc = roms_entry_check("roms_hip_pre_step3d");
   if (rc) return rc;
@@ -341,8 +330,8 @@ int pre_step3d_entry(const roms_step_idx_t *s, bool fused)
   if ((rc = dia_check("roms_hip_pre_step3d"))) return rc;
   ScopedTimer tm("pre_step3d");
   // (the reference does the tracers first; the two halves share no output)
-  if ((rc = pre_step3d_uv(s))) return rc;
+  if (!uvstart && (rc = pre_step3d_uv(s))) return rc;
   return pre_step3d_tracers(s, fused);
 }
 
-extern "C" int roms_hip_pre_step3d(const roms_step_idx_t *s) { return pre_step3d_entry(s, false); }
+extern "C" int roms_hip_pre_step3d(const roms_step_idx_t *s) { return pre_step3d_entry(s, false, false); }

@@ -485,6 +485,21 @@ static bool rhs3d_fuses_tstart(const roms_step_idx_t *s)
          s->nrhs == s->nstp;
 }
 
+// Inside roms_hip_rhs3d the predictor's start of u, v(nnew) (k_pre_uv) moves into the pressure-gradient kernel of
+// prsgrd32 (k_prsgrd.hip, k_prsgrd32<true>): that kernel overwrites ru, rv(nrhs) at exactly the point whose old value the
+// start has just read as its AB3 term, and both read Hz of the same two cells.  Nothing between the two reads u, v(nnew) or
+// ru, rv: the tracer half of the predictor reads neither, t3dbc_tile and the exchanges at its end act on t(3)
+// (pre_step3d.F:1131-1149).  With lambda = 1 the explicit vertical viscous flux is identically zero, so the start at level
+// k needs level k alone (and the stresses at k = 1 and k = N) and the downward march of the pressure kernel gives the bits
+// of the upward one.  With an explicit part (lambda < 1) or another pressure-gradient algorithm the two entries run as they
+// do on their own.
+static bool rhs3d_fuses_uvstart(const roms_step_idx_t *s)
+{
+  (void)s;
+  const roms_params_t &p = g_ctx.p;
+  return p.pgf == PGF_DJ_GRADPS && p.lambda == 1.0;
+}
+
 int roms_uv_mix_check(const char *where);    // k_uv3dmix2.hip
 
 // rhs3d(ng,tile) -- rhs3d.F:25-170: pre_step3d, prsgrd, t3dmix2, t3dmix4, rhs3d_tile, uv3dmix2, uv3dmix4
@@ -495,8 +510,9 @@ extern "C" int roms_hip_rhs3d(const roms_step_idx_t *s)
   if ((rc = roms_uv_adv_check("roms_hip_rhs3d"))) return rc;          // before the first piece has changed anything
   if ((rc = roms_uv_mix_check("roms_hip_rhs3d"))) return rc;
   const bool fused = rhs3d_fuses_tstart(s);
-  if ((rc = pre_step3d_entry(s, fused))) return rc;
-  if ((rc = roms_hip_prsgrd(s))) return rc;
+  const bool uvstart = rhs3d_fuses_uvstart(s);
+  if ((rc = pre_step3d_entry(s, fused, uvstart))) return rc;
+  if ((rc = prsgrd_entry(s, uvstart))) return rc;
   if (g_ctx.p.ts_dif2 && (rc = t3dmix2_entry(s, fused))) return rc;
   if (g_ctx.p.ts_dif4 && (rc = roms_hip_t3dmix4(s))) return rc;
   if ((rc = roms_hip_rhs3d_tile(s))) return rc;

@@ -234,6 +234,27 @@ typedef double __attribute__((address_space(1))) *gd_t;
 // field `name` of the constant block as a global-address-space pointer (device code with `c` in scope)
 #define GF(name) ((gd_t)c->F.name)
 
+// The predictor's start of u or v(nnew) at one point (pre_step3d.F:1040-1110; k_pre_uv, and k_prsgrd32<true> inside
+// roms_hip_rhs3d).  stage: 0 = first step (forward Euler), 1 = second step (AB2), 2 = AB3.  vk: u or v(nstp); hzs: the sum
+// of Hz over the face's two cells; r1, r2: ru or rv at nrhs and 3 - nrhs, read at q where the stage uses them;
+// d: FC(k) - FC(k-1) of the explicit vertical viscous flux.
+__device__ __forceinline__ double uv_start(int stage, double vk, double hzs, double DC0, gcd_t r1, gcd_t r2, long q, double d)
+{
+  double out;
+  if (stage == 0) {
+    const double a = vk * 0.5 * hzs;
+    out = a + d;
+  } else if (stage == 1) {
+    const double a = vk * 0.5 * hzs;
+    const double c3 = 0.5 * DC0;
+    out = a - c3 * r2[q] + d;
+  } else {
+    const double a = vk * 0.5 * hzs;
+    out = a + DC0 * ((5.0 / 12.0) * r1[q] - (16.0 / 12.0) * r2[q]) + d;
+  }
+  return out;
+}
+
 // WET_DRY: the land/sea mask of a point times its wet/dry mask.  Wherever the reference multiplies by the wet/dry mask
 // directly after the land/sea mask (x = x*umask; x = x*umask_wet -- every WET_DRY block of the mixing, bulk-flux,
 // MPDATA, step3d_uv and ini_fields files) the two small-integer factors combine exactly, signed zeros included:
@@ -432,7 +453,10 @@ int check_lbc();
 // roms_hip_pre_step3d / roms_hip_t3dmix2 as roms_hip_rhs3d runs them.  fused (k_rhs3d.hip: rhs3d_fuses_tstart()): the
 // predictor leaves t(nnew) alone and the rotated mixing kernel stores Hz*t(nstp) + the explicit vertical flux
 // divergence + its own term in one write; the two extern "C" entries pass false.
-int pre_step3d_entry(const roms_step_idx_t *s, bool fused);   // k_pre_step3d.hip
+// uvstart (k_rhs3d.hip: rhs3d_fuses_uvstart()): the predictor leaves u, v(nnew) to the pressure-gradient kernel, which
+// forms them at the point whose ru, rv(nrhs) it is about to overwrite.
+int pre_step3d_entry(const roms_step_idx_t *s, bool fused, bool uvstart);   // k_pre_step3d.hip
+int prsgrd_entry(const roms_step_idx_t *s, bool uvstart);     // k_prsgrd.hip
 int t3dmix2_entry(const roms_step_idx_t *s, bool fused);      // k_mix.hip
 int roms_rowm_prepare();               // k_step2d_mom.hip: examine the metric arrays if needed (synchronises once)
 void roms_rowm_invalidate();            // a metric array may have changed
