@@ -82,7 +82,11 @@ class Oracle:
         fn = getattr(self.l, "oracle_" + kernel)
         rc = fn(C.byref(self.st.b), C.byref(self.st.p), C.byref(s), C.byref(self.F))
         if rc != 0:
-            raise RuntimeError(f"oracle_{kernel} returned {rc}")
+            why = ""
+            if rc == 12:                                     # o_uv_mix_check: the refusal carries its text
+                self.l.oracle_last_error.restype = C.c_char_p
+                why = ": " + self.l.oracle_last_error().decode()
+            raise RuntimeError(f"oracle_{kernel} returned {rc}{why}")
 
     def ana_srflux(self, yday, hour):
         self.l.oracle_ana_srflux.restype = C.c_int

@@ -214,6 +214,9 @@ int oracle_t3dmix2_iso(OARGS);
 int oracle_rhs3d_tile(OARGS);
 int oracle_uv3dmix2(OARGS);
 int oracle_uv3dmix2_geo(OARGS);      /* uv3dmix2_geo.h (uv_vis2 = 2: MIX_GEO_UV) */
+int oracle_uv3dmix4_geo(OARGS);      /* uv3dmix4_geo.h (uv_vis4 = 2: MIX_GEO_UV) */
+int o_uv_mix_check(const roms_params_t *p, const char *where);   /* refuses (uv_vis2, uv_vis4) = (1, 2), (2, 1) */
+const char *oracle_last_error(void); /* the text of the last refusal */
 int oracle_rhs3d(OARGS);
 int oracle_step2d(OARGS);
 int oracle_step3d_uv(OARGS);

@@ -175,6 +175,8 @@ int oracle_t3dmix2(OARGS)
 
 int oracle_uv3dmix2(OARGS)
 {
+  int rc_mix;
+  if ((rc_mix = o_uv_mix_check(p, "oracle_uv3dmix2"))) return rc_mix;
   if (p->uv_vis2 == 2) return oracle_uv3dmix2_geo(b, p, s, F);     /* MIX_GEO_UV: oracle_uvmix_geo.c */
   ORACLE_PROLOGUE
   const int nrhs = s->nrhs, nnew = s->nnew;

@@ -486,6 +486,9 @@ int oracle_t3dmix4(OARGS)
 /* uv3dmix4_s_tile -- uv3dmix4_s.h:255-625 */
 int oracle_uv3dmix4(OARGS)
 {
+  int rc_mix;
+  if ((rc_mix = o_uv_mix_check(p, "oracle_uv3dmix4"))) return rc_mix;
+  if (p->uv_vis4 == 2) return oracle_uv3dmix4_geo(b, p, s, F);     /* MIX_GEO_UV: oracle_uvmix_geo.c */
   ORACLE_PROLOGUE
   const int nrhs = s->nrhs, nnew = s->nnew;
   const double dt = p->dt, gamma2 = p->gamma2;

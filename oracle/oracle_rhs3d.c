@@ -238,6 +238,7 @@ int oracle_rhs3d_tile(OARGS)
 int oracle_rhs3d(OARGS)
 {
   int rc;
+  if ((rc = o_uv_mix_check(p, "oracle_rhs3d"))) return rc;      /* before anything is changed */
   if ((rc = oracle_pre_step3d(b, p, s, F))) return rc;
   if ((rc = oracle_prsgrd(b, p, s, F))) return rc;
   if (p->ts_dif2 && (rc = oracle_t3dmix2(b, p, s, F))) return rc;

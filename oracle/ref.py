@@ -22,6 +22,10 @@ def available(app):
 
 class Ref:
     def __init__(self, state):
+        if state.p.uv_vis4 == 2 and state.p.uv_vis2 != 2:
+            # MIX_GEO_UV is one CPP switch for both operators: no build has uv3dmix4_geo.h beside uv3dmix2_s.h or
+            # without UV_VIS2, and a _DIF4 build would run uv3dmix4_s.h in its place
+            raise RuntimeError("no reference build for uv_vis4 = 2 (MIX_GEO_UV) without uv_vis2 = 2")
         app = state.cfg["app"] + ("_MASK" if state.p.masking else "")      # <APP>_MASK: built with -DMASKING
         if state.p.wet_dry:
             app += "_WET"                                                  # <APP>_MASK_WET...: built with -DWET_DRY as well
@@ -38,6 +42,8 @@ class Ref:
             app += "_STAB"                                                 # built with -DTS_MIX_STABILITY as well
         if state.p.mix_iso_ts:
             app += "_ISO"                                                  # ... and MIX_ISO_TS as the tracer mixing choice
+        elif state.p.uv_vis2 == 2 and state.p.uv_vis4 == 2:
+            pass                                                           # ..._GEOUV4 below: MIX_GEO_UV with UV_VIS4
         elif state.p.ts_dif4 or state.p.uv_vis4:
             app += "_DIF4"                                                 # built with TS_DIF4 and UV_VIS4 added
         if state.p.eminusp:
@@ -48,6 +54,8 @@ class Ref:
             app += "_RAD2D"                                                # built with -DRADIATION_2D
         if state.p.uv_vis2 == 2:
             app += "_GEOUV"                                                # MIX_GEO_UV instead of MIX_S_UV (uv3dmix2_geo.h)
+            if state.p.uv_vis4 == 2:
+                app += "4"                                                 # ... plus UV_VIS4 and TS_DIF4 (uv3dmix4_geo.h)
         if state.p.gls_mixing == 2:
             app += "_MY25"                                                 # MY25_MIXING builds (ref_headers/*_my25.h)
         elif state.p.gls_mixing:

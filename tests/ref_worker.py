@@ -156,6 +156,87 @@ def iso_state(config, basin=None, mask=None, extra=None):
     return st0
 
 
+# the states of tests/test_gpu_uvgeo4.py: MIX_GEO_UV is one switch for both operators, uv_vis2 = 2 as well
+GEOUV4 = {"UPWELLING": {"uv_vis2": 2, "uv_vis4": 2, "visc4": 4.0e7},
+          "SEAMOUNT": {"uv_vis2": 2, "uv_vis4": 2, "visc2": 50.0, "visc4": 1.0e8}}
+GEOUV4_OUT = ["rufrc", "rvfrc", "u", "v"]
+
+
+def geouv4_state(config, basin=None, mask=None):
+    import util
+    from roms_trunk_mgh_amd import abi
+    ov = dict(GEOUV4[config])
+    if basin:
+        ov["EWperiodic"] = False
+    st0 = util.prepared_state(config, overrides=ov, mask=mask)
+    assert st0.b.NghostPoints == 3 and st0.p.uv_vis2 == 2 and st0.p.uv_vis4 == 2
+    if basin == "open":                          # gradient conditions on u, v on all sides
+        for sd in ("west", "east", "south", "north"):
+            for var in ("u", "v"):
+                st0.p.lbc[abi.LBS[sd]][abi.LBV[var]] = abi.LBC["Gra"]
+    return st0, util.step_idx(iic=5, iif=1, pred=0, knew=2, krhs=3)
+
+
+def main_geouv4(config, basin=None, mask=None):
+    """uv3dmix4_geo.h (UV_VIS4 with MIX_GEO_UV): the reference built with the _GEOUV options plus UV_VIS4 and TS_DIF4
+    (oracle/_ref/<APP>[_MASK[_WET]]_GEOUV4) vs the C oracle at uv_vis2 = uv_vis4 = 2 and vs the numpy restatement of
+    tests/uvgeo4_util.py, on the states of tests/test_gpu_uvgeo4.py.  "s_surface": how far the oracle's uv_vis4 = 1 lies
+    from its uv_vis4 = 2 on the same state (the rotation has to act)."""
+    import oracle
+    import util
+    import uvgeo4_util
+    from oracle import ref
+    st0, s = geouv4_state(config, basin, mask)
+    st_r, st_o, st_n, st_s = st0.copy(), st0.copy(), st0.copy(), st0.copy()
+    ref.Ref(st_r).call("uv3dmix4", s)
+    oracle.Oracle(st_o).call("uv3dmix4", s)
+    uvgeo4_util.uv3dmix4_geo(st_n, s)
+    st_s.p = type(st0.p).from_buffer_copy(st0.p)
+    st_s.p.uv_vis2 = st_s.p.uv_vis4 = 1
+    oracle.Oracle(st_s).call("uv3dmix4", s)
+    diffs = util.compare_states(st_o, st_r)
+    numpy_diffs = util.compare_states(st_n, st_r)
+    out = {"EWperiodic": int(st0.b.EWperiodic), "masking": int(st0.p.masking), "wet_dry": int(st0.p.wet_dry),
+           "open": int(basin == "open"),
+           "kernels": {"uv3dmix4": {
+               "max_rel_diff": max(diffs.values()) if diffs else 0.0, "fields_diff": sorted(diffs),
+               "numpy_max_rel_diff": max(numpy_diffs.values()) if numpy_diffs else 0.0,
+               "numpy_bits_equal": all(np.array_equal(st_n[n], st_o[n]) for n in GEOUV4_OUT),
+               "changed": sorted(util.compare_states(st_r, st0)),
+               "change": {n: util.max_rel_diff(st_r[n], st0[n]) for n in GEOUV4_OUT},
+               "s_surface": max(util.max_rel_diff(st_o[n], st_s[n]) for n in ("u", "v"))}}}
+    print(json.dumps(out))
+
+
+def main_flat4(config, which, path):
+    """Masked level geopotentials: uv3dmix4 of ONE reference build -- "s": <APP>_MASK_DIF4 (uv3dmix4_s.h), "geo":
+    <APP>_MASK_GEOUV4 (uv3dmix4_geo.h) -- on the island grid with a flat bottom, zeta = 0 and theta_s = theta_b = 0, so
+    that every level is a geopotential.  The state is the same but for the switch; u, v, rufrc, rvfrc are written to
+    `path` for tests/test_ref_pinning.py to compare the two builds."""
+    import oracle
+    import util
+    from oracle import ref
+    vis = {"s": 1, "geo": 2}[which]
+    st0 = util.prepared_state(config, overrides=dict(GEOUV4[config], uv_vis2=vis, uv_vis4=vis, theta_s=0.0, theta_b=0.0),
+                              mask="island")
+    st0["h"][:] = float(st0["h"].max())
+    st0["zeta"][:] = 0.0
+    st0["Zt_avg1"][:] = 0.0
+    oracle.Oracle(st0).call("set_depth", util.step_idx())
+    b = st0.b
+    T = (st0.I(b.IstrT, b.IendT), st0.J(b.JstrT, b.JendT))
+    flat = float(np.ptp(st0["z_r"][T], axis=(0, 1)).max()) == 0.0 and float(np.ptp(st0["Hz"][T], axis=(0, 1)).max()) == 0.0
+    s = util.step_idx(iic=5, iif=1, pred=0, knew=2, krhs=3)
+    st_r, st_o = st0.copy(), st0.copy()
+    ref.Ref(st_r).call("uv3dmix4", s)
+    oracle.Oracle(st_o).call("uv3dmix4", s)
+    diffs = util.compare_states(st_o, st_r)
+    np.savez(path, **{n: st_r[n] for n in GEOUV4_OUT}, pmask=st0["pmask"], u0=st0["u"])
+    print(json.dumps({"flat": bool(flat), "masking": int(st0.p.masking), "uv_vis4": int(st0.p.uv_vis4),
+                      "oracle_max_rel_diff": max(diffs.values()) if diffs else 0.0,
+                      "changed": sorted(util.compare_states(st_r, st0))}))
+
+
 def main_iso(config, basin=None, mask=None):
     """t3dmix2_iso and t3dmix4_iso (MIX_ISO_TS): reference Fortran (the application with MIX_ISO_TS, TS_DIF2 and
     TS_DIF4) vs C oracle."""
@@ -771,6 +852,11 @@ if __name__ == "__main__":
     elif len(sys.argv) > 2 and sys.argv[2] in ("iso", "iso_closed", "iso_open", "iso_mask", "iso_mask_open"):
         m = sys.argv[2].split("_")
         main_iso(sys.argv[1], basin=m[-1] if m[-1] in ("closed", "open") else None, mask="island" if "mask" in m else None)
+    elif len(sys.argv) > 2 and sys.argv[2] in ("geouv4", "geouv4_closed", "geouv4_open", "geouv4_mask", "geouv4_mask_open"):
+        m = sys.argv[2].split("_")
+        main_geouv4(sys.argv[1], basin=m[-1] if m[-1] in ("closed", "open") else None, mask="island" if "mask" in m else None)
+    elif len(sys.argv) > 3 and sys.argv[2] in ("flat4_s", "flat4_geo"):
+        main_flat4(sys.argv[1], sys.argv[2].split("_")[1], sys.argv[3])
     elif len(sys.argv) > 2 and sys.argv[2] in ("dif4", "dif4_closed", "dif4_open", "dif4_mask", "dif4_mask_open"):
         m = sys.argv[2].split("_")
         main_dif4(sys.argv[1], basin=m[-1] if m[-1] in ("closed", "open") else None, mask="island" if "mask" in m else None)

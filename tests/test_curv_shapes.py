@@ -56,6 +56,8 @@ READS = {
     'step2d:dif4': (('pm', 'pn', 'om_r', 'on_r', 'fomn', 'pnom_r', 'pmon_r', 'on_u', 'om_v', 'pnom_p', 'pmon_p', 'om_p', 'on_p', 'dndx', 'dmde', 'visc2_r', 'visc2_p', 'visc4_r', 'visc4_p'), {}),
     'uv3dmix2:geo': (('pm', 'pn', 'om_r', 'on_r', 'om_u', 'on_u', 'om_v', 'on_v', 'om_p', 'on_p', 'visc2_r', 'visc2_p'), {}),
     'rhs3d:geo': (('pm', 'pn', 'om_r', 'on_r', 'fomn', 'om_u', 'on_u', 'om_v', 'on_v', 'om_p', 'on_p', 'dndx', 'dmde', 'visc2_r', 'visc2_p', 'diff2'), {'UPWELLING': ('pmon_u', 'pnom_v')}),
+    'uv3dmix4:geo': (('pm', 'pn', 'om_r', 'on_r', 'om_u', 'on_u', 'om_v', 'on_v', 'om_p', 'on_p', 'visc4_r', 'visc4_p'), {}),
+    'rhs3d:geo4': (('pm', 'pn', 'om_r', 'on_r', 'fomn', 'om_u', 'on_u', 'om_v', 'on_v', 'om_p', 'on_p', 'dndx', 'dmde', 'visc2_r', 'visc2_p', 'visc4_r', 'visc4_p', 'diff2'), {'UPWELLING': ('pmon_u', 'pnom_v')}),
     't3dmix2:iso': (('pm', 'pn', 'on_u', 'om_v', 'diff2'), {}),
     't3dmix4:iso': (('pm', 'pn', 'on_u', 'om_v', 'diff4'), {}),
     'gls_prestep:k-epsilon': (('pm', 'pn'), {}),
@@ -197,6 +199,35 @@ def test_oracle_runs_on_the_curvilinear_states(name):
     m = tw.run_steps(oracle.Oracle(st), 10)
     assert np.isfinite(st["t"]).all() and np.isfinite(st["u"]).all()
     assert float(np.abs(st["u"]).max()) > 1e-6 and m.last_diag is not None
+
+
+def _geo4_run_states():
+    import test_gpu_levels as tl
+    return ([("wide", n) for n in tw.RUNS if "geo4" in n] + [("levels", n) for n in tl.RUNS if "geo4" in n] +
+            [("curv", n) for n in tc.RUNS if "geo4" in n])
+
+
+@pytest.mark.parametrize("where,name", _geo4_run_states())
+def test_the_rotation_acts_in_the_whole_step_runs(where, name):
+    """the 10-step runs with uv_vis2 = uv_vis4 = 2 (w3 island and open_island, UPWELLING N = 33, SEAMOUNT curvilinear
+    closed): the oracle's run with both operators along s-surfaces instead ends with another u, so a device that ran
+    the s-surface operator would miss the run bound"""
+    import oracle
+    import test_gpu_levels as tl
+    mod = {"wide": tw, "levels": tl, "curv": tc}[where]
+    st_g, st_s = mod.run_state(name), mod.run_state(name)
+    st_s.p.uv_vis2 = st_s.p.uv_vis4 = 1
+    mg = tw.run_steps(oracle.Oracle(st_g), 10)
+    tw.run_steps(oracle.Oracle(st_s), 10)
+    u_g, u_s = st_g.interior("u")[..., mg.s.nnew - 1], st_s.interior("u")[..., mg.s.nnew - 1]
+    assert np.isfinite(u_g).all() and np.isfinite(st_g["t"]).all()
+    d = float(np.sqrt(np.mean((u_g - u_s) ** 2)) / np.sqrt(np.mean(u_s ** 2)))
+    print(where, name, "relative RMS distance of the s-surface run", d)
+    assert d > 100.0 * 1e-10
+
+
+def test_geo4_run_states_are_listed():
+    assert len(_geo4_run_states()) == 4
 
 
 @pytest.mark.parametrize("s", ["predictor", "corrector"])

@@ -722,13 +722,14 @@ def test_hip_reproduces_reference_ts_mix_stability():
     _stab_check(run, 1e-13)
 
 
-def _geouv_check(case, backend, tol):
+def _geouv_check(case, backend, tol, biharmonic=False):
+    import importlib
     import sys
     gd = os.path.join(HERE, "golden")
     if gd not in sys.path:
         sys.path.insert(0, gd)
-    import make_golden_geouv as mg
-    g = np.load(os.path.join(gd, "ref_geouv.npz"))
+    mg = importlib.import_module("make_golden_geouv4" if biharmonic else "make_golden_geouv")
+    g = np.load(os.path.join(gd, "ref_geouv4.npz" if biharmonic else "ref_geouv.npz"))
     st, s = mg.prepare(case)
     st0 = st.copy()
     backend(st, s)
@@ -768,6 +769,55 @@ def test_hip_reproduces_reference_uv3dmix2_geo(case):
         finally:
             h.close()
     _geouv_check(case, run, 1e-13)
+
+
+GEOUV4_CASES = ["channel", "seamount", "closed", "seamount_closed", "open", "seamount_open", "island", "island_open",
+                "island_wet"]
+
+
+@pytest.mark.parametrize("case", GEOUV4_CASES)
+def test_oracle_reproduces_reference_uv3dmix4_geo(case):
+    """uv3dmix4_geo.h (UV_VIS4 with MIX_GEO_UV, uv_vis2 = uv_vis4 = 2) of the reference built with the options
+    (tests/golden/make_golden_geouv4.py: channel, seamount, closed and open basins, island grid, island grid with open
+    edges and with WET_DRY) vs the oracle: bit for bit, SHA-256 of the whole arrays included."""
+    import oracle
+    _geouv_check(case, lambda st, s: oracle.Oracle(st).call("uv3dmix4", s), 0.0, biharmonic=True)
+
+
+@pytest.mark.parametrize("case", GEOUV4_CASES)
+def test_numpy_restatement_reproduces_reference_uv3dmix4_geo(case):
+    """the same vectors vs tests/uvgeo4_util.py, the independent second statement: bit for bit"""
+    import uvgeo4_util
+    _geouv_check(case, lambda st, s: uvgeo4_util.uv3dmix4_geo(st, s), 0.0, biharmonic=True)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", GEOUV4_CASES)
+def test_hip_reproduces_reference_uv3dmix4_geo(case):
+    """k_uv4_geo_first / k_uv4_geo_second against the reference's vectors directly: the kernels evaluate the reference's
+    expressions in the reference's order, so the bits are the reference's (SHA-256 of the whole arrays)."""
+    from roms_trunk_mgh_amd import hip
+
+    def run(st, s):
+        h = hip.RomsHip(st)
+        try:
+            h.call("uv3dmix4", s)
+            h.to_host()
+        finally:
+            h.close()
+    _geouv_check(case, run, 0.0, biharmonic=True)
+
+
+def test_geouv4_fixture_lists_its_cases():
+    import sys
+    gd = os.path.join(HERE, "golden")
+    if gd not in sys.path:
+        sys.path.insert(0, gd)
+    import make_golden_geouv4 as mg
+    assert list(mg.CASES) == GEOUV4_CASES
+    g = np.load(os.path.join(gd, "ref_geouv4.npz"))
+    assert {k.split("/")[0] for k in g.files} == set(GEOUV4_CASES)
+    assert os.path.getsize(os.path.join(gd, "ref_geouv4.npz")) < 1 << 20
 
 
 # ------------------------------------------------------------------------------------- the curvilinear grid --

@@ -417,14 +417,22 @@ def test_curv_uvadv_step2d(case, pair, s):
 
 
 # ------------------------------------------------------------------------------------------- 3. whole steps --
-RUNS = {"BENCHMARK_TINY-island": ("BENCHMARK_TINY", "island"), "UPWELLING-open": ("UPWELLING", "open_island")}
+RUNS = {"BENCHMARK_TINY-island": ("BENCHMARK_TINY", "island"), "UPWELLING-open": ("UPWELLING", "open_island"),
+        # the seamount's sloping levels with both viscosities rotated to geopotentials (uv_vis2 = uv_vis4 = 2; the
+        # viscosities of tests/test_gpu_uvgeo4.py)
+        "SEAMOUNT-geo4-closed": ("SEAMOUNT", "closed")}
+SEAMOUNT_GEO4 = {"uv_vis2": 2, "uv_vis4": 2, "visc2": 50.0, "visc4": 1.0e8}
 
 
 def run_state(name):
     config, variant = RUNS[name]
-    st = tw.tile(shape(config), variant)
+    geo4 = "geo4" in name
+    st = tw.tile(shape(config), variant, ov=SEAMOUNT_GEO4 if geo4 else None)
     check_geometry(st.b)
     tw.check_seam(st, variant)
+    if geo4:
+        tw.check_geo4_run(st)
+        assert float(np.ptp(st.interior("h"))) > 100.0            # sloping levels: the rotation acts
     return cv.curvilinear(st)
 
 

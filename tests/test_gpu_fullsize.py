@@ -34,6 +34,7 @@ def _check_prognostic(st_h, st_o, m):
     for it in range(st_o.b.NT):
         out[f"t{it+1}"] = rel_rms(st_h.interior("t")[..., s.nnew - 1, it], st_o.interior("t")[..., s.nnew - 1, it], FLOOR["t"])
     assert np.isfinite(st_h["t"]).all()
+    print("relative RMS differences:", out)
     assert all(v <= TOL for v in out.values()), out
     assert float(np.abs(st_o["u"]).max()) > 1e-6
 

@@ -229,6 +229,7 @@ RUNS = {f"{cfg}-N{N}-{v}": (cfg, N, variant, {}) for cfg in ("BENCHMARK_TINY", "
         for v, variant in (("island", "island"), ("open", "open_island"))}
 RUNS["BENCHMARK_TINY-N33-mpdata6"] = ("BENCHMARK_TINY", 33, "island", dict(ov=tw.SCHEMES["MPDATA"], NT=6))
 RUNS["UPWELLING-N49-beach"] = ("UPWELLING", 49, "island", dict(ov=tw.BEACH))
+RUNS["UPWELLING-N33-geo4"] = ("UPWELLING", 33, "island", dict(ov=tw.GEO4_RUN))      # uv_vis2 = uv_vis4 = 2 in whole steps
 
 
 def run_state(name):
@@ -236,6 +237,8 @@ def run_state(name):
     st = tw.tile(shape(N, config), variant, **kw)
     check_geometry(st.b, N)
     tw.check_seam(st, variant)
+    if name.endswith("geo4"):
+        tw.check_geo4_run(st)
     return st
 
 

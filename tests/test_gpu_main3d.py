@@ -6,11 +6,12 @@ import os
 import numpy as np
 import pytest
 
-from roms_trunk_mgh_amd import ana, hip, main3d
+from roms_trunk_mgh_amd import abi, ana, hip, main3d
 from roms_trunk_mgh_amd.state import rel_rms
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
+GEO4 = {"uv_vis2": 2, "uv_vis4": 2, "visc2": 50.0, "visc4": 1.0e8}      # tests/test_gpu_uvgeo4.py
 # stated magnitudes for fields whose reference RMS is ~0 (SEAMOUNT is at rest
 # up to the pressure-gradient error)
 FLOOR = {"zeta": 1e-3, "ubar": 1e-4, "vbar": 1e-4, "u": 1e-4, "v": 1e-4, "t": 1e-3}
@@ -42,12 +43,19 @@ def _run(config, nsteps, perturb, physics=False, overrides=None):
                                                     # the reference's default pressure gradient (prsgrd31.h)
                                                     ("SEAMOUNT", 0.0, "STANDARD"), ("UPWELLING", 1.0, "WJ_GRADP"),
                                                     # the finite-volume pressure Jacobian (prsgrd40.h)
-                                                    ("SEAMOUNT", 0.0, "PJ_GRADP")])
+                                                    ("SEAMOUNT", 0.0, "PJ_GRADP"),
+                                                    # both viscosities rotated to geopotentials (uv3dmix2_geo.h,
+                                                    # uv3dmix4_geo.h) over the seamount's sloping levels
+                                                    ("SEAMOUNT", 0.0, "GEO4")])
 def test_100_steps(config, perturb, physics):
     ov = None
-    if isinstance(physics, str):
+    if physics == "GEO4":
+        ov, physics = GEO4, False
+    elif isinstance(physics, str):
         ov, physics = {"pgf": physics}, False
     st_h, st_o, mo = _run(config, 100, perturb, physics, overrides=ov)
+    if ov is GEO4:         # the rotated pair runs inside rhs3d with the momentum start fused into prsgrd32 (lambda = 1)
+        assert (st_h.p.uv_vis2, st_h.p.uv_vis4) == (2, 2) and st_h.p.pgf == abi.PGF["DJ_GRADPS"] and st_h.p.lambda_ == 1.0
     s = mo.s
     out = {}
     out["zeta"] = rel_rms(st_h.interior("zeta")[..., mo.indx1 - 1], st_o.interior("zeta")[..., mo.indx1 - 1], FLOOR["zeta"])
@@ -58,6 +66,7 @@ def test_100_steps(config, perturb, physics):
     for it in range(st_o.b.NT):
         out[f"t{it+1}"] = rel_rms(st_h.interior("t")[..., s.nnew - 1, it], st_o.interior("t")[..., s.nnew - 1, it], FLOOR["t"])
     assert np.isfinite(st_o["t"]).all() and np.isfinite(st_h["t"]).all()
+    print(config, perturb, physics, "relative RMS differences:", out)
     assert all(v <= TOL for v in out.values()), out
     # the run must have done something
     assert float(np.abs(st_o["u"]).max()) > 1e-6

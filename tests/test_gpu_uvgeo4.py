@@ -1,8 +1,11 @@
 """-m gpu: biharmonic viscosity rotated to geopotential surfaces (UV_VIS4 with MIX_GEO_UV, uv3dmix4_geo.h:262-1478;
-roms_params_t.uv_vis4 = 2).  k_uv4_geo_first / k_uv4_geo_second through the C ABI against the numpy restatement of
-tests/uvgeo4_util.py (pinned without a GPU in tests/test_uvgeo4.py): the CPU oracle has no uv3dmix4_geo -- with
-uv_vis4 = 2 it computes the s-surface operator -- so no whole step is compared with it here.  The kernels evaluate the
-reference's expressions in the reference's order: the comparisons are for identical bits."""
+roms_params_t.uv_vis4 = 2).  k_uv4_geo_first / k_uv4_geo_second through the C ABI against two yardsticks written
+separately, both pinned bit for bit to the reference built with the option (tests/test_ref_pinning.py,
+tests/test_golden.py): the numpy restatement of tests/uvgeo4_util.py and the CPU oracle's uv3dmix4_geo
+(oracle/oracle_uvmix_geo.c).  The kernels evaluate the reference's expressions in the reference's order: the comparisons
+with the restatement and with the oracle's uv3dmix4 are for identical bits; the oracle's whole rhs3d at the per-call bound of
+tests/test_gpu_wide.py.  Whole steps against the oracle: tests/test_gpu_wide.py, test_gpu_levels.py,
+test_gpu_curvilinear.py (10 steps) and tests/test_gpu_main3d.py (100 steps)."""
 import numpy as np
 import pytest
 
@@ -54,9 +57,17 @@ def _device(st, kernel, s):
     return st
 
 
+def _oracle(st0, kernel, s):
+    """the oracle's entry, uv_vis2 = uv_vis4 = 2"""
+    import oracle
+    st = ru.clone(st0)
+    oracle.Oracle(st).call(kernel, s)
+    return st
+
+
 def _expected(st0, kernel, s):
-    """uv3dmix4: the restatement.  rhs3d: the oracle's rhs3d without UV_VIS4 (it has uv3dmix2_geo for uv_vis2 = 2), then
-    the restatement -- the operator reads u, v(nrhs) only and adds to u, v(nnew), rufrc, rvfrc."""
+    """the cross-check.  uv3dmix4: the restatement.  rhs3d: the oracle's rhs3d without UV_VIS4 (uv3dmix2_geo for
+    uv_vis2 = 2), then the restatement -- the operator reads u, v(nrhs) only and adds to u, v(nnew), rufrc, rvfrc."""
     import oracle
     st = ru.clone(st0)
     if kernel == "rhs3d":
@@ -78,11 +89,20 @@ def _same(st_h, st_n, st0):
 def test_uv3dmix4_geo_kernel(config, variant, kernel):
     st0 = _state(config, variant)
     s = _idx()
+    st_o = _oracle(st0, kernel, s)
     st_n = _expected(st0, kernel, s)
+    for name in OUT:                               # the two yardsticks agree on what they both compute, bit for bit
+        assert np.array_equal(st_o[name], st_n[name]), (name, float(np.abs(st_o[name] - st_n[name]).max()))
     st_h = _device(ru.clone(st0), kernel, s)
     _same(st_h, st_n, st0)
+    _same(st_h, st_o, st0)
     if kernel == "uv3dmix4":                       # the other registered fields are left alone
         assert sorted(util.compare_states(st_h, st0)) == sorted(OUT)
+        assert util.compare_states(st_h, st_o) == {}
+    else:                                          # every registered field of the whole rhs3d against the oracle's
+        diffs = util.compare_states(st_h, st_o)
+        print(config, variant, "rhs3d max relative differences:", diffs)
+        assert all(v <= wide.TOL for v in diffs.values()), diffs
 
 
 @pytest.mark.parametrize("variant,wet,curv", [("island", False, False), ("island", True, False), ("closed", False, False),
@@ -99,6 +119,7 @@ def test_workgroup_seams(variant, wet, curv):
     st_n = G.uv3dmix4_geo(ru.clone(st0), s)
     st_h = _device(ru.clone(st0), "uv3dmix4", s)
     _same(st_h, st_n, st0)
+    _same(st_h, _oracle(st0, "uv3dmix4", s), st0)
 
 
 @pytest.mark.parametrize("ntI,ntJ", [(2, 1), (1, 2)])

@@ -223,10 +223,20 @@ def _dif4(label, shape, variant):
     return st, _calls(label.split(":")[0])
 
 
+VISC4_GEO = {"UPWELLING": 4.0e7, "BENCHMARK_TINY": 2.0e10}      # tests/test_gpu_uvgeo4.py
+
+
 def _geo(label, shape, variant):
-    st = prepared(shape, variant, {"uv_vis2": 2})
-    assert st.p.uv_vis2 == 2
-    return st, _calls(label.split(":")[0])
+    """MIX_GEO_UV: uv3dmix2_geo.h (":geo"), and uv3dmix4_geo.h as well ("uv3dmix4:geo", "rhs3d:geo4": uv_vis2 = uv_vis4 = 2,
+    one CPP switch for both operators)"""
+    kernel, opt = label.split(":")
+    ov = {"uv_vis2": 2}
+    if kernel == "uv3dmix4" or opt == "geo4":
+        ov.update(uv_vis4=2, visc4=VISC4_GEO[config_of(shape)])
+    st = prepared(shape, variant, ov)
+    assert st.p.uv_vis2 == 2 and st.p.uv_vis4 == ov.get("uv_vis4", 0)
+    assert st.b.NghostPoints == 3 or not st.p.uv_vis4
+    return st, _calls(kernel)
 
 
 def _iso(label, shape, variant):
@@ -372,7 +382,7 @@ FAMILIES = {
                      "ini_fields", "step2d_loop"]),
     "prsgrd": (_prsgrd, ["prsgrd:STANDARD", "prsgrd:WJ_GRADP", "prsgrd:PJ_GRADP"]),         # prsgrd31 x 2, prsgrd40
     "dif4": (_dif4, ["t3dmix4:dif4", "uv3dmix4:dif4", "step2d:dif4"]),
-    "geo": (_geo, ["uv3dmix2:geo", "rhs3d:geo"]),
+    "geo": (_geo, ["uv3dmix2:geo", "rhs3d:geo", "uv3dmix4:geo", "rhs3d:geo4"]),
     "iso": (_iso, ["t3dmix2:iso", "t3dmix4:iso"]),
     "gls": (_gls, ["gls_prestep:k-epsilon", "gls_corstep:k-epsilon", "gls_prestep:my25", "gls_corstep:my25"]),
     "adv3": (_adv3, [k + ":" + sc for sc in ("MPDATA", "HSIMT", "MIXED") for k in ("pre_step3d", "step3d_t")]),
@@ -533,13 +543,25 @@ def test_wide_clima(shape, variant):
 
 # ------------------------------------------------------------------------------------------- 2. whole steps --
 BEACH = {"wet_dry": 1, "beach": 1, "zeta_amp": 0.3}          # tests/test_gpu_wetdry.py
+GEO4_RUN = {"uv_vis2": 2, "uv_vis4": 2, "visc4": VISC4_GEO["UPWELLING"]}
 RUNS = {
     "w8-island": ("w8", "island", {}), "w8-open": ("w8", "open_island", {}),
     "w10-island": ("w10", "island", {}), "w10-open": ("w10", "open_island", {}),
     "w8-mpdata6": ("w8", "island", dict(ov=SCHEMES["MPDATA"], NT=6, config="BENCHMARK_TINY")),
     "w8-beach": ("w8", "island", dict(ov=BEACH, config="UPWELLING")),
     "w3-sources": ("w3", "closed", dict(config="UPWELLING")),
+    # both viscosities rotated to geopotentials (uv_vis2 = uv_vis4 = 2): uv3dmix4_geo's two passes inside whole steps
+    "w3-geo4-island": ("w3", "island", dict(ov=GEO4_RUN, config="UPWELLING")),
+    "w3-geo4-open": ("w3", "open_island", dict(ov=GEO4_RUN, config="UPWELLING")),
 }
+
+
+def check_geo4_run(st):
+    """a whole-step state of the rotated pair: both switches at 2 and, with prsgrd32 and lambda = 1, the momentum start
+    fused into the pressure-gradient kernel (csrc/k_rhs3d.hip: rhs3d_fuses_uvstart) while uv3dmix4_geo runs"""
+    assert (st.p.uv_vis2, st.p.uv_vis4) == (2, 2) and st.b.NghostPoints == 3
+    assert st.p.pgf == abi.PGF["DJ_GRADPS"] and st.p.lambda_ == 1.0
+    assert float(np.abs(st["visc4_r"]).max()) > 0.0 and float(np.abs(st["visc2_r"]).max()) > 0.0
 
 
 def run_state(name):
@@ -549,6 +571,8 @@ def run_state(name):
     check_seam(st, variant)
     if name == "w3-sources":
         check_sources(util.river_sources(st, "walls", at=seam_sources(shape)), st.b)
+    if "geo4" in name:
+        check_geo4_run(st)
     return st
 
 

@@ -1,6 +1,8 @@
 """The numpy restatement of the viscosity rotated to geopotentials (tests/uvgeo4_util.py) pinned without a GPU: it is
-the yardstick of tests/test_gpu_uvgeo4.py for uv3dmix4_geo.h (UV_VIS4 + MIX_GEO_UV, roms_params_t.uv_vis4 = 2), which
-neither the CPU oracle nor any reference build has."""
+one of the two yardsticks of tests/test_gpu_uvgeo4.py for uv3dmix4_geo.h (UV_VIS4 + MIX_GEO_UV, roms_params_t.uv_vis4 =
+2).  The other is the C oracle's uv3dmix4_geo (oracle/oracle_uvmix_geo.c), written separately; both are pinned bit for
+bit to the reference built with the option (oracle/_ref/*_GEOUV4: tests/test_ref_pinning.py, and the fixture
+tests/golden/ref_geouv4.npz in tests/test_golden.py), and to each other here."""
 import numpy as np
 import pytest
 
@@ -36,6 +38,59 @@ def test_harmonic_form_is_the_oracles(config, variant):
     for name in OUT:
         assert np.array_equal(st_n[name], st_o[name]), (name, float(np.abs(st_n[name] - st_o[name]).max()))
     assert not np.array_equal(st_o["u"], st0["u"]) and not np.array_equal(st_o["rvfrc"], st0["rvfrc"])
+
+
+@pytest.mark.parametrize("config", ["UPWELLING", "SEAMOUNT", "BENCHMARK_TINY"])
+@pytest.mark.parametrize("variant", ["periodic", "closed", "open", "mask", "mask_closed", "mask_open", "wet"])
+def test_biharmonic_form_is_the_oracles(config, variant):
+    """the two statements of uv3dmix4_geo.h -- numpy here, C in the oracle at uv_vis2 = uv_vis4 = 2 -- give identical bits
+    on the states of tests/test_gpu_uvgeo4.py, BENCHMARK_TINY (which no reference build covers) and gradient conditions
+    on a masked basin included; u, v, rufrc, rvfrc change and the oracle changes nothing else"""
+    import oracle
+    from roms_trunk_mgh_amd import abi
+    ov = {"uv_vis2": 2, **VISC2.get(config, {}), **VIS4[config]}
+    if variant.endswith(("closed", "open")):
+        ov["EWperiodic"] = False
+    st0 = util.prepared_state(config, overrides=ov, mask="island" if variant.startswith("mask") else None,
+                              wet=(variant == "wet") or None)
+    if variant.endswith("open"):
+        for sd in ("west", "east", "south", "north"):
+            for var in ("u", "v"):
+                st0.p.lbc[abi.LBS[sd]][abi.LBV[var]] = abi.LBC["Gra"]
+    st_o, st_n = st0.copy(), st0.copy()
+    s = _idx()
+    oracle.Oracle(st_o).call("uv3dmix4", s)
+    G.uv3dmix4_geo(st_n, s)
+    for name in OUT:
+        assert np.array_equal(st_n[name], st_o[name]), (name, float(np.abs(st_n[name] - st_o[name]).max()))
+    assert sorted(util.compare_states(st_o, st0)) == sorted(OUT)
+
+
+@pytest.mark.parametrize("pair", [(1, 2), (2, 1)])
+@pytest.mark.parametrize("kernel", ["uv3dmix2", "uv3dmix4", "rhs3d"])
+def test_oracle_refuses_a_mixed_pair(pair, kernel):
+    """MIX_GEO_UV is one switch for both operators: the oracle refuses (uv_vis2, uv_vis4) = (1, 2) and (2, 1) by name, as
+    the device does, changes nothing, and never runs the s-surface operator in the rotated one's place"""
+    import oracle
+    st = util.prepared_state("UPWELLING", overrides=dict(VIS4["UPWELLING"], uv_vis2=2))
+    st.p.uv_vis2, st.p.uv_vis4 = pair
+    st0 = st.copy()
+    with pytest.raises(RuntimeError) as e:
+        oracle.Oracle(st).call(kernel, _idx())
+    assert "MIX_GEO_UV" in str(e.value)
+    assert util.compare_states(st, st0) == {}
+
+
+def test_oracle_rotates_on_sloping_levels():
+    """the oracle at uv_vis4 = 2 differs from uv_vis4 = 1 on SEAMOUNT: the s-surface operator is not what runs"""
+    import oracle
+    out = []
+    for vis in (1, 2):
+        st = util.prepared_state("SEAMOUNT", overrides=dict(VIS4["SEAMOUNT"], uv_vis2=0, uv_vis4=vis))
+        s = _idx()
+        oracle.Oracle(st).call("uv3dmix4", s)
+        out.append(st["u"][:, :, :, s.nnew - 1].copy())
+    assert util.max_rel_diff(out[1], out[0]) > 1e-9
 
 
 def test_uniform_velocities_are_left_alone():

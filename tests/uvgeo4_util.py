@@ -1,15 +1,16 @@
 """The horizontal viscosity rotated to geopotential surfaces (MIX_GEO_UV) restated in numpy, statement for statement
 and in the reference's order: uv3dmix2_geo_tile (ROMS/Nonlinear/uv3dmix2_geo.h:116-756) and uv3dmix4_geo_tile
 (uv3dmix4_geo.h:262-1478; default branch: no VISC_3DCOEF, UV_U3ADV_SPLIT, DIAGNOSTICS_UV; MASKING and WET_DRY by the
-parameters).  The yardstick of tests/test_uvgeo4.py (no GPU) and tests/test_gpu_uvgeo4.py: the CPU oracle has no
-uv3dmix4_geo and no reference build has the option.
+parameters).  A yardstick of tests/test_uvgeo4.py (no GPU) and tests/test_gpu_uvgeo4.py, kept as a second statement
+independent of the C oracle's (oracle/oracle_uvmix_geo.c): both are pinned bit for bit to the reference built with
+MIX_GEO_UV and UV_VIS4 (oracle/_ref/*_GEOUV4, tests/test_ref_pinning.py; tests/golden/ref_geouv4.npz).
 
 One level body -- the slopes, the six gradients, the four horizontal and the four vertical fluxes, on the ranges it is
 given -- serves the harmonic operator and both passes of the biharmonic one.  Its parameters are the velocity arrays,
 the coefficient pair, whether Hz is inside the horizontal fluxes, and what is done with the fluxes of a level (`finish`).
 Every statement is an elementwise operation on the index ranges the reference loops over, so the bits are those of the
-scalar loops; the harmonic form is pinned to the oracle's uv3dmix2_geo (itself pinned to four reference builds) in
-tests/test_uvgeo4.py."""
+scalar loops; the harmonic form is pinned to the oracle's uv3dmix2_geo (itself pinned to four reference builds) and the
+biharmonic one to the oracle's uv3dmix4_geo in tests/test_uvgeo4.py."""
 import numpy as np
 
 from roms_trunk_mgh_amd import abi
