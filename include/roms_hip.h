@@ -157,9 +157,9 @@ int roms_hip_get_unique_id(void *out128);
 /* BOUNDS(ng)%...(tile): get_bounds.F:738 (get_tile), :1009 (var_bounds).
  * May be called again in a live context (a re-grid; the tiling of roms_hip_init stays).  It forgets everything that
  * has the old extents: every field registration and device mirror, the library-kept defaults, the source table, the
- * climatology, the averages, the floats, the row table of the grid metrics, the halo neighbour table and message
+ * climatology, the averages, the floats, the tidal strips, the records of roms_hip_set_data_record, the row table of the grid metrics, the halo neighbour table and message
  * plan, and the captured LOOP_2D graphs.  The caller then sets the parameters, registers and uploads every field
- * and hands sources / climatology / averages / floats over again, as after roms_hip_init; the context then computes
+ * and hands sources / climatology / averages / floats / tides / data records over again, as after roms_hip_init; the context then computes
  * what a fresh one does, bit for bit. */
 int roms_hip_set_bounds(const roms_bounds_t *b);
 int roms_hip_set_params(const roms_params_t *p);
@@ -300,6 +300,9 @@ int roms_hip_set_sources(int Nsrc, const int *Isrc, const int *Jsrc, const doubl
 int roms_hip_set_clima(int LnudgeM2CLM, const double *M2nudgcof, const double *ubarclm, const double *vbarclm,
                        int LnudgeM3CLM, const double *M3nudgcof, const double *uclm, const double *vclm,
                        const int *LnudgeTCLM, const double *Tnudgcof, const double *tclm, double obcfac);
+/* One of the eight device copies ("M2nudgcof", "ubarclm", ..., "tclm") back to host memory, ordered after the kernels
+ * issued; n_doubles is checked.  For a host that writes out the climatology roms_hip_set_data interpolates, and for tests. */
+int roms_hip_get_clima(const char *name, double *host, long n_doubles);
 /* Time-averaged fields (AVERAGES): set_avg(ng,tile), ROMS/Nonlinear/set_avg.F:28, called after set_zeta
  * (main3d.F:493-495).  The averages are device arrays of the library, one per selected line of roms_avg.def, with the
  * tile's extents (LBi:UBi, LBj:UBj [, N | 0:N]) and zero wherever the reference's loops do not reach.
@@ -453,7 +456,66 @@ int roms_hip_set_tides(int NTC, int MTC, const double *Tperiod, const double *SS
                        int add_fsobc, const double *zeta_base, int add_m2obc, const double *ubar_base,
                        const double *vbar_base);
 int roms_hip_tides(double time);
-/* wvelocity(ng,tile,nstp)          ROMS/Nonlinear/wvelocity.F:27     (main3d.F:475; writes wvel) */
+/* Forcing, boundary and climatology snapshots: set_data(ng,tile), ROMS/Nonlinear/set_data.F:20-1390, called at
+ * main3d.F:222 before ini_fields, the surface physics and set_tides.  The calls of set_2dfld_tile (ROMS/Utility/set_2dfld.F:21),
+ * set_3dfld_tile (set_3dfld.F:21) and set_ngfld (set_ngfld.F:21) for the targets of include/roms_data.def: the host hands
+ * each time record over once, when get_data has read it, and every step one launch interpolates all of them.
+ *
+ * roms_hip_set_data_record: one record of target (enum roms_data_id).  index = itrc (1-based) of stflux / btflux /
+ * t_bry, the compact index ic (1-based, step3d_t.F:1551-1560) of tclm, not looked at otherwise; side = enum
+ * roms_lbc_side of an open-boundary target, not looked at otherwise.  slot in {1, 2} = the reference's Tindex =
+ * Iinfo(8,ifield,ng) after the read: the slot of the latest call is it2, the other one it1 = 3 - Tindex
+ * (set_2dfld.F:91-92).  Tintrp = Tintrp(slot,ifield,ng) in seconds, onerec = Linfo(3,ifield,ng).  rec has the extents the
+ * table gives for the target's shape (gridded: the host's Finp(:,:,slot) with the tile's LBi:UBi, LBj:UBj [, N]; an edge:
+ * the slice LBj:UBj or LBi:UBi [, N] of zeta_west(:), u_south(:,N), t_north(:,N) ..., Fortran order); n_doubles is checked.
+ * The record is copied to a device array of the library on the library's stream, behind the kernels that read the slot's
+ * old contents; the host buffer is free on return; nothing but that stream is waited for.  An edge record is kept as an
+ * edge-major strip, never as a tile-sized array.  A record for a side that is not a physical (non-periodic) edge of this
+ * tile returns 0 and keeps nothing.  A climatology target whose device copy does not exist (its switch is off) is
+ * refused: hand the arrays over with roms_hip_set_clima first.
+ * roms_hip_set_data_point: the same for point data, Linfo(1,ifield,ng) = .FALSE.: value = Fpoint(slot,ifield,ng); the
+ * targets of set_2dfld only.  The result is the uniform field of set_2dfld.F:127-133.
+ *
+ * roms_hip_set_data(time, dt, &synchro): time = time(ng), dt = dt(ng).  For every target with records the host evaluates
+ * set_2dfld.F:90-94, :116-120 in double (roms_hip_set_data_factors); *synchro is set to 1 where time + dt >
+ * Tintrp(it2) for any target (:139-141) and to 0 otherwise.  All or nothing: every target is checked before anything is
+ * launched, and if one fails the call returns non-zero, the message holds the target's name, "exceeds ending value" and
+ * the two record times (set_2dfld.F:156-162), and no target is written.  Then ONE launch writes
+ * Fout = fac1*Finp(it1) + fac2*Finp(it2) (onerec: Finp(Tindex)) for all targets: gridded ones on IstrR:IendR,
+ * JstrR:JendR, followed by the periodic images and the tile exchange of set_2dfld.F:170-201 / set_3dfld.F:183-219 in one
+ * packed exchange; edge ones on the row or column of the *_bry field where roms_fields.def puts the edge value, over the
+ * points of the allocated extent inside the reference's range (0 or 1 : Lm+1 / Mm+1).  With add_fsobc / add_m2obc tides
+ * the results for zeta_bry / ubar_bry, vbar_bry go into the tides' zeta_base / ubar_base, vbar_base copies, so that
+ * roms_hip_set_data followed by roms_hip_tides gives base + tide, as the reference's order does.  With wet_dry the
+ * interpolated zeta_bry is clipped to Dcrit - h on IstrR:IendR / JstrR:JendR of the edge in the same pass (:928-1003).
+ * A target with no records is not touched: roms_hip_sync_to_device and roms_hip_set_clima keep working for it, and a
+ * library in which no record was ever set behaves as before (the call returns 0 and launches nothing).
+ * Refused, leaving the library as it was: a call before bounds / params; an unknown target, index or side; a wrong length;
+ * slot outside 1..2; at roms_hip_set_data a target with a slot never filled (unless onerec).  roms_hip_set_bounds drops
+ * all records.  Timer name: "set_data".
+ *
+ * roms_hip_set_data_factors (host only, no GPU): the statement of set_2dfld.F:90-120 for Tintrp(1) = T1, Tintrp(2) = T2:
+ * fac1 (of it1 = 3 - Tindex), fac2 (of it2 = Tindex) and *synchro (set to 1 where :139 holds, left alone otherwise);
+ * onerec gives fac1 = 0, fac2 = 1.  Non-zero where the reference takes its error branch (:145).
+ *
+ * Not built, see roms_data.def: the CURVGRID rotation of point or coarse winds and stresses, DIURNAL_SRFLUX, the source
+ * table (roms_hip_set_sources), wave data, the 4D-Var blocks, CLIMA%ssh.  A host with one of those keeps interpolating
+ * that field itself and uploads it (roms_hip_sync_to_device). */
+enum roms_data_shape { DS_2D = 0, DS_N, DS_2DT, DS_NC, DS_E, DS_EN, DS_ENT };
+enum roms_data_dest { DD_FIELD = 0, DD_CLIMA, DD_BRY };
+enum roms_data_id {
+#define ROMS_DATA(name, routine, grid, shape, dest) DATA_##name,
+#include "roms_data.def"
+#undef ROMS_DATA
+  DATA_COUNT
+};
+int roms_hip_set_data_record(int target, int index, int side, int slot, double Tintrp, int onerec,
+                             const double *rec, long n_doubles);
+int roms_hip_set_data_point(int target, int index, int slot, double Tintrp, int onerec, double value);
+int roms_hip_set_data(double time, double dt, int *synchro);
+int roms_hip_set_data_factors(double time, double dt, double T1, double T2, int Tindex, int onerec,
+                              double *fac1, double *fac2, int *synchro);
+/* wvelocity(ng,tile,nstp)         ROMS/Nonlinear/wvelocity.F:27     (main3d.F:475; writes wvel) */
 int roms_hip_wvelocity(const roms_step_idx_t *s);
 /* diag(ng,tile)                    ROMS/Nonlinear/diag.F:31          (main3d.F:314), the tile-local part
  * diag.F:190-290 on time level nstp: out12 = { my_volume, my_avgke, my_avgpe, my_maxspeed, my_maxrho,

@@ -296,6 +296,7 @@ extern "C" int roms_hip_finalize(void)
   avg_release();
   floats_release();
   tides_release();
+  data_release();
   dia_release();
   if (g_ctx.devc) (void)hipFree(g_ctx.devc);
   g_ctx.devc = nullptr;
@@ -486,6 +487,27 @@ extern "C" int roms_hip_set_clima(int LnudgeM2CLM, const double *M2nudgcof, cons
   return 0;
 }
 
+// One of the eight device copies back to the host (tests; a host that writes the interpolated climatology out).
+extern "C" int roms_hip_get_clima(const char *name, double *host, long n_doubles)
+{
+  const char *me = "roms_hip_get_clima";
+  if (!g_ctx.inited) return roms_fail(me, "library not initialised");
+  if (!name || !host) return roms_fail(me, "climatology: null argument");
+  for (int q = 0; q < CL_COUNT; q++) {
+    if (strcmp(name, k_clima_name[q])) continue;
+    if (!g_clima.dev[q]) return roms_fail(me, (std::string("climatology: the library has no copy of ") + name + " (roms_hip_set_clima)").c_str());
+    if (n_doubles != g_clima.count[q]) {
+      char msg[200];
+      snprintf(msg, sizeof msg, "climatology: %s has %ld doubles, the host array %ld", name, g_clima.count[q], n_doubles);
+      return roms_fail(me, msg);
+    }
+    HIP_TRY(hipMemcpyAsync(host, g_clima.dev[q], sizeof(double) * n_doubles, hipMemcpyDeviceToHost, g_ctx.stream));
+    HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+    return 0;
+  }
+  return roms_fail(me, (std::string("climatology: unknown array ") + name).c_str());
+}
+
 // ---- time-averaged fields (AVERAGES; set_avg.F, mod_average.F) ----
 namespace {
 void avg_release()
@@ -636,6 +658,7 @@ extern "C" int roms_hip_set_bounds(const roms_bounds_t *b)
   avg_release();                           // ... and so have the averages
   floats_release();                        // ... and the floats' coordinate arrays
   tides_release();                         // ... and the tidal strips
+  data_release();                          // ... and the records of set_data
   dia_release();                           // ... and the tracer diagnostics
   halo_bounds_changed();                   // ... and the message plan has the old extents and ghost points
   g_ctx.b = *b;

@@ -427,6 +427,7 @@ int halo_batch_end();                     // ... and run them as one message per
 int halo_allreduce_sum(double *A, long n); // mp_collect: SUM over all tiles of a device array, in place (halo.hip)
 void floats_release();                    // k_floats.hip: frees what roms_hip_set_floats allocated
 void tides_release();                     // k_set_tides.hip: frees what roms_hip_set_tides allocated
+void data_release();                      // k_set_data.hip: drops every record of roms_hip_set_data_record / _point
 int guarded_alloc(double **user, double **base, long n);   // capi.hip: n zeroed doubles between two guard bands
 void guarded_free(double **user, double **base);
 void dia_release();                       // k_set_diags.hip: frees what roms_hip_set_diagnostics allocated

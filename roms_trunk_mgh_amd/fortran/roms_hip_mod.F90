@@ -149,6 +149,13 @@ MODULE roms_hip_mod
  &    AVG_avgv3RS=65, AVG_avgSxx3d=66, AVG_avgSxy3d=67, AVG_avgSyy3d=68, AVG_avgSzx3d=69, AVG_avgSzy3d=70,   &
  &    AVG_avgbedldu=71, AVG_avgbedldv=72, AVG_pmask_avg=73, AVG_rmask_avg=74, AVG_umask_avg=75,   &
  &    AVG_vmask_avg=76, AVG_COUNT=77, ROMS_AVG_NTKINDS=6
+  !  ids of the targets of set_data = the lines of include/roms_data.def (enum roms_data_id); a side is 0 = west, 1 = east,
+  !  2 = south, 3 = north (enum roms_lbc_side)
+  INTEGER(c_int), PARAMETER, PUBLIC :: DATA_sustr=0, DATA_svstr=1, DATA_srflx=2, DATA_stflux=3,   &
+ &    DATA_btflux=4, DATA_Uwind=5, DATA_Vwind=6, DATA_Tair=7, DATA_Pair=8, DATA_Hair=9,   &
+ &    DATA_rain=10, DATA_cloud=11, DATA_lrflx=12, DATA_ubarclm=13, DATA_vbarclm=14, DATA_uclm=15,   &
+ &    DATA_vclm=16, DATA_tclm=17, DATA_zeta_bry=18, DATA_ubar_bry=19, DATA_vbar_bry=20,   &
+ &    DATA_u_bry=21, DATA_v_bry=22, DATA_t_bry=23, DATA_COUNT=24
 
   INTERFACE
     INTEGER(c_int) FUNCTION roms_hip_init (rank, ntileI, ntileJ, device_id, uid)            &
@@ -427,6 +434,37 @@ MODULE roms_hip_mod
       IMPORT :: c_int, c_double
       REAL(c_double), VALUE :: time
     END FUNCTION
+    !  set_data (main3d.F:222): one roms_hip_set_data_record after each record get_data reads (C_LOC of Finp(:,:,Tindex) or
+    !  of the tile's slice of an edge vector; slot = Iinfo(8,ifield,ng), Tintrp = Tintrp(slot,ifield,ng) in seconds, onerec =
+    !  MERGE(1, 0, Linfo(3,ifield,ng))), roms_hip_set_data_point for point data, and one roms_hip_set_data (time(ng), dt(ng))
+    !  in place of the body of set_data_tile; synchro /= 0 sets synchro_flag(ng).
+    INTEGER(c_int) FUNCTION roms_hip_set_data_record (target, index, side, slot, Tintrp, onerec, rec, n_doubles)       &
+   &                        BIND(C, name='roms_hip_set_data_record')
+      IMPORT :: c_int, c_long, c_double, c_ptr
+      INTEGER(c_int), VALUE :: target, index, side, slot, onerec
+      REAL(c_double), VALUE :: Tintrp
+      TYPE(c_ptr), VALUE :: rec
+      INTEGER(c_long), VALUE :: n_doubles
+    END FUNCTION
+    INTEGER(c_int) FUNCTION roms_hip_set_data_point (target, index, slot, Tintrp, onerec, value)                        &
+   &                        BIND(C, name='roms_hip_set_data_point')
+      IMPORT :: c_int, c_double
+      INTEGER(c_int), VALUE :: target, index, slot, onerec
+      REAL(c_double), VALUE :: Tintrp, value
+    END FUNCTION
+    INTEGER(c_int) FUNCTION roms_hip_set_data (time, dt, synchro) BIND(C, name='roms_hip_set_data')
+      IMPORT :: c_int, c_double
+      REAL(c_double), VALUE :: time, dt
+      INTEGER(c_int), INTENT(out) :: synchro
+    END FUNCTION
+    INTEGER(c_int) FUNCTION roms_hip_set_data_factors (time, dt, T1, T2, Tindex, onerec, fac1, fac2, synchro)          &
+   &                        BIND(C, name='roms_hip_set_data_factors')
+      IMPORT :: c_int, c_double
+      REAL(c_double), VALUE :: time, dt, T1, T2
+      INTEGER(c_int), VALUE :: Tindex, onerec
+      REAL(c_double), INTENT(out) :: fac1, fac2
+      INTEGER(c_int), INTENT(inout) :: synchro
+    END FUNCTION
     !  GLS_MIXING: gls_prestep (main3d.F:567) and gls_corstep (main3d.F:793)
     INTEGER(c_int) FUNCTION roms_hip_gls_prestep (s) BIND(C, name='roms_hip_gls_prestep')
       IMPORT :: c_int, roms_step_idx_t
@@ -459,6 +497,7 @@ MODULE roms_hip_mod
   PUBLIC :: roms_hip_set_diagnostics, roms_hip_set_diags, roms_hip_get_diagnostic, roms_hip_dia_index
   PUBLIC :: roms_hip_set_floats, roms_hip_floats_put, roms_hip_floats_get, roms_hip_step_floats
   PUBLIC :: roms_hip_set_tides, roms_hip_tides
+  PUBLIC :: roms_hip_set_data_record, roms_hip_set_data_point, roms_hip_set_data, roms_hip_set_data_factors
   PUBLIC :: roms_hip_entry, roms_hip_make_idx, roms_hip_status
 
 CONTAINS

@@ -45,7 +45,8 @@ DECLARED_SYMBOLS = (
      "roms_hip_set_clima", "roms_hip_set_averages", "roms_hip_get_average", "roms_hip_average_device_ptr",
      "roms_hip_avg_phase", "roms_hip_set_floats", "roms_hip_floats_put", "roms_hip_floats_get",
      "roms_hip_step_floats", "roms_hip_set_tides", "roms_hip_tides", "roms_hip_set_diagnostics",
-     "roms_hip_get_diagnostic", "roms_hip_dia_index"] + ["roms_hip_" + e for e in ENTRIES])
+     "roms_hip_get_diagnostic", "roms_hip_dia_index", "roms_hip_set_data_record", "roms_hip_set_data_point",
+     "roms_hip_set_data", "roms_hip_set_data_factors", "roms_hip_get_clima"] + ["roms_hip_" + e for e in ENTRIES])
 
 
 _DP = C.POINTER(C.c_double)
@@ -104,11 +105,24 @@ def load():
     lib.roms_hip_set_diagnostics.argtypes = [C.c_int] * 4
     lib.roms_hip_get_diagnostic.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long]
     lib.roms_hip_dia_index.argtypes = [C.c_int] * 3
+    lib.roms_hip_set_data_record.argtypes = [C.c_int] * 4 + [C.c_double, C.c_int, C.c_void_p, C.c_long]
+    lib.roms_hip_set_data_point.argtypes = [C.c_int] * 3 + [C.c_double, C.c_int, C.c_double]
+    lib.roms_hip_set_data.argtypes = [C.c_double, C.c_double, _ip]
+    lib.roms_hip_set_data_factors.argtypes = [C.c_double] * 4 + [C.c_int, C.c_int, _DP, _DP, _ip]
     lib.roms_hip_set_halo_relay.argtypes = [RELAY_FN, C.c_void_p]
     if hasattr(lib, "roms_hip_tile_neighbors"):
         lib.roms_hip_tile_neighbors.argtypes = [C.c_int] * 7 + [C.POINTER(C.c_int)]
     _LIB = lib
     return lib
+
+
+def set_data_factors(time, dt, T1, T2, Tindex, onerec=False):
+    """Host-only helper of the library (roms_hip_set_data_factors; needs no GPU): the weights of set_2dfld.F:90-120 for
+    Tintrp(1:2) = T1, T2 as (fac1, fac2, synchro), or None where the reference takes its error branch."""
+    f1, f2, syn = C.c_double(0.0), C.c_double(0.0), C.c_int(0)
+    rc = load().roms_hip_set_data_factors(float(time), float(dt), float(T1), float(T2), int(Tindex), int(bool(onerec)),
+                                          C.byref(f1), C.byref(f2), C.byref(syn))
+    return None if rc else (f1.value, f2.value, syn.value)
 
 
 def tile_neighbors(rank, ntileI, ntileJ, Nghost, NghostPoints, EWperiodic, NSperiodic):
@@ -187,6 +201,13 @@ class RomsHip:
         only = names of the arrays to hand over again (the others keep their device copy)."""
         self._chk(self.l.roms_hip_set_clima(*clima.c_args(only)), "set_clima")
 
+    def get_clima(self, clima, name):
+        """The library's device copy of one array of `clima` as a host array of its extents (roms_hip_get_clima)."""
+        out = np.zeros(clima.arr[name].shape, dtype=np.float64, order="F")
+        self.l.roms_hip_get_clima.argtypes = [C.c_char_p, C.c_void_p, C.c_long]
+        self._chk(self.l.roms_hip_get_clima(name.encode(), out.ctypes.data, out.size), "get_clima " + name)
+        return out
+
     def set_averages(self, averages):
         """The selection of time-averaged fields (roms_trunk_mgh_amd/avg.py) -> roms_hip_set_averages; None switches
         the averages off (nAVG = 0)."""
@@ -262,6 +283,32 @@ class RomsHip:
     def tides(self, time):
         """set_tides (main3d.F:396) at time = time(ng): writes zeta_bry, ubar_bry, vbar_bry on the device, roms_hip_tides"""
         self._chk(self.l.roms_hip_tides(float(time)), "tides")
+
+    def set_data_record(self, name, slot, Tintrp, record, index=0, side=None, onerec=False):
+        """One time record of a target of roms_data.def (roms_trunk_mgh_amd/data.py) -> roms_hip_set_data_record; side =
+        a name of data.SIDES or its code."""
+        from . import data as _data
+        a = np.asfortranarray(record, dtype=np.float64)
+        sd = 0 if side is None else _data.SIDES.index(side) if isinstance(side, str) else int(side)
+        self._chk(self.l.roms_hip_set_data_record(_data.DATA_ID.get(name, -1) if isinstance(name, str) else int(name), int(index),
+                                                  sd, int(slot), float(Tintrp), int(bool(onerec)), a.ctypes.data, a.size),
+                  f"set_data_record {name}")
+
+    def set_data_point(self, name, slot, Tintrp, value, index=0, onerec=False):
+        """Point data Fpoint(slot) of a set_2dfld target -> roms_hip_set_data_point"""
+        from . import data as _data
+        self._chk(self.l.roms_hip_set_data_point(_data.DATA_ID.get(name, -1) if isinstance(name, str) else int(name), int(index),
+                                                 int(slot), float(Tintrp), int(bool(onerec)), float(value)),
+                  f"set_data_point {name}")
+
+    def set_data(self, time, dt):
+        """set_data (main3d.F:222) at time = time(ng): interpolates every target with records on the device; returns the
+        synchro flag (set_2dfld.F:139-141), roms_hip_set_data"""
+        syn = C.c_int(0)
+        self._chk(self.l.roms_hip_set_data(float(time), float(dt), C.byref(syn)), "set_data")
+        return syn.value
+
+    set_data_factors = staticmethod(set_data_factors)
 
     def _chk(self, rc, what):
         if rc != 0:

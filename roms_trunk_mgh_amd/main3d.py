@@ -8,6 +8,7 @@ because the full Fortran executable cannot be linked in this environment
 against either backend (`hip.RomsHip` = the product, or the CPU oracle in tests):
 
     main3d.F:189-191  nstp/nnew/nrhs rotation
+    main3d.F:222      set_data                         (data=...: the records of roms_data.def, interpolated on the device)
     main3d.F:269-283  first step only: ini_zeta, set_depth, ini_fields
     main3d.F:307-314  set_massflux, rho_eos, diag      (diag: diagnostics=True, every ninfo steps)
     main3d.F:280      set_data -> ana_srflux           (physics=True, BENCHMARK: shortwave flux of the hour)
@@ -47,7 +48,7 @@ def host_clock(tdays):
 
 class Main3D:
     def __init__(self, backend, ntstart=1, physics=False, diagnostics=False, ninfo=1, averages=None, floats=None, tides=None,
-                 diags=None):
+                 diags=None, data=None):
         """physics=True also runs the per-step physics that is on the device:
         bulk_flux and lmd_vmix (BULK_FLUXES / LMD_MIXING applications, i.e. BENCHMARK) and set_vbc, in
         the reference's order;
@@ -67,8 +68,16 @@ class Main3D:
         physics=False at the same place in the sequence.
         diags: a diags.Diags (DIAGNOSTICS_TS applications): handed to the backend here (set_diagnostics); every step issues
         set_diags after set_zeta and before set_avg (main3d.F:490-492), and pre_step3d, t3dmix2 and step3d_t write the
-        budget terms; the host fetches them with backend.get_diagnostic."""
+        budget terms; the host fetches them with backend.get_diagnostic.
+        data: a data.Data (the records get_data has read): its records are handed to the backend here and every later
+        Data.load goes there too; every step issues set_data((iic - ntstart) * dt, dt) first, at the place of main3d.F:222:
+        before ini_fields, ana_srflux / bulk_flux / set_vbc and tides, and keeps the flag it returns in `last_synchro`
+        (set_2dfld.F:139-141: a new record is due before the next step).  With None the sequence is unchanged."""
         self.be = backend
+        self.data = data
+        self.last_synchro = 0
+        if data is not None:
+            data.attach(backend)
         self.tides = tides
         if tides is not None:
             backend.set_tides(tides)
@@ -115,6 +124,8 @@ class Main3D:
         be, s = self.be, self
         self._rotate()
         s = self.s
+        if self.data is not None:             # main3d.F:219-224: before ini_fields, whose boundary conditions read the data
+            self.last_synchro = be.set_data((self.iic - self.ntstart) * be.st.p.dt, be.st.p.dt)
         if self.iic == self.ntstart:          # main3d.F:269-283: all time levels and the other initial fields
             be.call("ini_zeta", s)
             be.call("set_depth", s)
