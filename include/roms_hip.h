@@ -244,6 +244,25 @@ int roms_hip_bulk_flux(const roms_step_idx_t *s);
 int roms_hip_set_vbc(const roms_step_idx_t *s);
 /* lmd_vmix(ng,tile) = lmd_vmix_tile + lmd_skpp + lmd_finish   ROMS/Nonlinear/lmd_vmix.F:37 */
 int roms_hip_lmd_vmix(const roms_step_idx_t *s);
+/* LMD_BKPP: the K-profile bottom boundary layer, lmd_bkpp(ng,tile), ROMS/Nonlinear/lmd_bkpp.F:44 -> lmd_bkpp_tile
+ * (:95, the text :233-804), which lmd_vmix calls between lmd_skpp and lmd_finish (lmd_vmix.F:83-89).  Built as the file
+ * is (its own SASHA) with RI_SPLINES and SALINITY, MASKING at run time; not built: LMD_SHAPIRO, LMD_DDMIX, the form
+ * without RI_SPLINES, LIMIT_VDIFF / LIMIT_VVISC, the average avghbbl.
+ *
+ * roms_hip_set_kpp(1, hbbl) switches it on: the library allocates hbbl (double), kbbl and ksbl (int) of mod_mixing.F on
+ * (LBi:UBi, LBj:UBj); hbbl is set from the host array (a restart: get_state.F reads it, and the depth of the previous
+ * step enters bl_dpth at lmd_bkpp.F:243) or, with NULL, to zero as mod_mixing.F leaves it.  From then on
+ * roms_hip_lmd_vmix runs lmd_skpp, lmd_bkpp and lmd_finish in the reference's order, with bc_r2d_tile(hbbl) and its
+ * exchange (lmd_bkpp.F:577-586) beside those of hsbl; the per-step call stays the one roms_hip_lmd_vmix.
+ * roms_hip_set_kpp(0, NULL) releases the arrays and roms_hip_lmd_vmix launches what it launched before;
+ * roms_hip_set_bounds drops them.  Refused by name, leaving the library as it was: a call before bounds / params, a
+ * value other than 0 / 1, NAT < 2 or no salinity.
+ *
+ * roms_hip_get_kpp copies "hbbl" (n doubles), "kbbl" or "ksbl" (n ints; ksbl as lmd_skpp.F:653-658, :787 leave it, 0
+ * included) to host memory, ordered after the kernels issued; n = the points of (LBi:UBi, LBj:UBj) is checked.  wrt_rst.F
+ * writes hbbl: the host fetches it here. */
+int roms_hip_set_kpp(int lmd_bkpp, const double *hbbl);
+int roms_hip_get_kpp(const char *name, void *host, long n);
 /* ana_srflux(ng,tile,model)        ROMS/Functionals/ana_srflux.h:2, the ALBEDO branch (:120-150) the BENCHMARK
  * application uses: shortwave radiation from the zenith angle at (lonr, latr) for the day of the year and the
  * hour that caldate (ROMS/Utility/dateclock.F:73) returns for tdays(ng) -- the host passes those two numbers --

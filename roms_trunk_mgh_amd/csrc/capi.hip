@@ -208,6 +208,14 @@ extern "C" int roms_hip_check_guards(void)
     for (int q = 0; q < n; q++)
       if ((rc = check(name[q], -1, base[q], count[q]))) return rc;
   }
+  {
+    const char *name[3];
+    const double *base[3];
+    long count[3];
+    const int n = kpp_arrays(name, base, count);
+    for (int q = 0; q < n; q++)
+      if ((rc = check(name[q], -1, base[q], count[q]))) return rc;
+  }
   for (int q = 0; q < ROMS_NWS3; q++)
     if ((rc = check("ws3", q, g_ctx.ws3_base[q], nij * (b.N + 1)))) return rc;
   for (int q = 0; q < 32; q++)
@@ -298,6 +306,7 @@ extern "C" int roms_hip_finalize(void)
   tides_release();
   data_release();
   dia_release();
+  kpp_release();
   if (g_ctx.devc) (void)hipFree(g_ctx.devc);
   g_ctx.devc = nullptr;
   if (g_ctx.stream) (void)hipStreamDestroy(g_ctx.stream);
@@ -660,6 +669,7 @@ extern "C" int roms_hip_set_bounds(const roms_bounds_t *b)
   tides_release();                         // ... and the tidal strips
   data_release();                          // ... and the records of set_data
   dia_release();                           // ... and the tracer diagnostics
+  kpp_release();                           // ... and hbbl, kbbl, ksbl of the bottom boundary layer
   halo_bounds_changed();                   // ... and the message plan has the old extents and ghost points
   g_ctx.b = *b;
   g_ctx.hostc.b = *b;

@@ -453,7 +453,9 @@ __device__ __forceinline__ void wscale(double Ustar, double sigma, double Bf, do
 // waiting on memory for 72 % of its wave-cycles, SQ_WAIT_ANY, with one level's loads in flight).
 #define LMD_SEG 5
 
-template <int NMAX>
+// BKPP (LMD_BKPP, roms_hip_set_kpp): lmd_bkpp runs between lmd_skpp and lmd_finish (lmd_vmix.F:83-89), so the last sweep
+// stores Akv / Akt without the lmd_finish increment -- k_lmd_bkpp adds it -- and ksbl goes to the library's array.
+template <int NMAX, bool BKPP = false>
 __global__ void __launch_bounds__(BLK_X *BLK_Y, 2)
 k_lmd_vmix(const RomsDev *__restrict__ c, int nstp, double lmd_Cg, double Vtc)
 {
@@ -757,6 +759,7 @@ k_lmd_vmix(const RomsDev *__restrict__ c, int nstp, double lmd_Cg, double Vtc)
     Gs1 = Gt1;
     dGs1dS = dGt1dS;
   }
+  if constexpr (BKPP) c->kpp.ksbl[a] = ksbl;                      // lmd_skpp.F:653-658, :787
   // ---------- upward again, LMD_SEG levels at a time: boundary-layer profiles, convective adjustment, final values ----------
   for (int kb = 1; kb <= N - 1; kb += LMD_SEG) {
     double nuA[LMD_SEG], zwA[LMD_SEG], bvA[LMD_SEG];
@@ -799,11 +802,236 @@ k_lmd_vmix(const RomsDev *__restrict__ c, int nstp, double lmd_Cg, double Vtc)
         cff = fmin(1.0, (lmd_bvfcon - cff) / lmd_bvfcon);
         double nu_sxc = 1.0 - cff * cff;
         nu_sxc = nu_sxc * nu_sxc * nu_sxc;
-        Akv[w3i(k)] = akv + lmd_nu0c * nu_sxc;
-        AkT[w3i(k)] = akt + lmd_nu0c * nu_sxc;
-        AkS[w3i(k)] = aks + lmd_nu0c * nu_sxc;
+        if constexpr (BKPP) {
+          Akv[w3i(k)] = akv;
+          AkT[w3i(k)] = akt;
+          AkS[w3i(k)] = aks;
+        } else {
+          Akv[w3i(k)] = akv + lmd_nu0c * nu_sxc;
+          AkT[w3i(k)] = akt + lmd_nu0c * nu_sxc;
+          AkS[w3i(k)] = aks + lmd_nu0c * nu_sxc;
+        }
       }
     }
+  }
+}
+
+// =================================================================================================
+// lmd_bkpp_tile (ROMS/Nonlinear/lmd_bkpp.F:233-804; LMD_BKPP with the file's own SASHA, RI_SPLINES, SALINITY, MASKING at
+// run time, no LMD_SHAPIRO), then the lmd_finish increment (lmd_vmix.F:524-540).  Runs behind k_lmd_vmix<NMAX, true>,
+// which left Akv / Akt without that increment and ksbl in the library's array.  Column-local, one thread per (i,j).
+// The plain form: the critical function FC(k) needs the reference values at the bottom, which need the BACK-SUBSTITUTED
+// derivative at level 1, so the descending sweep has to finish before the ascending one that searches; the three
+// derivative profiles wait in the 3-D scratch slots ws3[0..2] (forward values from the first sweep, overwritten by the
+// final ones in the second; every access is one double per lane along i) and the spline coefficient in LDS.  The
+// buoyancy-flux profile is recomputed where used (two exp), as in k_lmd_vmix.
+// =================================================================================================
+typedef int __attribute__((address_space(1))) *gi_t;
+
+template <int NMAX>
+__global__ void __launch_bounds__(BLK_X *BLK_Y)
+k_lmd_bkpp(const RomsDev *__restrict__ c, int nstp, double Vtc)
+{
+  DEV_PROLOGUE(c)
+  const roms_params_t &p = c->p;
+  const Blk XB = xcd_block();
+  const int i = b.Istr + XB.x * BLK_X + threadIdx.x;
+  const int j = b.Jstr + XB.y * BLK_Y + threadIdx.y;
+  if (i > b.Iend || j > b.Jend) return;
+  const long a = I2(i, j);
+  const double g = p.g, vonKar = 0.41, eps = 1.0E-10;
+  const double lmd_Ric = 0.3, lmd_cekman = 0.7, lmd_epsilon = 0.1, lmd_bvfcon = -2.0E-5, lmd_nu0c = 0.01;
+  const double gorho0 = g / p.rho0;
+  const gcd_t Hz = (gcd_t)c->F.Hz, pden = (gcd_t)c->F.pden, bvf = (gcd_t)c->F.bvf, z_w = (gcd_t)c->F.z_w;
+  const gcd_t u = (gcd_t)(c->F.u + (long)(nstp - 1) * n3r), v = (gcd_t)(c->F.v + (long)(nstp - 1) * n3r);
+  const gd_t Akv = (gd_t)c->F.Akv, AkT = (gd_t)c->F.Akt, AkS = (gd_t)(c->F.Akt + n3w);
+  const gd_t dR = (gd_t)c->ws3[0], dU = (gd_t)c->ws3[1], dV = (gd_t)c->ws3[2];     // W-levels 1..N-1 of this column
+  const gd_t hbbl_a = (gd_t)c->kpp.hbbl;
+  auto r3i = [&](int k) { return a + (long)(k - 1) * nij; };     // rho-type level k = 1..N
+  auto w3i = [&](int k) { return a + (long)k * nij; };           // W-type level k = 0..N
+  constexpr int NTH = BLK_X * BLK_Y;
+  __shared__ double s_fc[(NMAX - 1) * NTH];                      // the spline coefficient FC(k), k = 1..N-1
+  double *const fc_col = s_fc + threadIdx.y * BLK_X + threadIdx.x;
+
+  const bool masking = p.masking != 0;
+  const double mr = masking ? (double)GF(rmask)[a] : 1.0;
+  const double zw0 = z_w[w3i(0)], zwN = z_w[w3i(N)];
+  // bl_dpth from the depth of the previous step (:243), Ustar from the bottom stress (:254)
+  double hbbl = hbbl_a[a];
+  double bl_dpth = lmd_epsilon * (hbbl - zw0);
+  const double b1 = 0.5 * (GF(bustr)[a] + GF(bustr)[a + 1]), b2 = 0.5 * (GF(bvstr)[a] + GF(bvstr)[a + ni]);
+  double Ustar = sqrt(sqrt(b1 * b1 + b2 * b2));
+  if (masking) Ustar = Ustar * mr;                               // :257
+  // bottom turbulent and surface radiative buoyancy forcing (:272-277), total buoyancy flux at depth z (:288-300)
+  const double alpha = GF(alpha)[a], beta = GF(beta)[a];
+  const double Bo = g * (alpha * GF(btflx)[a] - beta * GF(btflx)[a + nij]);
+  const double Bosol = g * alpha * GF(srflx)[a];
+  auto bflux_z = [&](double zgrid) {
+    double bf = (Bo + Bosol * (1.0 - swfrac(p, zgrid)));
+    if (masking) bf = bf * mr;                                   // :299
+    return bf;
+  };
+
+  // ---------- the three parabolic splines, forward (:316-336) ----------
+  {
+    double FCm = 0.0, dRm = 0.0, dUm = 0.0, dVm = 0.0;
+    long q = r3i(1);
+    double hzA = Hz[q], pdA = pden[q], uaA = u[q], ubA = u[q + 1], vaA = v[q], vbA = v[q + ni];
+    for (int k = 1; k <= N - 1; k++) {
+      q = r3i(k + 1);
+      const double hzB = Hz[q], pdB = pden[q], uaB = u[q], ubB = u[q + 1], vaB = v[q], vbB = v[q + ni];
+      const double cff = 1.0 / (2.0 * hzB + hzA * (2.0 - FCm));
+      FCm = cff * hzB;
+      dRm = cff * (6.0 * (pdB - pdA) - hzA * dRm);
+      dUm = cff * (3.0 * (uaB - uaA + ubB - ubA) - hzA * dUm);
+      dVm = cff * (3.0 * (vaB - vaA + vbB - vbA) - hzA * dVm);
+      fc_col[(k - 1) * NTH] = FCm;
+      dR[w3i(k)] = dRm; dU[w3i(k)] = dUm; dV[w3i(k)] = dVm;
+      hzA = hzB; pdA = pdB; uaA = uaB; ubA = ubB; vaA = vaB; vbA = vbB;
+    }
+  }
+  // ---------- back-substitution (:337-348); the values of level 1 stay in registers ----------
+  double dR1 = 0.0, dU1 = 0.0, dV1 = 0.0;                        // x(N) = 0
+  for (int k = N - 1; k >= 1; k--) {
+    const double fc = fc_col[(k - 1) * NTH];
+    dR1 = dR[w3i(k)] - fc * dR1;
+    dU1 = dU[w3i(k)] - fc * dU1;
+    dV1 = dV[w3i(k)] - fc * dV1;
+    dR[w3i(k)] = dR1; dU[w3i(k)] = dU1; dV[w3i(k)] = dV1;
+  }
+  // ---------- the reference values at the bottom (:408-413): x(0) = 0 ----------
+  const double cff1 = 1.0 / 3.0, cff2 = 1.0 / 6.0;
+  double Rref, Uref, Vref;
+  {
+    const long q = r3i(1);
+    const double hz = Hz[q];
+    Rref = pden[q] - hz * (cff1 * 0.0 + cff2 * dR1);
+    Uref = 0.5 * (u[q] + u[q + 1]) - hz * (cff1 * 0.0 + cff2 * dU1);
+    Vref = 0.5 * (v[q] + v[q + ni]) - hz * (cff1 * 0.0 + cff2 * dV1);
+  }
+  // ---------- the critical function FC(k) (:419-465) and the first crossing from the bottom (:474-482), level by
+  // level until it is found: the levels above it cannot change hbbl / kbbl any more ----------
+  int kbbl = N;
+  hbbl = zwN;
+  {
+    double FCkm = 0.0, zwm = zw0;                                // FC(i,0) = 0
+    double dRm = 0.0, dUm = 0.0, dVm = 0.0;
+    for (int k = 1; k <= N - 1 && kbbl == N; k++) {
+      const long q = r3i(k), qw = w3i(k);
+      const double zwk = z_w[qw];
+      const double dRk = dR[qw], dUk = dU[qw], dVk = dV[qw];
+      const double depth = zwk - zw0;
+      const double bf = bflux_z(zwN - zwk);
+      const double sigma = (bf < 0.0) ? fmin(bl_dpth, depth) : depth;
+      double wmk, wsk;
+      wscale(Ustar, sigma, bf, wmk, wsk);
+      const double hz = Hz[q];
+      const double Rk = pden[q] + hz * (cff1 * dRk + cff2 * dRm);
+      const double Uk = 0.5 * (u[q] + u[q + 1]) + hz * (cff1 * dUk + cff2 * dUm);
+      const double Vk = 0.5 * (v[q] + v[q + ni]) + hz * (cff1 * dVk + cff2 * dVm);
+      const double Ritop = -gorho0 * (Rk - Rref) * depth;
+      const double Ribot = (Uk - Uref) * (Uk - Uref) + (Vk - Vref) * (Vk - Vref) + Vtc * depth * wsk * sqrt(fabs(bvf[qw]));
+      const double FCk = Ritop - lmd_Ric * Ribot;
+      if (FCk > 0.0) {
+        hbbl = (zwk * FCkm - zwm * FCk) / (FCkm - FCk);
+        kbbl = k;
+      }
+      FCkm = FCk; zwm = zwk;
+      dRm = dRk; dUm = dUk; dVm = dVk;
+    }
+  }
+  // ---------- the Ekman limit, the clamps and the mask (:528-536) ----------
+  if (Ustar >= 0.0) {
+    const double hekman = lmd_cekman * Ustar / fmax(fabs(GF(f)[a]), eps) - GF(h)[a];
+    hbbl = fmin(hekman, hbbl);
+  }
+  hbbl = fmin(hbbl, zwN);
+  hbbl = fmax(hbbl, zw0);
+  if (masking) hbbl = hbbl * mr;
+  hbbl_a[a] = hbbl;
+  if (!b.NSperiodic) {                                           // bc_r2d_tile: zero gradient at closed walls
+    if (b.south_edge && j == b.Jstr) hbbl_a[a - ni] = hbbl;
+    if (b.north_edge && j == b.Jend) hbbl_a[a + ni] = hbbl;
+  }
+  // ---------- kbbl (:592-597) and the buoyancy flux at the final depth (:607-621) ----------
+  kbbl = N;
+  for (int k = 1; k <= N - 1 && kbbl == N; k++)
+    if (z_w[w3i(k)] > hbbl) kbbl = k;
+  ((gi_t)c->kpp.kbbl)[a] = kbbl;
+  double Bfbot;
+  {
+    double zgrid = zwN - hbbl;
+    if (masking) zgrid = zgrid * mr;
+    Bfbot = bflux_z(zgrid);
+  }
+  // ---------- velocity scales and shape functions at hbbl (:635-721) ----------
+  bl_dpth = lmd_epsilon * (hbbl - zw0);
+  double wm, ws;
+  {
+    const double cff = (Bfbot > 0.0) ? 1.0 : lmd_epsilon;
+    wscale(Ustar, cff * (hbbl - zw0), Bfbot, wm, ws);
+  }
+  const double f1 = 5.0 * fmax(0.0, Bfbot) * vonKar / (Ustar * Ustar * Ustar * Ustar + eps);
+  const double zbl = hbbl - zw0;
+  double Gm1, Gt1, Gs1, dGm1dS, dGt1dS, dGs1dS;
+  {
+    const int k = kbbl;
+    const double zk = z_w[w3i(k)], zm = z_w[w3i(k - 1)];
+    const double cff = 1.0 / (zk - zm);
+    const double cff_dn = cff * (hbbl - zm);
+    const double cff_up = cff * (zk - hbbl);
+    double K_bl = cff_dn * Akv[w3i(k)] + cff_up * Akv[w3i(k - 1)];
+    double dK_bl = -cff * (Akv[w3i(k)] - Akv[w3i(k - 1)]);
+    Gm1 = K_bl / (zbl * wm + eps);
+    if (masking) Gm1 = Gm1 * mr;                                 // :693
+    dGm1dS = fmin(0.0, K_bl * f1 - dK_bl / (wm + eps));
+    K_bl = cff_dn * AkT[w3i(k)] + cff_up * AkT[w3i(k - 1)];
+    dK_bl = -cff * (AkT[w3i(k)] - AkT[w3i(k - 1)]);
+    Gt1 = K_bl / (zbl * ws + eps);
+    if (masking) Gt1 = Gt1 * mr;                                 // :704
+    dGt1dS = fmin(0.0, K_bl * f1 - dK_bl / (ws + eps));
+    K_bl = cff_dn * AkS[w3i(k)] + cff_up * AkS[w3i(k - 1)];
+    dK_bl = -cff * (AkS[w3i(k)] - AkS[w3i(k - 1)]);
+    Gs1 = K_bl / (zbl * ws + eps);
+    if (masking) Gs1 = Gs1 * mr;                                 // :716
+    dGs1dS = fmin(0.0, K_bl * f1 - dK_bl / (ws + eps));
+  }
+  // ---------- the merged profile (:727-804), then the lmd_finish increment (lmd_vmix.F:524-540) ----------
+  const int ksbl = ((gi_t)c->kpp.ksbl)[a];
+  for (int k = 1; k <= N - 1; k++) {
+    const long qw = w3i(k);
+    const double zwk = z_w[qw];
+    double akv = Akv[qw], akt = AkT[qw], aks = AkS[qw];
+    if (zwk < hbbl) {
+      const double depth = zwk - zw0;
+      const double bf = bflux_z(zwN - zwk);
+      double sigma = (bf < 0.0) ? fmin(bl_dpth, depth) : depth;
+      double wmk, wsk;
+      wscale(Ustar, sigma, bf, wmk, wsk);
+      sigma = depth / (hbbl - zw0 + eps);
+      if (masking) sigma = sigma * mr;                           // :765
+      const double a1 = sigma - 2.0, a2 = 3.0 - 2.0 * sigma, a3 = sigma - 1.0;
+      const double Gm = a1 + a2 * Gm1 + a3 * dGm1dS;
+      const double Gt = a1 + a2 * Gt1 + a3 * dGt1dS;
+      const double Gs = a1 + a2 * Gs1 + a3 * dGs1dS;
+      // the maximum only where the two boundary layers overlap (:785)
+      if (k > ksbl) {
+        akv = fmax(akv, depth * wmk * (1.0 + sigma * Gm));
+        akt = fmax(akt, depth * wsk * (1.0 + sigma * Gt));
+        aks = fmax(aks, depth * wsk * (1.0 + sigma * Gs));
+      } else {
+        akv = depth * wmk * (1.0 + sigma * Gm);
+        akt = depth * wsk * (1.0 + sigma * Gt);
+        aks = depth * wsk * (1.0 + sigma * Gs);
+      }
+    }
+    double cff = fmax(bvf[qw], lmd_bvfcon);
+    cff = fmin(1.0, (lmd_bvfcon - cff) / lmd_bvfcon);
+    double nu_sxc = 1.0 - cff * cff;
+    nu_sxc = nu_sxc * nu_sxc * nu_sxc;
+    Akv[qw] = akv + lmd_nu0c * nu_sxc;
+    AkT[qw] = akt + lmd_nu0c * nu_sxc;
+    AkS[qw] = aks + lmd_nu0c * nu_sxc;
   }
 }
 
@@ -847,6 +1075,92 @@ __global__ void k_lmd_edges(const RomsDev *__restrict__ c, int phase)
 
 }  // namespace
 
+// ---- LMD_BKPP: the switch and hbbl, kbbl, ksbl of mod_mixing.F (roms_hip_set_kpp / roms_hip_get_kpp) ----
+namespace {
+const char *const k_kpp_name[3] = {"hbbl", "kbbl", "ksbl"};
+struct KppStore {
+  double *dev[3] = {nullptr, nullptr, nullptr}, *base[3] = {nullptr, nullptr, nullptr};
+  long count[3] = {0, 0, 0};                                     // doubles of the allocation (two ints per double)
+  long nij = 0;
+} g_kpp;
+}  // namespace
+
+void kpp_release()
+{
+  for (int q = 0; q < 3; q++) {
+    guarded_free(&g_kpp.dev[q], &g_kpp.base[q]);
+    g_kpp.count[q] = 0;
+  }
+  g_kpp.nij = 0;
+  g_ctx.hostc.kpp = RomsKpp{};
+  g_ctx.devc_dirty = true;
+}
+
+int kpp_arrays(const char *name[3], const double *base[3], long count[3])
+{
+  if (!g_kpp.dev[0]) return 0;
+  for (int q = 0; q < 3; q++) { name[q] = k_kpp_name[q]; base[q] = g_kpp.base[q]; count[q] = g_kpp.count[q]; }
+  return 3;
+}
+
+extern "C" int roms_hip_set_kpp(int lmd_bkpp, const double *hbbl)
+{
+  const char *me = "roms_hip_set_kpp";
+  if (!g_ctx.inited || !g_ctx.have_bounds || !g_ctx.have_params)
+    return roms_fail(me, "roms_hip_init, roms_hip_set_bounds and roms_hip_set_params come first");
+  if (lmd_bkpp != 0 && lmd_bkpp != 1) return roms_fail(me, "kpp: lmd_bkpp is 0 or 1");
+  if (lmd_bkpp == 0) {
+    if (g_kpp.dev[0]) HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+    kpp_release();
+    return 0;
+  }
+  const roms_bounds_t &b = g_ctx.b;
+  if (b.NAT < 2 || !g_ctx.p.salinity) return roms_fail(me, "kpp: LMD_BKPP is built for the SALINITY set-up (NAT = 2)");
+  const long nij = (long)(b.UBi - b.LBi + 1) * (long)(b.UBj - b.LBj + 1);
+  HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+  if (!g_kpp.dev[0]) {
+    const long n[3] = {nij, (nij + 1) / 2, (nij + 1) / 2};
+    for (int q = 0; q < 3; q++) {
+      int rc = guarded_alloc(&g_kpp.dev[q], &g_kpp.base[q], n[q]);
+      if (rc) { kpp_release(); return rc; }
+      g_kpp.count[q] = n[q];
+    }
+    g_kpp.nij = nij;
+  }
+  // hbbl of the restart file, or zero as mod_mixing.F leaves it; kbbl and ksbl are outputs and start at zero
+  if (hbbl) HIP_TRY(hipMemcpyAsync(g_kpp.dev[0], hbbl, sizeof(double) * nij, hipMemcpyHostToDevice, g_ctx.stream));
+  else HIP_TRY(hipMemsetAsync(g_kpp.dev[0], 0, sizeof(double) * nij, g_ctx.stream));
+  for (int q = 1; q < 3; q++) HIP_TRY(hipMemsetAsync(g_kpp.dev[q], 0, sizeof(double) * g_kpp.count[q], g_ctx.stream));
+  HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+  RomsKpp &K = g_ctx.hostc.kpp;
+  K.bkpp = 1;
+  K.hbbl = g_kpp.dev[0];
+  K.kbbl = reinterpret_cast<int *>(g_kpp.dev[1]);
+  K.ksbl = reinterpret_cast<int *>(g_kpp.dev[2]);
+  g_ctx.devc_dirty = true;
+  return 0;
+}
+
+extern "C" int roms_hip_get_kpp(const char *name, void *host, long n)
+{
+  const char *me = "roms_hip_get_kpp";
+  if (!g_ctx.inited) return roms_fail(me, "library not initialised");
+  if (!name || !host) return roms_fail(me, "kpp: null argument");
+  for (int q = 0; q < 3; q++) {
+    if (strcmp(name, k_kpp_name[q])) continue;
+    if (!g_kpp.dev[q]) return roms_fail(me, "kpp: LMD_BKPP is not switched on (roms_hip_set_kpp)");
+    if (n != g_kpp.nij) {
+      char msg[200];
+      snprintf(msg, sizeof msg, "kpp: %s has %ld elements, the host array %ld", name, g_kpp.nij, n);
+      return roms_fail(me, msg);
+    }
+    HIP_TRY(hipMemcpyAsync(host, g_kpp.dev[q], (q == 0 ? sizeof(double) : sizeof(int)) * n, hipMemcpyDeviceToHost, g_ctx.stream));
+    HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+    return 0;
+  }
+  return roms_fail(me, (std::string("kpp: unknown array ") + name).c_str());
+}
+
 extern "C" int roms_hip_lmd_vmix(const roms_step_idx_t *s)
 {
   int rc = roms_entry_check("roms_hip_lmd_vmix");
@@ -856,6 +1170,7 @@ extern "C" int roms_hip_lmd_vmix(const roms_step_idx_t *s)
   if (b.NAT < 2 || !g_ctx.p.salinity) return roms_fail("roms_hip_lmd_vmix", "built for the SALINITY set-up (NAT = 2)");
   const long nij = (long)(b.UBi - b.LBi + 1) * (b.UBj - b.LBj + 1);
   const long n3w = nij * (b.N + 1);
+  const bool bkpp = g_ctx.hostc.kpp.bkpp != 0;
   {
     ScopedTimer tm("lmd_vmix");
     // run-time constants of mod_scalars.F:4330 (lmd_Cg) and lmd_skpp.F:300 (Vtc), evaluated on the host
@@ -864,10 +1179,25 @@ extern "C" int roms_hip_lmd_vmix(const roms_step_idx_t *s)
     const double lmd_Cg = lmd_Cstar * vonKar * pow(lmd_cs * vonKar * lmd_epsilon, 1.0 / 3.0);
     const double Vtc = lmd_Cv * sqrt(-lmd_betaT) / (sqrt(lmd_cs * lmd_epsilon) * lmd_Ric * vonKar * vonKar);
     const dim3 grid = grid2d(b.Iend - b.Istr + 1, b.Jend - b.Jstr + 1);
-    if (b.N <= 32) hipLaunchKernelGGL(k_lmd_vmix<32>, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nstp, lmd_Cg, Vtc);
-    else if (b.N <= ROMS_MAXN) hipLaunchKernelGGL(k_lmd_vmix<ROMS_MAXN>, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nstp, lmd_Cg, Vtc);
-    else return roms_fail("roms_hip_lmd_vmix", "N > 64 not instantiated");
-    KERNEL_CHECK("k_lmd_vmix");
+    if (b.N > ROMS_MAXN) return roms_fail("roms_hip_lmd_vmix", "N > 64 not instantiated");
+    if (!bkpp) {
+      if (b.N <= 32) hipLaunchKernelGGL(k_lmd_vmix<32>, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nstp, lmd_Cg, Vtc);
+      else hipLaunchKernelGGL(k_lmd_vmix<ROMS_MAXN>, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nstp, lmd_Cg, Vtc);
+      KERNEL_CHECK("k_lmd_vmix");
+    } else {
+      // LMD_BKPP, lmd_vmix.F:83-89: lmd_skpp without the lmd_finish increment, then lmd_bkpp, which adds it (the Vtc of
+      // lmd_bkpp.F:233 is the expression of lmd_skpp.F:300)
+      if (b.N <= 32) {
+        hipLaunchKernelGGL((k_lmd_vmix<32, true>), grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nstp, lmd_Cg, Vtc);
+        KERNEL_CHECK("k_lmd_vmix");
+        hipLaunchKernelGGL(k_lmd_bkpp<32>, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nstp, Vtc);
+      } else {
+        hipLaunchKernelGGL((k_lmd_vmix<ROMS_MAXN, true>), grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nstp, lmd_Cg, Vtc);
+        KERNEL_CHECK("k_lmd_vmix");
+        hipLaunchKernelGGL(k_lmd_bkpp<ROMS_MAXN>, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nstp, Vtc);
+      }
+      KERNEL_CHECK("k_lmd_bkpp");
+    }
     const int nj = b.Jend - b.Jstr + 1, ni_ = b.Iend - b.Istr + 1;
     if (b.west_edge || b.east_edge)
       hipLaunchKernelGGL(k_lmd_edges, dim3((nj + 63) / 64, b.N + 1), dim3(64), 0, g_ctx.stream, g_ctx.devc, 0);
@@ -881,6 +1211,10 @@ extern "C" int roms_hip_lmd_vmix(const roms_step_idx_t *s)
   // generic edge kernel) + exchange; bc_w3d_tile(Akv), bc_w3d_tile(Akt(:,:,:,itrc)): wall rows + exchange
   if (!b.EWperiodic && (rc = bc_generic(LBV_ZETA, LBV_ZETA, g_ctx.dev[FID_hsbl], 1))) return rc;
   if ((rc = halo_exchange2d(GT_R, g_ctx.dev[FID_hsbl]))) return rc;
+  if (bkpp) {                                                    // bc_r2d_tile(hbbl) + exchange, lmd_bkpp.F:577-586
+    if (!b.EWperiodic && (rc = bc_generic(LBV_ZETA, LBV_ZETA, g_kpp.dev[0], 1))) return rc;
+    if ((rc = halo_exchange2d(GT_R, g_kpp.dev[0]))) return rc;
+  }
   if ((rc = bc_w3d(g_ctx.dev[FID_Akv]))) return rc;
   for (int it = 0; it < b.NAT; it++)
     if ((rc = bc_w3d(g_ctx.dev[FID_Akt] + (long)it * n3w))) return rc;

@@ -113,6 +113,15 @@ struct RomsDia {
 // DiaTwrk(:,:,:,itrc,idiag) of term `id` (device code; n3r = points of a rho-array)
 #define DIA_PLANE(c, id, itrc, n3r) ((gd_t)((c)->dia.wrk + ((long)(c)->dia.ix[id] * (c)->b.NT + ((itrc) - 1)) * (n3r)))
 
+// LMD_BKPP (roms_hip_set_kpp, k_physics.hip): the switch and the library-owned arrays of mod_mixing.F the bottom
+// boundary layer adds -- hbbl (double), kbbl and ksbl (int), all (LBi:UBi, LBj:UBj).  bkpp = 0: off, and no kernel reads
+// this block.
+struct RomsKpp {
+  int bkpp;
+  double *hbbl;
+  int *kbbl, *ksbl;
+};
+
 struct RomsDev {
   roms_bounds_t b;
   roms_params_t p;
@@ -125,6 +134,7 @@ struct RomsDev {
   RomsClima clima;      // climatology nudging, all flags zero without
   RomsTides tides;      // tidal boundary forcing, ntc = 0 without
   RomsDia dia;          // tracer diagnostics, wrk = nullptr without
+  RomsKpp kpp;          // KPP bottom boundary layer, bkpp = 0 without
 };
 
 struct RomsCtx {
@@ -435,6 +445,8 @@ bool dia_on();                            // ... diagnostics are switched on (th
 int dia_check(const char *where);         // ... and what they are not built with, refused by name (0 when off)
 int dia_rate(int nnew);                   // ... step3d_t.F:1598-1611 on IstrR:IendR, JstrR:JendR (k_dia_rate)
 int dia_arrays(const char *name[4], const double *base[4], long count[4]);   // ... its arrays, for roms_hip_check_guards
+void kpp_release();                       // k_physics.hip: frees what roms_hip_set_kpp allocated
+int kpp_arrays(const char *name[3], const double *base[3], long count[3]);   // ... its arrays, for roms_hip_check_guards
 // lateral boundary conditions on the S/N edges (k_base.hip); s = the barotropic time indices (Chapman, Flather),
 // nstp = the time level the radiation condition compares with
 int bc_zeta(int kout, const roms_step_idx_t *s);

@@ -293,6 +293,20 @@ MODULE roms_hip_mod
       IMPORT :: c_int, roms_step_idx_t
       TYPE(roms_step_idx_t), INTENT(in) :: s
     END FUNCTION
+    !  LMD_BKPP: once after roms_hip_set_params, lmd_bkpp = 1 and C_LOC(MIXING(ng)%hbbl(LBi,LBj)) after get_state has read
+    !  it (C_NULL_PTR: zero, as mod_mixing.F leaves it); roms_hip_lmd_vmix then carries lmd_bkpp.  For wrt_rst / wrt_his:
+    !  name = 'hbbl'//C_NULL_CHAR (doubles), 'kbbl' or 'ksbl' (C ints), n = the points of (LBi:UBi,LBj:UBj)
+    INTEGER(c_int) FUNCTION roms_hip_set_kpp (lmd_bkpp, hbbl) BIND(C, name='roms_hip_set_kpp')
+      IMPORT :: c_int, c_ptr
+      INTEGER(c_int), VALUE :: lmd_bkpp
+      TYPE(c_ptr), VALUE :: hbbl
+    END FUNCTION
+    INTEGER(c_int) FUNCTION roms_hip_get_kpp (name, host, n) BIND(C, name='roms_hip_get_kpp')
+      IMPORT :: c_int, c_long, c_char, c_ptr
+      CHARACTER(kind=c_char), INTENT(in) :: name(*)
+      TYPE(c_ptr), VALUE :: host
+      INTEGER(c_long), VALUE :: n
+    END FUNCTION
     !  asynchronous snapshot for output / wrt_his / wrt_rst: ids(n) = FID_* of the fields wanted
     INTEGER(c_int) FUNCTION roms_hip_snapshot_begin (ids, n) BIND(C, name='roms_hip_snapshot_begin')
       IMPORT :: c_int
@@ -492,7 +506,7 @@ MODULE roms_hip_mod
   PUBLIC :: roms_hip_step3d_uv, roms_hip_step3d_t, roms_hip_bulk_flux, roms_hip_set_vbc, roms_hip_lmd_vmix
   PUBLIC :: roms_hip_ana_srflux, roms_hip_wvelocity, roms_hip_diag, roms_hip_snapshot_begin, roms_hip_snapshot_end
   PUBLIC :: roms_hip_ini_zeta, roms_hip_ini_fields, roms_hip_gls_prestep, roms_hip_gls_corstep, roms_hip_wetdry
-  PUBLIC :: roms_hip_set_sources, roms_hip_set_clima
+  PUBLIC :: roms_hip_set_sources, roms_hip_set_clima, roms_hip_set_kpp, roms_hip_get_kpp
   PUBLIC :: roms_hip_set_averages, roms_hip_set_avg, roms_hip_get_average, roms_hip_average_device_ptr, roms_hip_avg_phase
   PUBLIC :: roms_hip_set_diagnostics, roms_hip_set_diags, roms_hip_get_diagnostic, roms_hip_dia_index
   PUBLIC :: roms_hip_set_floats, roms_hip_floats_put, roms_hip_floats_get, roms_hip_step_floats

@@ -46,7 +46,8 @@ DECLARED_SYMBOLS = (
      "roms_hip_avg_phase", "roms_hip_set_floats", "roms_hip_floats_put", "roms_hip_floats_get",
      "roms_hip_step_floats", "roms_hip_set_tides", "roms_hip_tides", "roms_hip_set_diagnostics",
      "roms_hip_get_diagnostic", "roms_hip_dia_index", "roms_hip_set_data_record", "roms_hip_set_data_point",
-     "roms_hip_set_data", "roms_hip_set_data_factors", "roms_hip_get_clima"] + ["roms_hip_" + e for e in ENTRIES])
+     "roms_hip_set_data", "roms_hip_set_data_factors", "roms_hip_get_clima",
+     "roms_hip_set_kpp", "roms_hip_get_kpp"] + ["roms_hip_" + e for e in ENTRIES])
 
 
 _DP = C.POINTER(C.c_double)
@@ -109,6 +110,8 @@ def load():
     lib.roms_hip_set_data_point.argtypes = [C.c_int] * 3 + [C.c_double, C.c_int, C.c_double]
     lib.roms_hip_set_data.argtypes = [C.c_double, C.c_double, _ip]
     lib.roms_hip_set_data_factors.argtypes = [C.c_double] * 4 + [C.c_int, C.c_int, _DP, _DP, _ip]
+    lib.roms_hip_set_kpp.argtypes = [C.c_int, C.c_void_p]
+    lib.roms_hip_get_kpp.argtypes = [C.c_char_p, C.c_void_p, C.c_long]
     lib.roms_hip_set_halo_relay.argtypes = [RELAY_FN, C.c_void_p]
     if hasattr(lib, "roms_hip_tile_neighbors"):
         lib.roms_hip_tile_neighbors.argtypes = [C.c_int] * 7 + [C.POINTER(C.c_int)]
@@ -123,6 +126,29 @@ def set_data_factors(time, dt, T1, T2, Tindex, onerec=False):
     rc = load().roms_hip_set_data_factors(float(time), float(dt), float(T1), float(T2), int(Tindex), int(bool(onerec)),
                                           C.byref(f1), C.byref(f2), C.byref(syn))
     return None if rc else (f1.value, f2.value, syn.value)
+
+
+KPP_ARRAYS = {"hbbl": np.float64, "kbbl": np.int32, "ksbl": np.int32}
+
+
+def kpp_args(state, lmd_bkpp, hbbl=None):
+    """The arguments of roms_hip_set_kpp for the tile `state`, checked on the host: lmd_bkpp is a bool (or 0 / 1); hbbl
+    is None (zero, as mod_mixing.F leaves it) or an array of the tile's (LBi:UBi, LBj:UBj), and only goes with the switch
+    on.  Returns (int, array or None); the array is a Fortran-ordered float64 copy the caller keeps alive over the call."""
+    if isinstance(lmd_bkpp, (bool, np.bool_)):
+        lmd_bkpp = int(lmd_bkpp)
+    if not isinstance(lmd_bkpp, (int, np.integer)) or lmd_bkpp not in (0, 1):
+        raise ValueError(f"set_kpp: lmd_bkpp is False / True (0 / 1), not {lmd_bkpp!r}")
+    if hbbl is None:
+        return int(lmd_bkpp), None
+    if not lmd_bkpp:
+        raise ValueError("set_kpp: hbbl goes with lmd_bkpp = True only")
+    a = np.asfortranarray(hbbl, dtype=np.float64)
+    if a.shape != (state.ni, state.nj):
+        raise ValueError(f"set_kpp: hbbl has shape {a.shape}, the tile's rho points are {(state.ni, state.nj)}")
+    if not np.isfinite(a).all():
+        raise ValueError("set_kpp: hbbl is not finite")
+    return 1, a
 
 
 def tile_neighbors(rank, ntileI, ntileJ, Nghost, NghostPoints, EWperiodic, NSperiodic):
@@ -245,6 +271,22 @@ class RomsHip:
         out = np.zeros(self.diags.shape(name), dtype=np.float64, order="F")
         self._chk(self.l.roms_hip_get_diagnostic(_diags.DIA_ID[name], int(itrc), int(bool(accumulated)), out.ctypes.data,
                                                  out.size), "get_diagnostic " + name)
+        return out
+
+    def set_kpp(self, lmd_bkpp=True, hbbl=None):
+        """LMD_BKPP, the KPP bottom boundary layer inside lmd_vmix -> roms_hip_set_kpp; hbbl = the depth of a restart
+        file on the tile's rho points, None = zero; False releases hbbl, kbbl, ksbl (kpp_args checks the arguments)."""
+        on, a = kpp_args(self.st, lmd_bkpp, hbbl)
+        self._chk(self.l.roms_hip_set_kpp(on, None if a is None else a.ctypes.data), "set_kpp")
+        self.bkpp = bool(on)
+
+    def get_kpp(self, name):
+        """"hbbl" (float64), "kbbl" or "ksbl" (int32) of the bottom boundary layer on the tile's rho points
+        (roms_hip_get_kpp)."""
+        if name not in KPP_ARRAYS:
+            raise ValueError(f"get_kpp: {name!r} is not one of {sorted(KPP_ARRAYS)}")
+        out = np.zeros((self.st.ni, self.st.nj), dtype=KPP_ARRAYS[name], order="F")
+        self._chk(self.l.roms_hip_get_kpp(name.encode(), out.ctypes.data, out.size), "get_kpp " + name)
         return out
 
     def set_floats(self, floats):

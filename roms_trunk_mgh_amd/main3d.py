@@ -14,7 +14,8 @@ against either backend (`hip.RomsHip` = the product, or the CPU oracle in tests)
     main3d.F:280      set_data -> ana_srflux           (physics=True, BENCHMARK: shortwave flux of the hour)
     main3d.F:388-394  bulk_flux, set_vbc               (physics=True; else fixed forcing inputs)
     main3d.F:395-397  set_tides                        (SSH_TIDES / UV_TIDES: tides=...)
-    main3d.F:467-475  lmd_vmix (physics=True; else fixed mixing inputs); omega; wvelocity (diagnostics=True)
+    main3d.F:467-475  lmd_vmix (physics=True; else fixed mixing inputs; bkpp=True: with lmd_bkpp inside, LMD_BKPP);
+                      omega; wvelocity (diagnostics=True)
     main3d.F:489      set_zeta
     main3d.F:491      set_diags                        (DIAGNOSTICS_TS: diags=...)
     main3d.F:494      set_avg                          (AVERAGES: averages=...)
@@ -48,7 +49,7 @@ def host_clock(tdays):
 
 class Main3D:
     def __init__(self, backend, ntstart=1, physics=False, diagnostics=False, ninfo=1, averages=None, floats=None, tides=None,
-                 diags=None, data=None):
+                 diags=None, data=None, bkpp=False, hbbl=None):
         """physics=True also runs the per-step physics that is on the device:
         bulk_flux and lmd_vmix (BULK_FLUXES / LMD_MIXING applications, i.e. BENCHMARK) and set_vbc, in
         the reference's order;
@@ -72,7 +73,9 @@ class Main3D:
         data: a data.Data (the records get_data has read): its records are handed to the backend here and every later
         Data.load goes there too; every step issues set_data((iic - ntstart) * dt, dt) first, at the place of main3d.F:222:
         before ini_fields, ana_srflux / bulk_flux / set_vbc and tides, and keeps the flag it returns in `last_synchro`
-        (set_2dfld.F:139-141: a new record is due before the next step).  With None the sequence is unchanged."""
+        (set_2dfld.F:139-141: a new record is due before the next step).  With None the sequence is unchanged.
+        bkpp=True (LMD_BKPP applications): set_kpp is issued here, once, with hbbl (the depth of a restart file; None =
+        zero, mod_mixing.F); the per-step call stays lmd_vmix, as the reference's lmd_vmix(ng, tile) is one call."""
         self.be = backend
         self.data = data
         self.last_synchro = 0
@@ -90,6 +93,9 @@ class Main3D:
         self.averages = averages
         if averages is not None:
             backend.set_averages(averages)
+        self.bkpp = bool(bkpp)
+        if bkpp:
+            backend.set_kpp(True, hbbl)
         self.physics = physics
         self.diagnostics = diagnostics
         self.ninfo = ninfo
