@@ -136,6 +136,12 @@ typedef struct roms_step_idx {
 #include "roms_step_idx.def"
 } roms_step_idx_t;
 
+/* Parameters of the NPZD_POWELL ecosystem model (roms_hip_set_biology): a table of its own, roms_bio.def, so that the
+ * three structs above keep their layout. */
+typedef struct roms_bio_powell {
+#include "roms_bio.def"
+} roms_bio_powell_t;
+
 #undef ROMS_MEMBER
 #undef ROMS_MEMBER_A
 #undef ROMS_MEMBER_A2
@@ -277,6 +283,27 @@ int roms_hip_ana_srflux(double yday, double hour);
  * MY25_MIXING applications bind the same two entries with roms_params_t.gls_mixing = 2. */
 int roms_hip_gls_prestep(const roms_step_idx_t *s);
 int roms_hip_gls_corstep(const roms_step_idx_t *s);
+/* BIOLOGY: biology(ng,tile)        ROMS/Nonlinear/biology.F:35, called between gls_corstep and step3d_t
+ * (main3d.F:795-797).  Built: NPZD_POWELL, npzd_powell_tile (ROMS/Nonlinear/Biology/npzd_Powell.h:91-661) with the
+ * default, strictly monotone end conditions of the sinking reconstruction; CONST_PAR at run time.  The routine never
+ * looks at rmask (land columns are computed as the reference computes them), stores t(:,:,:,nnew,idbio) on
+ * Istr:Iend, Jstr:Jend only and exchanges nothing: step3d_t does afterwards.  Not built: the other models (ids below,
+ * each refused by name), the LINEAR_CONTINUATION / NEUMANN end conditions, FLOAT_BIOLOGY, the TL / AD twins.
+ *
+ * roms_hip_set_biology(model, par, nbytes): model = ROMS_BIO_NONE drops the setting (par may be NULL, nbytes is not
+ * read); ROMS_BIO_NPZD_POWELL takes par = a roms_bio_powell_t of nbytes = sizeof(roms_bio_powell_t) bytes.  Refused by
+ * name, leaving the previous setting in force: a call before bounds / params, a model that is not built or unknown,
+ * another nbytes, an idbio entry outside NAT+1 .. NT or repeated, BioIter < 0, a sinking speed < 0.  BioIter = 0 is
+ * accepted and roms_hip_biology then returns at once (npzd_Powell.h:180).  roms_hip_set_bounds drops the setting.
+ *
+ * roms_hip_biology(s) uses s->nstp and s->nnew; refused before roms_hip_set_biology ("biology is not switched on") and
+ * for N < 4.  Timer entry: "biology". */
+enum roms_bio_model {
+  ROMS_BIO_NONE = 0, ROMS_BIO_NPZD_POWELL = 1, ROMS_BIO_NPZD_FRANKS = 2, ROMS_BIO_NPZD_IRON = 3, ROMS_BIO_FENNEL = 4,
+  ROMS_BIO_NEMURO = 5, ROMS_BIO_ECOSIM = 6, ROMS_BIO_HYPOXIA_SRM = 7, ROMS_BIO_RED_TIDE = 8
+};
+int roms_hip_set_biology(int model, const void *par, long nbytes);
+int roms_hip_biology(const roms_step_idx_t *s);
 /* wetdry(ng,tile,Tindex,.TRUE.)    ROMS/Nonlinear/wetdry.F:17 -> wetdry_ini_tile (:395): the initial wet/dry masks
  * from zeta, ubar, vbar of time level Tindex = s->kstp (initial.F:438-466; WET_DRY applications).  The per-call
  * update wetdry_tile (:93) runs inside roms_hip_step2d. */

@@ -98,10 +98,12 @@ def _parse_members(def_file):
     return out
 
 
-# the three structs of the C ABI, member for member as include/roms_hip.h declares them
+# the structs of the C ABI, member for member as include/roms_hip.h declares them: the three of the boundary and the
+# parameter block of the NPZD_POWELL biology (roms_hip_set_biology)
 STRUCTS = {"roms_bounds_t": _parse_members("roms_bounds.def"),
            "roms_params_t": _parse_members("roms_params.def"),
-           "roms_step_idx_t": _parse_members("roms_step_idx.def")}
+           "roms_step_idx_t": _parse_members("roms_step_idx.def"),
+           "roms_bio_powell_t": _parse_members("roms_bio.def")}
 _CTYPES = {"int": C.c_int, "double": C.c_double}
 
 
@@ -137,6 +139,15 @@ class Params(C.Structure):
 class StepIdx(C.Structure):
     """roms_step_idx_t -- mod_stepping.F indices, main3d.F:189-191,597-662."""
     _fields_ = _ctypes_fields(STRUCTS["roms_step_idx_t"])
+
+
+class BioPowell(C.Structure):
+    """roms_bio_powell_t -- the parameters of npzd_Powell_mod.h / npzd_Powell.in, idbio and Cp (roms_bio.def)."""
+    _fields_ = _ctypes_fields(STRUCTS["roms_bio_powell_t"])
+
+
+# enum roms_bio_model: the ecosystem models of the reference; only NPZD_POWELL is built
+BIO_MODEL = {n[len("ROMS_BIO_"):]: v for n, v in CONSTANTS.items() if n.startswith("ROMS_BIO_")}
 
 
 class Fields(C.Structure):

@@ -232,6 +232,7 @@ extern "C" int roms_abi_sizeof(int which)
   case 2: return (int)sizeof(roms_step_idx_t);
   case 3: return (int)sizeof(roms_fields_t);
   case 4: return (int)FID_COUNT;
+  case 5: return (int)sizeof(roms_bio_powell_t);
   }
   return -1;
 }
@@ -307,6 +308,7 @@ extern "C" int roms_hip_finalize(void)
   data_release();
   dia_release();
   kpp_release();
+  bio_release();
   if (g_ctx.devc) (void)hipFree(g_ctx.devc);
   g_ctx.devc = nullptr;
   if (g_ctx.stream) (void)hipStreamDestroy(g_ctx.stream);
@@ -670,6 +672,7 @@ extern "C" int roms_hip_set_bounds(const roms_bounds_t *b)
   data_release();                          // ... and the records of set_data
   dia_release();                           // ... and the tracer diagnostics
   kpp_release();                           // ... and hbbl, kbbl, ksbl of the bottom boundary layer
+  bio_release();                           // ... and the biology setting (its tracer indices belong to the old NT)
   halo_bounds_changed();                   // ... and the message plan has the old extents and ghost points
   g_ctx.b = *b;
   g_ctx.hostc.b = *b;

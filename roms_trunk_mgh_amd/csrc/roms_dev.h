@@ -122,6 +122,13 @@ struct RomsKpp {
   int *kbbl, *ksbl;
 };
 
+// BIOLOGY (roms_hip_set_biology, k_biology.hip): the model and its parameters.  model = ROMS_BIO_NONE: off, and no
+// kernel reads this block.
+struct RomsBio {
+  int model;
+  roms_bio_powell_t powell;
+};
+
 struct RomsDev {
   roms_bounds_t b;
   roms_params_t p;
@@ -135,6 +142,7 @@ struct RomsDev {
   RomsTides tides;      // tidal boundary forcing, ntc = 0 without
   RomsDia dia;          // tracer diagnostics, wrk = nullptr without
   RomsKpp kpp;          // KPP bottom boundary layer, bkpp = 0 without
+  RomsBio bio;          // biology, model = ROMS_BIO_NONE without
 };
 
 struct RomsCtx {
@@ -447,6 +455,7 @@ int dia_rate(int nnew);                   // ... step3d_t.F:1598-1611 on IstrR:I
 int dia_arrays(const char *name[4], const double *base[4], long count[4]);   // ... its arrays, for roms_hip_check_guards
 void kpp_release();                       // k_physics.hip: frees what roms_hip_set_kpp allocated
 int kpp_arrays(const char *name[3], const double *base[3], long count[3]);   // ... its arrays, for roms_hip_check_guards
+void bio_release();                       // k_biology.hip: drops the setting of roms_hip_set_biology
 // lateral boundary conditions on the S/N edges (k_base.hip); s = the barotropic time indices (Chapman, Flather),
 // nstp = the time level the radiation condition compares with
 int bc_zeta(int kout, const roms_step_idx_t *s);

@@ -99,6 +99,19 @@ MODULE roms_hip_mod
     INTEGER(c_int) :: ts_mix_min_strat
   END TYPE roms_params_t
 
+  !  mirrors `roms_bio_powell_t` of include/roms_hip.h member for member (include/roms_bio.def, where every member is
+  !  documented): the NPZD_POWELL parameters of mod_biology (npzd_Powell_mod.h) for grid ng, idbio and Cp of mod_scalars
+  TYPE, BIND(C), PUBLIC :: roms_bio_powell_t
+    INTEGER(c_int) :: BioIter, const_par, idbio(4)
+    REAL(c_double) :: AttSW, AttPhy, PhyIS, Vm_NO3, PhyMRD, PhyMRN, K_NO3, Ivlev
+    REAL(c_double) :: ZooGR, ZooEED, ZooEEN, ZooMRD, ZooMRN, DetRR, wPhy, wDet, PARfrac, Cp
+  END TYPE roms_bio_powell_t
+  !  ecosystem models = enum roms_bio_model of include/roms_hip.h; only ROMS_BIO_NPZD_POWELL is built, the others are
+  !  refused by name
+  INTEGER(c_int), PARAMETER, PUBLIC :: ROMS_BIO_NONE = 0, ROMS_BIO_NPZD_POWELL = 1, ROMS_BIO_NPZD_FRANKS = 2
+  INTEGER(c_int), PARAMETER, PUBLIC :: ROMS_BIO_NPZD_IRON = 3, ROMS_BIO_FENNEL = 4, ROMS_BIO_NEMURO = 5
+  INTEGER(c_int), PARAMETER, PUBLIC :: ROMS_BIO_ECOSIM = 6, ROMS_BIO_HYPOXIA_SRM = 7, ROMS_BIO_RED_TIDE = 8
+
   !  mirrors `roms_halo_msg_t` of include/roms_hip.h (host relay of the halo exchange)
   TYPE, BIND(C), PUBLIC :: roms_halo_msg_t
     INTEGER(c_int) :: peer, tag
@@ -307,6 +320,19 @@ MODULE roms_hip_mod
       TYPE(c_ptr), VALUE :: host
       INTEGER(c_long), VALUE :: n
     END FUNCTION
+    !  BIOLOGY (NPZD_POWELL): once after roms_hip_set_params, model = ROMS_BIO_NPZD_POWELL, par = C_LOC of a TARGET
+    !  roms_bio_powell_t, nbytes = C_SIZEOF of it (ROMS_BIO_NONE with C_NULL_PTR drops the setting); roms_hip_biology
+    !  in the place of CALL biology (ng, tile), main3d.F:795-797
+    INTEGER(c_int) FUNCTION roms_hip_set_biology (model, par, nbytes) BIND(C, name='roms_hip_set_biology')
+      IMPORT :: c_int, c_long, c_ptr
+      INTEGER(c_int), VALUE :: model
+      TYPE(c_ptr), VALUE :: par
+      INTEGER(c_long), VALUE :: nbytes
+    END FUNCTION
+    INTEGER(c_int) FUNCTION roms_hip_biology (s) BIND(C, name='roms_hip_biology')
+      IMPORT :: c_int, roms_step_idx_t
+      TYPE(roms_step_idx_t), INTENT(in) :: s
+    END FUNCTION
     !  asynchronous snapshot for output / wrt_his / wrt_rst: ids(n) = FID_* of the fields wanted
     INTEGER(c_int) FUNCTION roms_hip_snapshot_begin (ids, n) BIND(C, name='roms_hip_snapshot_begin')
       IMPORT :: c_int
@@ -507,6 +533,7 @@ MODULE roms_hip_mod
   PUBLIC :: roms_hip_ana_srflux, roms_hip_wvelocity, roms_hip_diag, roms_hip_snapshot_begin, roms_hip_snapshot_end
   PUBLIC :: roms_hip_ini_zeta, roms_hip_ini_fields, roms_hip_gls_prestep, roms_hip_gls_corstep, roms_hip_wetdry
   PUBLIC :: roms_hip_set_sources, roms_hip_set_clima, roms_hip_set_kpp, roms_hip_get_kpp
+  PUBLIC :: roms_hip_set_biology, roms_hip_biology
   PUBLIC :: roms_hip_set_averages, roms_hip_set_avg, roms_hip_get_average, roms_hip_average_device_ptr, roms_hip_avg_phase
   PUBLIC :: roms_hip_set_diagnostics, roms_hip_set_diags, roms_hip_get_diagnostic, roms_hip_dia_index
   PUBLIC :: roms_hip_set_floats, roms_hip_floats_put, roms_hip_floats_get, roms_hip_step_floats

@@ -29,7 +29,7 @@ def use_library(path):
 ENTRIES = ["set_massflux", "rho_eos", "omega", "set_zeta", "set_depth", "rhs3d",
            "pre_step3d", "prsgrd", "t3dmix2", "rhs3d_tile", "uv3dmix2", "step2d",
            "step3d_uv", "step3d_t", "bulk_flux", "set_vbc", "lmd_vmix", "wvelocity", "ini_zeta", "ini_fields",
-           "t3dmix4", "uv3dmix4", "gls_prestep", "gls_corstep", "wetdry", "set_avg", "set_diags"]
+           "t3dmix4", "uv3dmix4", "gls_prestep", "gls_corstep", "wetdry", "set_avg", "set_diags", "biology"]
 
 # every symbol include/roms_hip.h declares
 DECLARED_SYMBOLS = (
@@ -47,7 +47,7 @@ DECLARED_SYMBOLS = (
      "roms_hip_step_floats", "roms_hip_set_tides", "roms_hip_tides", "roms_hip_set_diagnostics",
      "roms_hip_get_diagnostic", "roms_hip_dia_index", "roms_hip_set_data_record", "roms_hip_set_data_point",
      "roms_hip_set_data", "roms_hip_set_data_factors", "roms_hip_get_clima",
-     "roms_hip_set_kpp", "roms_hip_get_kpp"] + ["roms_hip_" + e for e in ENTRIES])
+     "roms_hip_set_kpp", "roms_hip_get_kpp", "roms_hip_set_biology"] + ["roms_hip_" + e for e in ENTRIES])
 
 
 _DP = C.POINTER(C.c_double)
@@ -112,6 +112,10 @@ def load():
     lib.roms_hip_set_data_factors.argtypes = [C.c_double] * 4 + [C.c_int, C.c_int, _DP, _DP, _ip]
     lib.roms_hip_set_kpp.argtypes = [C.c_int, C.c_void_p]
     lib.roms_hip_get_kpp.argtypes = [C.c_char_p, C.c_void_p, C.c_long]
+    lib.roms_hip_set_biology.argtypes = [C.c_int, C.c_void_p, C.c_long]
+    if lib.roms_abi_sizeof(5) != C.sizeof(abi.BioPowell):
+        raise RuntimeError(f"ABI struct size mismatch: roms_bio_powell_t python={C.sizeof(abi.BioPowell)} "
+                           f"C={lib.roms_abi_sizeof(5)}")
     lib.roms_hip_set_halo_relay.argtypes = [RELAY_FN, C.c_void_p]
     if hasattr(lib, "roms_hip_tile_neighbors"):
         lib.roms_hip_tile_neighbors.argtypes = [C.c_int] * 7 + [C.POINTER(C.c_int)]
@@ -288,6 +292,22 @@ class RomsHip:
         out = np.zeros((self.st.ni, self.st.nj), dtype=KPP_ARRAYS[name], order="F")
         self._chk(self.l.roms_hip_get_kpp(name.encode(), out.ctypes.data, out.size), "get_kpp " + name)
         return out
+
+    def set_biology(self, model="NPZD_POWELL", par=None):
+        """BIOLOGY -> roms_hip_set_biology.  model: a name of abi.BIO_MODEL or its code, None / "NONE" drops the
+        setting; par: a bio.PowellPar (or an abi.BioPowell), None = the values of npzd_Powell.in with the tracers
+        NAT+1 .. NAT+4.  A refused call leaves the setting in force."""
+        from . import bio as _bio
+        code = 0 if model is None else abi.BIO_MODEL[model] if isinstance(model, str) else int(model)
+        if code == 0:
+            self._chk(self.l.roms_hip_set_biology(0, None, 0), "set_biology")
+            self.biology = None
+            return
+        if par is None:
+            par = _bio.PowellPar()
+        blk = par.c_struct(self.st.b) if hasattr(par, "c_struct") else par
+        self._chk(self.l.roms_hip_set_biology(code, C.byref(blk), C.sizeof(blk)), "set_biology")
+        self.biology = par
 
     def set_floats(self, floats):
         """DRIFTER(ng) (roms_trunk_mgh_amd/floats.py) -> roms_hip_set_floats; None releases the floats (Nfloats = 0)."""

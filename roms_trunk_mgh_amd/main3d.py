@@ -26,6 +26,7 @@ against either backend (`hip.RomsHip` = the product, or the CPU oracle in tests)
     main3d.F:762      step3d_uv
     main3d.F:789      omega
     main3d.F:793      gls_corstep                      (GLS_MIXING applications)
+    main3d.F:795-797  biology                          (BIOLOGY applications: biology=...)
     main3d.F:814      step3d_t
     main3d.F:894-903  step_floats, rotation of nfm3 ... nfp1   (FLOATS: floats=...)
     main3d.F:914      iic += 1
@@ -49,7 +50,7 @@ def host_clock(tdays):
 
 class Main3D:
     def __init__(self, backend, ntstart=1, physics=False, diagnostics=False, ninfo=1, averages=None, floats=None, tides=None,
-                 diags=None, data=None, bkpp=False, hbbl=None):
+                 diags=None, data=None, bkpp=False, hbbl=None, biology=None):
         """physics=True also runs the per-step physics that is on the device:
         bulk_flux and lmd_vmix (BULK_FLUXES / LMD_MIXING applications, i.e. BENCHMARK) and set_vbc, in
         the reference's order;
@@ -75,7 +76,9 @@ class Main3D:
         before ini_fields, ana_srflux / bulk_flux / set_vbc and tides, and keeps the flag it returns in `last_synchro`
         (set_2dfld.F:139-141: a new record is due before the next step).  With None the sequence is unchanged.
         bkpp=True (LMD_BKPP applications): set_kpp is issued here, once, with hbbl (the depth of a restart file; None =
-        zero, mod_mixing.F); the per-step call stays lmd_vmix, as the reference's lmd_vmix(ng, tile) is one call."""
+        zero, mod_mixing.F); the per-step call stays lmd_vmix, as the reference's lmd_vmix(ng, tile) is one call.
+        biology: a bio.PowellPar (BIOLOGY applications with NPZD_POWELL): set_biology is issued here, once, and every step
+        issues biology between gls_corstep and step3d_t (main3d.F:795-797).  With None the sequence is unchanged."""
         self.be = backend
         self.data = data
         self.last_synchro = 0
@@ -96,6 +99,9 @@ class Main3D:
         self.bkpp = bool(bkpp)
         if bkpp:
             backend.set_kpp(True, hbbl)
+        self.biology = biology
+        if biology is not None:
+            backend.set_biology(biology.model, biology)
         self.physics = physics
         self.diagnostics = diagnostics
         self.ninfo = ninfo
@@ -170,6 +176,8 @@ class Main3D:
         be.call("omega", s)
         if gls:                               # main3d.F:790-793
             be.call("gls_corstep", s)
+        if self.biology is not None:          # main3d.F:795-797
+            be.call("biology", s)
         be.call("step3d_t", s)
         if self.floats is not None:
             be.step_floats(s, (self.iic - self.ntstart) * be.st.p.dt, self.floats.nfl())
