@@ -10,9 +10,9 @@
 //                The coupling of the same column (:997-1460: ubar,vbar(:,:,1:2)
 //                and the corrected mass fluxes Huon,Hvom with DU_avg2/DV_avg2)
 //                needs nothing but the column's own final velocity, so it is
-//                done in the same thread from the registers that hold it: the
-//                Thomas arrays are dead by then and keep the layer factors and
-//                the intermediate fluxes.
+//                done in the same thread.  The Thomas coefficients are kept at
+//                every UV_SEG-th row only and the back substitution re-runs a
+//                segment from its checkpoint; the registers hold loads in flight.
 //   k_uv_couple  the columns the first kernel does not step -- boundary rows
 //                (after u3dbc/v3dbc) with their mean correction (:1087-1110) --
 //                one thread per column over IstrT:IendT, JstrT:JendT.
@@ -23,6 +23,15 @@
 int roms_entry_check(const char *name);
 
 namespace {
+
+// uv_column: rows per segment of the Thomas re-run, and levels the first sweep requests ahead
+// (tests/test_gpu_uv_segments.py restates both)
+#ifndef UV_SEG
+#define UV_SEG 5
+#endif
+#ifndef UV_AHEAD
+#define UV_AHEAD 4
+#endif
 
 // One momentum column.  off = 1 (u: neighbour i-1) or ni (v: neighbour j-1).
 template <int NMAX>
@@ -36,67 +45,154 @@ __device__ __forceinline__ void uv_column(const RomsDev *__restrict__ c, long c0
   // Hz(k) of the neighbour, the one input all four sweeps need: the sweeps after the first read Hz no more (15 -> 9
   // loads per level; the mean and the final sweep have no load to wait for at all)
   constexpr int UN_S = BLK_X * BLK_Y;
+  constexpr int S = UV_SEG, D = UV_AHEAD;
+  constexpr int MS = (NMAX - 1 + S - 1) / S;                // segments of the rows 1..NMAX-1 of the tridiagonal system
   const gcd_t Akv = (gcd_t)(c->F.Akv);
   const gcd_t Hz = (gcd_t)(c->F.Hz);
   const double dt = c->p.dt;
-  double hs[NMAX + 1], CF[NMAX + 1], DC[NMAX + 1];
-  CF[0] = 0.0;
-  DC[0] = 0.0;
+  const double c6 = 1.0 / 6.0, c3 = 1.0 / 3.0;
+  // hs[] is the one level array in registers.  The Thomas coefficients CF(j), DC(j) of row j (levels j, j+1) are not
+  // kept: the forward sweep keeps them at the rows 0, S, 2S, ... only (ckCF, ckDC), and the back substitution re-runs
+  // the rows of a segment from its checkpoint -- the same operations on the same operands, so the same bits.  The
+  // registers this frees hold loads in flight: D levels of the six inputs in the first sweep, a segment's Akv pairs
+  // in the second, the whole Hflx column in the coupling.
+  double hs[NMAX + 1], ckCF[MS], ckDC[MS];
+  ckCF[0] = 0.0;
+  ckDC[0] = 0.0;
   double hzk_m1 = 0.0, ohz_m1 = 0.0, ak_m2 = 0.0;
   double ak_m1 = 0.5 * (Akv[c0 - off] + Akv[c0]);           // AK(0)
-  double sumH = 0.0, un_prev = 0.0;
-  // the six inputs of level k+1 are requested before level k is computed (the kernel waits for memory on 85 % of its
-  // wave-cycles otherwise: a level's loads sit behind the `k <= N` test of its own block)
-  double n_aA = Akv[c0 + nij - off], n_aB = Akv[c0 + nij], n_hA = Hz[c0 - off], n_hB = Hz[c0], n_v = vel[c0], n_r = rhs[c0 + nij];
+  double sumH = 0.0, un_prev = 0.0, cf_prev = 0.0, dc_prev = 0.0;
+  // the six inputs of the levels k+1 .. k+D are requested before level k is computed; slot (k-1) % D holds level k.
+  // The level is clamped to N and the load is not branched around (a clamped one is loaded and not used): the
+  // number of loads in flight is then the same on every path and the wait for level k leaves the younger ones alone
+  double pA[D], pB[D], pHa[D], pHb[D], pV[D], pR[D];
+#pragma unroll
+  for (int t = 0; t < D; t++) {
+    const long cn = c0 + (long)(min(1 + t, N) - 1) * nij;
+    pA[t] = Akv[cn + nij - off]; pB[t] = Akv[cn + nij]; pHa[t] = Hz[cn - off]; pHb[t] = Hz[cn]; pV[t] = vel[cn]; pR[t] = rhs[cn + nij];
+  }
+  // A slot is used up and requested again outside the `k <= N` test of its level (above N: the clamped level, for
+  // nothing): no load is then in flight on one side of a join only -- where one is, the compiler copies the loaded
+  // registers at the end of the block, or counts the loads of the skipped blocks as missing, and waits for all of them.
 #pragma unroll
   for (int k = 1; k <= NMAX; k++) {
+    const int sl = (k - 1) % D;
+    const double ak_0 = 0.5 * (pA[sl] + pB[sl]);   // AK(k)
+    const double hsk = pHa[sl] + pHb[sl];
+    double uv = pV[sl];
+    uv = uv + dc0 * pR[sl];
+    if (k + D <= NMAX) {
+      const long cn = c0 + (long)(min(k + D, N) - 1) * nij;
+      pA[sl] = Akv[cn + nij - off]; pB[sl] = Akv[cn + nij]; pHa[sl] = Hz[cn - off]; pHb[sl] = Hz[cn]; pV[sl] = vel[cn]; pR[sl] = rhs[cn + nij];
+    }
     if (k <= N) {
-      const double aA = n_aA, aB = n_aB, hA = n_hA, hB = n_hB, v0 = n_v, r0 = n_r;
-      if (k + 1 <= N) {
-        const long cn = c0 + (long)k * nij;
-        n_aA = Akv[cn + nij - off]; n_aB = Akv[cn + nij]; n_hA = Hz[cn - off]; n_hB = Hz[cn]; n_v = vel[cn]; n_r = rhs[cn + nij];
-      }
-      const double ak_0 = 0.5 * (aA + aB);   // AK(k)
-      hs[k] = hA + hB;
+      hs[k] = hsk;
       const double hzk = 0.5 * hs[k];
       const double ohz = 1.0 / hzk;
-      double uv = v0;
-      uv = uv + dc0 * r0;
       uv = uv * ohz;
       un[k * UN_S] = uv;
       const double un_k = uv;
-      if (k >= 2) {
-        const double c6 = 1.0 / 6.0, c3 = 1.0 / 3.0;
+      if (k >= 2) {                                             // row k-1
         const double fc = c6 * hzk_m1 - dt * ak_m2 * ohz_m1;
         const double cf = c6 * hzk - dt * ak_0 * ohz;
         const double bc = c3 * (hzk_m1 + hzk) + dt * ak_m1 * (ohz_m1 + ohz);
-        const double cff = 1.0 / (bc - fc * CF[k - 2]);
-        CF[k - 1] = cff * cf;
-        DC[k - 1] = cff * (un_k - un_prev - fc * DC[k - 2]);
+        const double cff = 1.0 / (bc - fc * cf_prev);
+        cf_prev = cff * cf;
+        dc_prev = cff * (un_k - un_prev - fc * dc_prev);
+        if ((k - 1) % S == 0 && (k - 1) / S < MS) {             // the state the segment (k-1)/S starts from
+          ckCF[(k - 1) / S < MS ? (k - 1) / S : 0] = cf_prev;
+          ckDC[(k - 1) / S < MS ? (k - 1) / S : 0] = dc_prev;
+        }
       }
       sumH = (k == 1) ? hzk : sumH + hzk;
       un_prev = un_k;
       hzk_m1 = hzk; ohz_m1 = ohz; ak_m2 = ak_m1; ak_m1 = ak_0;
     }
   }
-  // back substitution (descending) with the viscous update
+  // back substitution (descending) with the viscous update, segment by segment from the top.  Segment m holds the rows
+  // j0+1 .. j0+S (j0 = m S; the top one ends at row N-1) and reads AK(j0 .. j0+S+1), the levels j0+1 .. j0+S+1 of hs[]
+  // and of un[]; it writes the levels j0+2 .. j0+S+1 of un[] (the lowest also level 1), so the segment below it, which
+  // reads up to level j0+1, still finds the velocities the forward sweep left.  AK(j0), AK(j0+1) pass down to the next
+  // segment as its AK(j0'+S), AK(j0'+S+1): every Akv value is loaded once, as before.  The S pairs of the segment below
+  // are requested before this one is computed.  Every segment of NMAX runs, with its rows tested against N one by one
+  // and its W-levels clamped to N: a test around a whole segment would put the requests on one side of a join (above).
+  // akNa, akNb: the Akv pairs of AK(j0 .. j0+S-1) of the next segment to run (of the top one also j0+S, j0+S+1)
+  double akNa[S + 2], akNb[S + 2];
+#pragma unroll
+  for (int t = 0; t < S + 2; t++) {
+    const long cw = c0 + (long)min((MS - 1) * S + t, N) * nij;
+    akNa[t] = Akv[cw - off]; akNb[t] = Akv[cw];
+  }
+  double akc0 = 0.5 * (akNa[S] + akNb[S]), akc1 = 0.5 * (akNa[S + 1] + akNb[S + 1]);
   double dcA_up = 0.0, dc_up = 0.0;
 #pragma unroll
-  for (int kk = NMAX - 1; kk >= 0; kk--) {
-    if (kk <= N - 1) {
-      double dcA = 0.0;
-      if (kk >= 1) {
-        const double dc = DC[kk] - CF[kk] * dc_up;
-        dc_up = dc;
-        const double ak = 0.5 * (Akv[c0 + (long)kk * nij - off] + Akv[c0 + (long)kk * nij]);
-        dcA = dc * ak;
+  for (int m = MS - 1; m >= 0; m--) {
+    {
+      const int j0 = m * S;
+      double ak[S + 2];                                         // ak[t] = AK(j0 + t)
+#pragma unroll
+      for (int t = 0; t < S; t++) ak[t] = 0.5 * (akNa[t] + akNb[t]);
+      ak[S] = akc0; ak[S + 1] = akc1;
+      akc0 = ak[0]; akc1 = ak[1];
+      if (m >= 1) {
+#pragma unroll
+        for (int t = 0; t < S; t++) {
+          const long cw = c0 + (long)min(j0 - S + t, N) * nij;
+          akNa[t] = Akv[cw - off]; akNb[t] = Akv[cw];
+        }
       }
-      const double hzk = 0.5 * hs[kk + 1];           // level kk+1
-      const double ohz = 1.0 / hzk;
-      un[(kk + 1) * UN_S] = un[(kk + 1) * UN_S] + dt * ohz * (dcA_up - dcA);
-      dcA_up = dcA;
+      double oh[S + 1], uu[S + 1];                              // 1 / Hz and the velocity of the levels j0+1 .. j0+S+1
+#pragma unroll
+      for (int t = 0; t <= S; t++) {
+        const int lev = j0 + 1 + t;
+        oh[t] = 0.0; uu[t] = 0.0;
+        if (lev <= NMAX && lev <= N) {
+          oh[t] = 1.0 / (0.5 * hs[lev <= NMAX ? lev : NMAX]);
+          uu[t] = un[(lev <= NMAX ? lev : NMAX) * UN_S];
+        }
+      }
+      // the rows of the segment again, from its checkpoint
+      double cfS[S], dcS[S];
+      double cfp = ckCF[m], dcp = ckDC[m];
+#pragma unroll
+      for (int t = 0; t < S; t++) {
+        const int j = j0 + 1 + t;                               // row j: levels j and j+1
+        cfS[t] = 0.0; dcS[t] = 0.0;
+        if (j + 1 <= NMAX && j <= N - 1) {
+          const double hzk_lo = 0.5 * hs[j <= NMAX ? j : NMAX];
+          const double hzk = 0.5 * hs[j + 1 <= NMAX ? j + 1 : NMAX];
+          const double fc = c6 * hzk_lo - dt * ak[t] * oh[t];
+          const double cf = c6 * hzk - dt * ak[t + 2] * oh[t + 1];
+          const double bc = c3 * (hzk_lo + hzk) + dt * ak[t + 1] * (oh[t] + oh[t + 1]);
+          const double cff = 1.0 / (bc - fc * cfp);
+          cfp = cff * cf;
+          dcp = cff * (uu[t + 1] - uu[t] - fc * dcp);
+          cfS[t] = cfp; dcS[t] = dcp;
+        }
+      }
+      // and their back substitution: row kk updates level kk+1
+#pragma unroll
+      for (int t = S - 1; t >= 0; t--) {
+        const int kk = j0 + 1 + t;
+        if (kk + 1 <= NMAX && kk <= N - 1) {
+          const double dc = dcS[t] - cfS[t] * dc_up;
+          dc_up = dc;
+          const double dcA = dc * ak[t + 1];
+          un[(kk + 1 <= NMAX ? kk + 1 : NMAX) * UN_S] = uu[t + 1] + dt * oh[t + 1] * (dcA_up - dcA);
+          dcA_up = dcA;
+        }
+      }
+      if (m == 0) {                                             // level 1 has no row below it
+        const double dcA = 0.0;
+        un[UN_S] = uu[0] + dt * oh[0] * (dcA_up - dcA);
+        dcA_up = dcA;
+      }
     }
   }
+  // the column of Hflx the coupling reads is requested here, ahead of the two sweeps that need no load (level clamped)
+  double hf[NMAX + 1];
+#pragma unroll
+  for (int k = 1; k <= NMAX; k++) hf[k] = Hflx[c0 + (long)(min(k, N) - 1) * nij];
   // vertical mean replacement, step3d_uv.F:466-520 (sums ascend in k)
   double sumU = 0.0;
 #pragma unroll
@@ -108,8 +204,8 @@ __device__ __forceinline__ void uv_column(const RomsDev *__restrict__ c, long c0
   }
   const double cff1 = 1.0 / (sumH * metric);
   const double corr = (sumU * metric - Davg1) * cff1;
-  // final velocity; then the coupling of this column (couple_column below, fix_mean = false) from registers:
-  // CF[] now holds DC(i,k) of step3d_uv.F:1010, DC[] the intermediate flux
+  // final velocity; then the coupling of this column (couple_column below, fix_mean = false): DC(i,k) of
+  // step3d_uv.F:1010 is cffm * hs[k] wherever it is used (the same product), hf[] becomes the intermediate flux
   const double cffm = 0.5 * metric;
   double DC0 = 0.0;
 #pragma unroll
@@ -122,7 +218,6 @@ __device__ __forceinline__ void uv_column(const RomsDev *__restrict__ c, long c0
       vel[ck] = uv;
       un[k * UN_S] = uv;
       const double dck = cffm * hs[k];
-      CF[k] = dck;
       DC0 = DC0 + dck;
     }
   }
@@ -135,15 +230,15 @@ __device__ __forceinline__ void uv_column(const RomsDev *__restrict__ c, long c0
 #pragma unroll
   for (int k = NMAX; k >= 1; k--) {
     if (k <= N) {
-      const double h = 0.5 * (Hflx[c0 + (long)(k - 1) * nij] + un[k * UN_S] * CF[k]);
-      DC[k] = h;
+      const double h = 0.5 * (hf[k] + un[k * UN_S] * (cffm * hs[k]));
+      hf[k] = h;
       FC0 = FC0 + h;
     }
   }
   FC0 = DC0 * (FC0 - Davg2);
 #pragma unroll
   for (int k = 1; k <= NMAX; k++)
-    if (k <= N) Hflx[c0 + (long)(k - 1) * nij] = DC[k] - CF[k] * FC0;
+    if (k <= N) Hflx[c0 + (long)(k - 1) * nij] = hf[k] - (cffm * hs[k]) * FC0;
 }
 
 template <int NMAX>
