@@ -28,7 +28,10 @@
 #                                 UPWELLING_MASK_WET[_DIF4|_ISO|_PG31], BENCHMARK_MASK_WET (+ -DWET_DRY; PJ_GRADP with WET_DRY does not
 #                                 compile in the reference itself: prsgrd40.h:98-100 passes umask_wet, vmask_wet without declaring them);
 #                                 UPWELLING_STAB_DIF4, SEAMOUNT_STAB_DIF4, UPWELLING_STAB_ISO, SEAMOUNT_STAB_ISO (+ -DTS_MIX_STABILITY);
-#                                 UPWELLING_MINSTRAT_ISO, SEAMOUNT_MINSTRAT_ISO (+ -DTS_MIX_MIN_STRAT)
+#                                 UPWELLING_MINSTRAT_ISO, SEAMOUNT_MINSTRAT_ISO (+ -DTS_MIX_MIN_STRAT);
+#                                 UPWELLING_BIO, UPWELLING_BIO_CPAR (+ NPZD_POWELL, and CONST_PAR: mod_biology.F, biology.F with
+#                                 npzd_Powell.h, behind ref_biology); BENCHMARK_BKPP, BENCHMARK_MASK_BKPP (+ LMD_BKPP: lmd_bkpp.F
+#                                 inside the reference's own lmd_vmix)
 #
 # This is the reference's own recipe (makefile:207, Compilers/Linux-gfortran.mk:
 # 43-44: cpp -P -traditional then the Fortran compiler), serial build (no
@@ -83,6 +86,19 @@ build_app () {
   case $TAG in *_MINSTRAT*) XDEF="$XDEF -DTS_MIX_MIN_STRAT";; esac
   case $TAG in *_LIMBS) XDEF="$XDEF -DLIMIT_BSTRESS";; esac
   case $TAG in *_EMP) XDEF="$XDEF -DEMINUSP";; esac              # BENCHMARK[_MASK]_EMP: + EMINUSP (bulk_flux.F:883-899)      # <APP>_LIMBS: + LIMIT_BSTRESS (set_vbc.F:533-567)
+  # UPWELLING_BIO[_CPAR]: the application plus NPZD_POWELL (globaldefs.h derives BIOLOGY from it) and what upwelling.h:51-57
+  # adds for an ecosystem model (ANA_BIOLOGY, ANA_SPFLUX, ANA_BPFLUX, ANA_SRFLUX); _CPAR: plus CONST_PAR (npzd_Powell.h:269-274).
+  # Modules/mod_biology (needs mod_param alone; mod_ncparam, mod_forces and mod_diags USE it) and Nonlinear/Biology/biology
+  # join the list; the wrapper binds ref_biology and calls initialize_biology before initialize_param (NBT = 4)
+  local files="$FILES" INC=""
+  case $TAG in *_BIO*) XDEF="$XDEF -DNPZD_POWELL -DANA_BIOLOGY -DANA_SPFLUX -DANA_BPFLUX -DANA_SRFLUX"; WDEF="-DREF_BIO"
+                       INC="-I$REF/ROMS/Nonlinear/Biology"
+                       files="${files/Modules\/mod_param/Modules/mod_param Modules/mod_biology} Nonlinear/Biology/biology";; esac
+  case $TAG in *_BIO_CPAR) XDEF="$XDEF -DCONST_PAR";; esac
+  # BENCHMARK[_MASK]_BKPP: the application plus LMD_BKPP: lmd_bkpp.F, which lmd_vmix(ng, tile) calls between lmd_skpp and
+  # lmd_finish; the wrapper binds h and the doorway for hbbl, kbbl, ksbl
+  case $TAG in *_BKPP) XDEF="$XDEF -DLMD_BKPP"; WDEF="-DREF_BKPP"
+                       files="${files/Nonlinear\/lmd_vmix/Nonlinear/lmd_bkpp Nonlinear/lmd_vmix}";; esac
   case $TAG in *_PG31) VAR=pg31;; *_WJ) VAR=wj;; *_PJ) VAR=pj;; *_DIF4) VAR=dif4; WDEF="-DREF_DIF4";; *_ISO) VAR=iso; WDEF="-DREF_DIF4";; *_LOGDRAG) VAR=logdrag; WDEF="-DREF_LOGDRAG";; *_GLS) VAR=gls; WDEF="-DREF_GLS";; *_MY25) VAR=my25; WDEF="-DREF_GLS -DREF_MY25";; *_GEOUV) VAR=geouv; WDEF="-DREF_GEOUV";; esac
   # <APP>[_MASK[_WET]]_GEOUV4: the _GEOUV options plus TS_DIF4 and UV_VIS4 on the command line, so that uv3dmix.F includes
   # uv3dmix4_geo.h as well (the biharmonic viscosity rotated to geopotential surfaces); the wrapper binds uv3dmix4
@@ -106,9 +122,9 @@ build_app () {
      '-DMY_OS="Linux"' '-DMY_CPU="x86_64"' '-DMY_FORT="flang"' '-DMY_FC="flang"' '-DMY_FFLAGS="-O2"'
      '-DSVN_URL="x"' '-DSVN_REV="x"' '-DANALYTICAL_DIR="x"' '-DHEADER_DIR="x"' "-DHEADER=\"$hdr\""
      '-DMY_ANALYTICAL_DIR="x"' '-DMY_HEADER_DIR="x"' "-DMY_HEADER=\"$hdr\"" '-DMY_ROOT_DIR="x"' '-DMY_ANALYTICAL="x"'
-     -I$HERE/ref_headers -I$REF/ROMS/Include -I$REF/ROMS/Functionals -I$REF/ROMS/Nonlinear -I$REF/ROMS/Utility -I$REF/ROMS/Modules)
+     -I$HERE/ref_headers $INC -I$REF/ROMS/Include -I$REF/ROMS/Functionals -I$REF/ROMS/Nonlinear -I$REF/ROMS/Utility -I$REF/ROMS/Modules)
   local objs=""
-  for f in $FILES; do
+  for f in $files; do
     local bn=$(basename $f)
     # the MASKING variants leave analytical.F out: its ana_mask.h stops the compilation on purpose until a user
     # fills in mask values ("no values provided for mask"); the masks reach GRID(ng) through the wrapper
@@ -124,7 +140,7 @@ build_app () {
   echo "[$TAG] built $D/libref.so"
 }
 
-for app in ${APPS:-BENCHMARK UPWELLING SEAMOUNT BENCHMARK_MASK UPWELLING_MASK UPWELLING_PG31 UPWELLING_WJ SEAMOUNT_PG31 SEAMOUNT_WJ UPWELLING_DIF4 SEAMOUNT_DIF4 UPWELLING_MASK_DIF4 UPWELLING_ISO SEAMOUNT_ISO UPWELLING_MASK_ISO UPWELLING_LOGDRAG UPWELLING_PJ SEAMOUNT_PJ UPWELLING_RAD2D UPWELLING_MASK_RAD2D BENCHMARK_RAD2D UPWELLING_LIMBS BENCHMARK_LIMBS BENCHMARK_EMP BENCHMARK_MASK_EMP UPWELLING_GLS UPWELLING_MASK_GLS BENCHMARK_GLS UPWELLING_MY25 UPWELLING_MASK_MY25 BENCHMARK_MY25 UPWELLING_GEOUV SEAMOUNT_GEOUV UPWELLING_MASK_GEOUV UPWELLING_MASK_WET_GEOUV UPWELLING_GEOUV4 SEAMOUNT_GEOUV4 UPWELLING_MASK_GEOUV4 UPWELLING_MASK_WET_GEOUV4 UPWELLING_MASK_WET BENCHMARK_MASK_WET UPWELLING_MASK_WET_DIF4 UPWELLING_MASK_WET_ISO UPWELLING_MASK_WET_PG31 UPWELLING_ATM UPWELLING_ATM_PG31 UPWELLING_ATM_PJ UPWELLING_ATM_PC UPWELLING_STAB_DIF4 SEAMOUNT_STAB_DIF4 UPWELLING_STAB_ISO SEAMOUNT_STAB_ISO UPWELLING_MINSTRAT_ISO SEAMOUNT_MINSTRAT_ISO}; do
+for app in ${APPS:-BENCHMARK UPWELLING SEAMOUNT BENCHMARK_MASK UPWELLING_MASK UPWELLING_PG31 UPWELLING_WJ SEAMOUNT_PG31 SEAMOUNT_WJ UPWELLING_DIF4 SEAMOUNT_DIF4 UPWELLING_MASK_DIF4 UPWELLING_ISO SEAMOUNT_ISO UPWELLING_MASK_ISO UPWELLING_LOGDRAG UPWELLING_PJ SEAMOUNT_PJ UPWELLING_RAD2D UPWELLING_MASK_RAD2D BENCHMARK_RAD2D UPWELLING_LIMBS BENCHMARK_LIMBS BENCHMARK_EMP BENCHMARK_MASK_EMP UPWELLING_GLS UPWELLING_MASK_GLS BENCHMARK_GLS UPWELLING_MY25 UPWELLING_MASK_MY25 BENCHMARK_MY25 UPWELLING_GEOUV SEAMOUNT_GEOUV UPWELLING_MASK_GEOUV UPWELLING_MASK_WET_GEOUV UPWELLING_GEOUV4 SEAMOUNT_GEOUV4 UPWELLING_MASK_GEOUV4 UPWELLING_MASK_WET_GEOUV4 UPWELLING_MASK_WET BENCHMARK_MASK_WET UPWELLING_MASK_WET_DIF4 UPWELLING_MASK_WET_ISO UPWELLING_MASK_WET_PG31 UPWELLING_ATM UPWELLING_ATM_PG31 UPWELLING_ATM_PJ UPWELLING_ATM_PC UPWELLING_STAB_DIF4 SEAMOUNT_STAB_DIF4 UPWELLING_STAB_ISO SEAMOUNT_STAB_ISO UPWELLING_MINSTRAT_ISO SEAMOUNT_MINSTRAT_ISO UPWELLING_BIO UPWELLING_BIO_CPAR BENCHMARK_BKPP BENCHMARK_MASK_BKPP}; do
   build_app $app &
 done
 wait

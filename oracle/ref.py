@@ -21,7 +21,9 @@ def available(app):
 
 
 class Ref:
-    def __init__(self, state):
+    def __init__(self, state, build=None):
+        """build: the tag of the build to load where the state's switches do not name it -- UPWELLING_BIO[_CPAR]
+        (biology reads no switch of the state) and BENCHMARK[_MASK]_BKPP (LMD_BKPP is no member of roms_params_t)"""
         if state.p.uv_vis4 == 2 and state.p.uv_vis2 != 2:
             # MIX_GEO_UV is one CPP switch for both operators: no build has uv3dmix4_geo.h beside uv3dmix2_s.h or
             # without UV_VIS2, and a _DIF4 build would run uv3dmix4_s.h in its place
@@ -60,6 +62,10 @@ class Ref:
             app += "_MY25"                                                 # MY25_MIXING builds (ref_headers/*_my25.h)
         elif state.p.gls_mixing:
             app += "_GLS"                                                  # GLS_MIXING builds (ref_headers/*_gls.h)
+        if build is not None:
+            if "_MASK" in build and not state.p.masking:
+                raise RuntimeError(f"{build} is built with MASKING, the state is not masked")
+            app = build
         self.l = C.CDLL(lib_path(app))
         self.st = state
         self.l.ref_abi_sizeof.argtypes = [C.c_int]
@@ -130,6 +136,32 @@ class Ref:
         rc = self.l.ref_physics(kid, C.byref(self.st.b), C.byref(self.st.p), C.byref(s), C.byref(self.F))
         if rc != 0:
             raise RuntimeError(f"ref_physics {kernel} rc={rc}")
+
+    def kpp_layers(self, hbbl=None):
+        """LMD_BKPP builds: hbbl, kbbl, ksbl of MIXING(ng) (ref_kpp_layers in ref_wrap.F90).  hbbl given: it is handed
+        to the reference (the depth of the previous step, lmd_bkpp.F:243); otherwise the three arrays are returned as
+        physics("lmd_vmix") left them."""
+        import numpy as np
+        self.l.ref_kpp_layers.argtypes = [C.c_int, C.POINTER(abi.Bounds), C.c_void_p, C.c_void_p, C.c_void_p]
+        shape = (self.st.ni, self.st.nj)
+        h = np.zeros(shape, order="F") if hbbl is None else np.asfortranarray(hbbl, dtype=np.float64).copy(order="F")
+        assert h.shape == shape
+        kb, ks = np.zeros(shape, dtype=np.int32, order="F"), np.zeros(shape, dtype=np.int32, order="F")
+        rc = self.l.ref_kpp_layers(0 if hbbl is not None else 1, C.byref(self.st.b), h.ctypes.data, kb.ctypes.data, ks.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"ref_kpp_layers rc={rc}")
+        return None if hbbl is not None else dict(hbbl=h, kbbl=kb, ksbl=ks)
+
+    def biology(self, par, s):
+        """biology(ng, tile) of the BIOLOGY builds (NPZD_POWELL) with the parameters of a bio.PowellPar (ref_biology)."""
+        blk = par.c_struct(self.st.b)
+        if self.l.ref_abi_sizeof(4) != C.sizeof(blk):
+            raise RuntimeError(f"ref ABI mismatch: roms_bio_powell_t python={C.sizeof(blk)} fortran={self.l.ref_abi_sizeof(4)}")
+        self.l.ref_biology.argtypes = [C.POINTER(abi.Bounds), C.POINTER(abi.Params), C.POINTER(abi.StepIdx),
+                                       C.POINTER(abi.Fields), C.POINTER(type(blk))]
+        rc = self.l.ref_biology(C.byref(self.st.b), C.byref(self.st.p), C.byref(s), C.byref(self.F), C.byref(blk))
+        if rc != 0:
+            raise RuntimeError(f"ref_biology rc={rc}")
 
     def gls(self, kernel, s):
         """gls_prestep / gls_corstep through the reference's own module procedures (GLS builds only: ref_gls)."""

@@ -82,6 +82,12 @@ MODULE ref_wrap_types
     TYPE(c_ptr) :: tke, gls, Lscale, Akk, Akp
     TYPE(c_ptr) :: pmask_wet, rmask_wet, umask_wet, vmask_wet, rmask_wet_avg, pmask_full, rmask_full, umask_full, vmask_full
   END TYPE fields_t
+  !  order of include/roms_bio.def (the image of bio.PowellPar)
+  TYPE, BIND(C) :: bio_powell_t
+    INTEGER(c_int) :: BioIter, const_par, idbio(4)
+    REAL(c_double) :: AttSW, AttPhy, PhyIS, Vm_NO3, PhyMRD, PhyMRN, K_NO3, Ivlev, ZooGR, ZooEED, ZooEEN, ZooMRD, ZooMRN
+    REAL(c_double) :: DetRR, wPhy, wDet, PARfrac, Cp
+  END TYPE bio_powell_t
   LOGICAL, SAVE :: have_boundary = .FALSE.      ! allocate_boundary is done once per process
 END MODULE ref_wrap_types
 
@@ -94,11 +100,13 @@ FUNCTION ref_abi_sizeof (which) BIND(C, name='ref_abi_sizeof') RESULT(n)
   TYPE(params_t) :: p
   TYPE(stepidx_t) :: s
   TYPE(fields_t) :: f
+  TYPE(bio_powell_t) :: q
   n = -1
   IF (which == 0) n = INT(c_sizeof(b), c_int)
   IF (which == 1) n = INT(c_sizeof(p), c_int)
   IF (which == 2) n = INT(c_sizeof(s), c_int)
   IF (which == 3) n = INT(c_sizeof(f), c_int)
+  IF (which == 4) n = INT(c_sizeof(q), c_int)
 END FUNCTION ref_abi_sizeof
 
 !-----------------------------------------------------------------------
@@ -115,6 +123,9 @@ FUNCTION ref_setup (b, p) BIND(C, name='ref_setup') RESULT(rc)
   USE mod_coupling, ONLY : allocate_coupling
   USE mod_mixing,   ONLY : allocate_mixing
   USE mod_forces,   ONLY : allocate_forces
+#ifdef REF_BIO
+  USE mod_biology,  ONLY : initialize_biology
+#endif
   TYPE(bounds_t), INTENT(in) :: b
   TYPE(params_t), INTENT(in) :: p
   INTEGER(c_int) :: rc
@@ -129,6 +140,9 @@ FUNCTION ref_setup (b, p) BIND(C, name='ref_setup') RESULT(rc)
   Lm(ng) = b%Lm;  Mm(ng) = b%Mm;  N(ng) = b%N
   NtileI(ng) = 1; NtileJ(ng) = 1
   NAT = b%NAT
+#ifdef REF_BIO
+  CALL initialize_biology              ! read_phypar.F does so before initialize_param: NBT = 4, idbio = NAT+1 .. NAT+4
+#endif
   CALL initialize_param
   CALL initialize_parallel
   CALL allocate_parallel (Ngrids)
@@ -543,6 +557,11 @@ FUNCTION ref_physics (kernel, b, p, s, F) BIND(C, name='ref_physics') RESULT(rc)
 # endif
   iic(ng) = s%iic; ntstart(ng) = s%ntfirst
   CALL c_f_pointer (F%f, a2, (/ni,nj/));        GRID(ng)%f = a2
+# ifdef REF_BKPP
+  !  lmd_bkpp_tile reads, beyond what lmd_vmix_tile and lmd_skpp_tile do, h (the Ekman limit, lmd_bkpp.F:528-536), btflx,
+  !  bustr, bvstr (bound above) and hbbl of the previous step; hbbl, kbbl, ksbl travel through ref_kpp_layers
+  CALL c_f_pointer (F%h, a2, (/ni,nj/));        GRID(ng)%h = a2
+# endif
   CALL c_f_pointer (F%pden, a3, (/ni,nj,NN/));  OCEAN(ng)%pden = a3
   CALL c_f_pointer (F%bvf, a3, (/ni,nj,NN+1/)); MIXING(ng)%bvf = a3
   CALL c_f_pointer (F%Akv, a3, (/ni,nj,NN+1/)); MIXING(ng)%Akv = a3
@@ -1257,4 +1276,99 @@ FUNCTION ref_gls (kernel, b, p, s, F) BIND(C, name='ref_gls') RESULT(rc)
 # endif
   CALL c_f_pointer (F%Lscale, a3, (/ni,nj,NN+1/)); a3 = MIXING(ng)%Lscale
 END FUNCTION ref_gls
+#endif
+
+!-----------------------------------------------------------------------
+!  LMD_BKPP builds: hbbl, kbbl and ksbl of MIXING(ng) are no members of roms_fields_t.  dir = 0: hbbl in (the depth
+!  of the previous step, which lmd_bkpp_tile reads at lmd_bkpp.F:243); dir = 1: the three arrays out, as
+!  lmd_vmix(ng, tile) of ref_physics (kernel 3) left them.
+#ifdef REF_BKPP
+FUNCTION ref_kpp_layers (dir, b, hbbl, kbbl, ksbl) BIND(C, name='ref_kpp_layers') RESULT(rc)
+  USE ref_wrap_types
+  USE mod_param
+  USE mod_mixing
+  INTEGER(c_int), VALUE :: dir
+  TYPE(bounds_t), INTENT(in) :: b
+  REAL(c_double), INTENT(inout) :: hbbl(b%LBi:b%UBi, b%LBj:b%UBj)
+  INTEGER(c_int), INTENT(inout) :: kbbl(b%LBi:b%UBi, b%LBj:b%UBj), ksbl(b%LBi:b%UBi, b%LBj:b%UBj)
+  INTEGER(c_int) :: rc
+  INTEGER :: ng
+  ng = 1
+  rc = 0
+  IF (b%LBi /= BOUNDS(ng)%LBi(0) .OR. b%UBi /= BOUNDS(ng)%UBi(0) .OR. b%LBj /= BOUNDS(ng)%LBj(0) .OR. b%UBj /= BOUNDS(ng)%UBj(0)) THEN
+    rc = 1
+    RETURN
+  END IF
+  IF (dir == 0) THEN
+    MIXING(ng)%hbbl = hbbl
+  ELSE
+    hbbl = MIXING(ng)%hbbl
+    kbbl = MIXING(ng)%kbbl
+    ksbl = MIXING(ng)%ksbl
+  END IF
+END FUNCTION ref_kpp_layers
+#endif
+
+!-----------------------------------------------------------------------
+!  BIOLOGY builds (NPZD_POWELL): biology(ng, tile) of biology.F:35 with the parameters of mod_biology set from q (what
+!  npzd_Powell_inp.h reads from npzd_Powell.in), on Hz, z_r, z_w, srflx and t of F; t is handed back.  idbio is the
+!  reference's own (initialize_biology in ref_setup), Cp that of mod_scalars.F, CONST_PAR a CPP option of the build: a
+!  block that asks for anything else is refused (rc = 3).
+#ifdef REF_BIO
+FUNCTION ref_biology (b, p, s, F, q) BIND(C, name='ref_biology') RESULT(rc)
+  USE ref_wrap_types
+  USE mod_param
+  USE mod_scalars
+  USE mod_stepping
+  USE mod_grid
+  USE mod_ocean
+  USE mod_forces
+  USE mod_biology
+  USE biology_mod, ONLY : biology
+  TYPE(bounds_t), INTENT(in) :: b
+  TYPE(params_t), INTENT(in) :: p
+  TYPE(stepidx_t), INTENT(in) :: s
+  TYPE(fields_t), INTENT(in) :: F
+  TYPE(bio_powell_t), INTENT(in) :: q
+  INTEGER(c_int) :: rc
+  INTEGER :: ng, tile, LBi, UBi, LBj, UBj, ni, nj, NN, NTT, i
+  REAL(c_double), POINTER :: a2(:,:), a3(:,:,:), a5(:,:,:,:,:)
+  ng = 1; tile = 0
+  LBi = b%LBi; UBi = b%UBi; LBj = b%LBj; UBj = b%UBj
+  ni = UBi-LBi+1; nj = UBj-LBj+1; NN = b%N; NTT = b%NT
+  rc = 0
+  IF (LBi /= BOUNDS(ng)%LBi(0) .OR. UBi /= BOUNDS(ng)%UBi(0) .OR. LBj /= BOUNDS(ng)%LBj(0) .OR. UBj /= BOUNDS(ng)%UBj(0)) THEN
+    rc = 1
+    RETURN
+  END IF
+  IF (NBT /= 4 .OR. NT(ng) /= NTT .OR. N(ng) /= NN .OR. q%Cp /= Cp) rc = 3
+  DO i = 1, 4
+    IF (idbio(i) /= q%idbio(i)) rc = 3
+  END DO
+#ifdef CONST_PAR
+  IF (q%const_par /= 1) rc = 3
+#else
+  IF (q%const_par /= 0) rc = 3
+#endif
+  IF (rc /= 0) RETURN
+  nstp(ng) = s%nstp; nnew(ng) = s%nnew; nrhs(ng) = s%nrhs
+  dt(ng) = p%dt
+  rho0 = p%rho0
+  BioIter(ng) = q%BioIter
+  AttSW(ng) = q%AttSW;   AttPhy(ng) = q%AttPhy; PhyIS(ng) = q%PhyIS;   Vm_NO3(ng) = q%Vm_NO3
+  PhyMRD(ng) = q%PhyMRD; PhyMRN(ng) = q%PhyMRN; K_NO3(ng) = q%K_NO3;   Ivlev(ng) = q%Ivlev
+  ZooGR(ng) = q%ZooGR;   ZooEED(ng) = q%ZooEED; ZooEEN(ng) = q%ZooEEN; ZooMRD(ng) = q%ZooMRD
+  ZooMRN(ng) = q%ZooMRN; DetRR(ng) = q%DetRR;   wPhy(ng) = q%wPhy;     wDet(ng) = q%wDet
+  PARfrac(ng) = q%PARfrac
+#ifdef MASKING
+  CALL c_f_pointer (F%rmask, a2, (/ni,nj/));    GRID(ng)%rmask = a2
+#endif
+  CALL c_f_pointer (F%Hz, a3, (/ni,nj,NN/));    GRID(ng)%Hz = a3
+  CALL c_f_pointer (F%z_r, a3, (/ni,nj,NN/));   GRID(ng)%z_r = a3
+  CALL c_f_pointer (F%z_w, a3, (/ni,nj,NN+1/)); GRID(ng)%z_w = a3
+  CALL c_f_pointer (F%srflx, a2, (/ni,nj/));    FORCES(ng)%srflx = a2
+  CALL c_f_pointer (F%t, a5, (/ni,nj,NN,3,NTT/)); OCEAN(ng)%t = a5
+  CALL biology (ng, tile)
+  CALL c_f_pointer (F%t, a5, (/ni,nj,NN,3,NTT/)); a5 = OCEAN(ng)%t
+END FUNCTION ref_biology
 #endif

@@ -1,8 +1,10 @@
 """The yardstick of the NPZD_POWELL biology (roms_hip_biology): a vectorised numpy restatement of npzd_powell_tile,
 ROMS/Nonlinear/Biology/npzd_Powell.h:199-656, written from the Fortran text and not from the kernel, with the same
 operation order (one numpy operation per Fortran operation, on all columns at once; the loops over k that carry a
-dependence stay loops).  Parity status: UNPINNED -- no reference build with BIOLOGY exists under oracle/, so nothing
-here has been compared with the compiled reference; tests/test_bio.py pins the restatement to closed forms.
+dependence stay loops).  Parity status: pinned -- tests/test_ref_pinning.py compares it with
+the reference's own biology(ng, tile) (oracle/_ref/UPWELLING_BIO, UPWELLING_BIO_CPAR) on the states of bio_state within 1e-13
+of each pool's maximum (measured: 1e-16 and below), tests/test_golden.py with the vectors of tests/golden/ref_bio.npz;
+tests/test_bio.py pins it to closed forms as well.
 
     positive           :237-251, one time level
     light              :337-363

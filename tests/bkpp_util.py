@@ -8,6 +8,10 @@ LMD_SHAPIRO) -- loops over k, vectorised over i, j, the operation order of the r
     expected           what roms_hip_lmd_vmix with the switch on must give, from its result with the switch off
     bkpp_state         the states the GPU tests run, and PARITY_CASES, their table
 
+Parity status: pinned -- tests/test_ref_pinning.py compares `expected` with the reference's own lmd_vmix(ng, tile) built
+with LMD_BKPP (oracle/_ref/BENCHMARK_BKPP, BENCHMARK_MASK_BKPP) on every state of PARITY_CASES (kbbl, ksbl identical; hbbl,
+Akv, Akt within 1e-13 of each field's maximum), tests/test_golden.py with the vectors of tests/golden/ref_bkpp.npz.
+
 lmd_bkpp_tile also returns a branch census and the decision margins per column (tests/test_bkpp.py asserts both over
 PARITY_CASES, tests/test_gpu_bkpp.py compares the device with the restatement on the same cases)."""
 import math

@@ -507,6 +507,100 @@ def main_mpdata(config, mask=None, basin=None):
     print(json.dumps(out))
 
 
+def positivity_outcomes(v):
+    """the three outcomes of npzd_Powell.h:237-251 per cell of v[..., 4]: no pool below MinVal; a deficit the largest
+    pool covers (:249 true); a deficit it does not cover (nothing is deducted)"""
+    import bio_util as bu
+    lifted = np.maximum(bu.MINVAL, v)
+    deficit = np.maximum(0.0, bu.MINVAL - v).sum(axis=-1)
+    top = lifted.max(axis=-1)
+    return {"none": int((deficit == 0.0).sum()), "covered": int(((deficit > 0.0) & (top > deficit)).sum()),
+            "not_covered": int(((deficit > 0.0) & ~(top > deficit)).sum())}
+
+
+def main_bio(grid, mask, pset, path=None):
+    """biology(ng, tile) of the reference built with NPZD_POWELL (oracle/_ref/UPWELLING_BIO, with CONST_PAR:
+    UPWELLING_BIO_CPAR) vs the numpy restatement of tests/bio_util.py on one state of tests/test_gpu_bio.py.  The
+    reference never looks at rmask, so the island states run on the same builds.  path: the reference's t is written
+    there (tests/golden/make_golden_bio.py)."""
+    import bio_util as bu
+    import util
+    from oracle import ref
+    from roms_trunk_mgh_amd import bio
+    st = bu.bio_state(grid, mask)
+    par = bu.params(pset, st.p.dt)
+    s = util.step_idx()
+    b, N = st.b, st.b.N
+    info = {}
+    want = bu.expected(st, par, info=info)
+    st_r = st.copy()
+    ref.Ref(st_r, build="UPWELLING_BIO" + ("_CPAR" if par.const_par else "")).biology(par, s)
+    got = st_r["t"]
+    I = bu.interior(b)
+    idbio = par.tracers(b)
+    out = {"masking": int(st.p.masking), "N": int(N), "build_const_par": int(par.const_par), "pools": {}}
+    for q, itrc in enumerate(idbio):
+        g, w = got[I][:, :, :, s.nnew - 1, itrc - 1], want[I][:, :, :, s.nnew - 1, itrc - 1]
+        scale = float(np.abs(g).max())
+        out["pools"][bio.POOLS[q]] = {"diff": float(np.abs(g - w).max()), "max": scale, "rel": float(np.abs(g - w).max()) / scale,
+                                     "moved": float((g != st["t"][I][:, :, :, s.nnew - 1, itrc - 1]).mean())}
+    keep = np.ones(got.shape, dtype=bool)                 # everything but t(nnew) of the pools on Istr:Iend, Jstr:Jend
+    keep[I[0], I[1], :, s.nnew - 1, idbio[0] - 1:idbio[0] + 3] = False
+    out["rest_of_t_bits_equal"] = bool(np.array_equal(got[keep], st["t"][keep]))
+    out["other_fields_changed"] = sorted(n for n in util.compare_states(st_r, st) if n != "t")
+    cols = bu.columns(st, par)
+    out["day_columns"], out["night_columns"] = int((cols["srflx"] > 0.0).sum()), int((cols["srflx"] <= 0.0).sum())
+    out["positivity_nstp"] = positivity_outcomes(cols["tS"])
+    out["positivity_nnew"] = positivity_outcomes(cols["tN"] / cols["Hz"][..., None])
+    ks = info["ksource_SDet"] - np.arange(1, N + 1)
+    out["ksource_shifts"] = int(np.unique(ks).size)
+    out["ksource_reaches_N"] = bool((info["ksource_SDet"][..., 0] == N).any())
+    out["ksource_stays_below_N"] = bool((info["ksource_SDet"][..., 0] < N).any())
+    if path:
+        np.savez(path, t=got)
+    print(json.dumps(out))
+
+
+def main_bkpp(grid, mask, basin, unstable, path=None):
+    """lmd_vmix(ng, tile) of the reference built with LMD_BKPP (oracle/_ref/BENCHMARK[_MASK]_BKPP: lmd_vmix_tile,
+    lmd_skpp, lmd_bkpp, lmd_finish) vs the numpy restatement of tests/bkpp_util.py on one state of
+    tests/test_gpu_bkpp.py.  As in tests/test_bkpp.py the C oracle's lmd_vmix (pinned to the plain builds) gives the
+    restatement its input, the result with the switch off."""
+    import bkpp_util as bk
+    import oracle
+    import util
+    from oracle import ref
+    st, hprev = bk.bkpp_state(grid, mask, basin, unstable)
+    s = util.step_idx()
+    b, N = st.b, st.b.N
+    I, D = bk.interior(b), bk.defined_points(b)
+    sa = st.copy()
+    oracle.Oracle(sa).call("lmd_vmix", s)
+    r = bk.expected(st, sa["Akv"], sa["Akt"], sa["hsbl"], hprev)
+    st_r = st.copy()
+    R = ref.Ref(st_r, build="BENCHMARK" + ("_MASK" if mask else "") + "_BKPP")
+    R.kpp_layers(hprev)
+    R.physics("lmd_vmix", s)
+    L = R.kpp_layers()
+    out = {"masking": int(st.p.masking), "EWperiodic": int(b.EWperiodic), "N": int(N),
+           "kbbl_equal": bool(np.array_equal(L["kbbl"][I], r["kbbl"][I])), "ksbl_equal": bool(np.array_equal(L["ksbl"][I], r["ksbl"][I])),
+           "kbbl_max": int(L["kbbl"][I].max()), "fields": {}}
+    lev = slice(1, N)
+    pairs = {"hbbl": (L["hbbl"][D], r["hbbl"][D]), "Akv": (st_r["Akv"][I][:, :, lev], r["Akv"][:, :, lev]),
+             "Akt1": (st_r["Akt"][I][:, :, lev, 0], r["Akt"][:, :, lev, 0]), "Akt2": (st_r["Akt"][I][:, :, lev, 1], r["Akt"][:, :, lev, 1])}
+    for name, (g, w) in pairs.items():
+        scale = float(np.abs(g).max())
+        out["fields"][name] = {"diff": float(np.abs(g - w).max()), "max": scale, "rel": float(np.abs(g - w).max()) / scale}
+    # the surface layer's own outputs are those of the build without the bottom layer (the oracle, pinned to it)
+    out["surface_layer"] = {n: util.max_rel_diff(sa[n], st_r[n]) for n in ("hsbl", "ghats")}
+    out["changed_columns"] = float((st_r["Akv"][I] != sa["Akv"][I]).any(axis=2).mean())
+    out["census"] = {k: int(v.sum()) for k, v in r["census"].items()}
+    out["margins"] = {k: float(v.min()) for k, v in r["margins"].items()}
+    if path:
+        np.savez(path, hbbl=L["hbbl"], kbbl=L["kbbl"], ksbl=L["ksbl"], Akv=st_r["Akv"], Akt=st_r["Akt"])
+    print(json.dumps(out))
+
+
 def logdrag_state(config="UPWELLING"):
     """prepared_state with UV_LOGDRAG: a roughness length varying over two decades, so large in one corner that the drag
     coefficient runs into Cdb_max, so small in another that it runs into a raised Cdb_min."""
@@ -832,7 +926,12 @@ if __name__ == "__main__":
         sys.argv.pop()
     PC = len(sys.argv) > 3 and sys.argv[3] == "pc"            # ATM_PRESS + PRESS_COMPENSATE builds (bc, bc4 modes)
     RAD2D = len(sys.argv) > 3 and sys.argv[3] == "rad2d"      # the builds with -DRADIATION_2D (bc, bc4 modes)
-    if len(sys.argv) > 2 and sys.argv[2] == "ana":
+    if len(sys.argv) > 4 and sys.argv[1] == "bio":            # bio <grid> <plain|island> <parameter set> [file for t]
+        main_bio(sys.argv[2], None if sys.argv[3] == "plain" else sys.argv[3], sys.argv[4], *sys.argv[5:6])
+    elif len(sys.argv) > 5 and sys.argv[1] == "bkpp":         # bkpp <grid> <plain|island> <channel|basin> <stable|unstable> [file]
+        main_bkpp(sys.argv[2], None if sys.argv[3] == "plain" else sys.argv[3], sys.argv[4] == "basin", sys.argv[5] == "unstable",
+                  *sys.argv[6:7])
+    elif len(sys.argv) > 2 and sys.argv[2] == "ana":
         main_ana(sys.argv[1])
     elif len(sys.argv) > 2 and sys.argv[2] in ("gls", "gls_mask", "gls_basin"):
         main_gls(sys.argv[1], mask="island" if sys.argv[2] == "gls_mask" else None, basin=sys.argv[2] == "gls_basin")

@@ -2,7 +2,8 @@
 forms -- conservation and the one-line formulas of the reaction sweeps, the analytic cell average of the light, sinking
 of a uniform profile, sinking over many cells and past the surface, the four outcomes of the positivity step -- and
 shown to be continuous at every parity case; the table roms_bio.def through abi.py, the header and the Fortran module.
-Parity status: UNPINNED -- no reference build with BIOLOGY exists under oracle/."""
+The restatement itself is pinned to the reference builds UPWELLING_BIO / UPWELLING_BIO_CPAR by tests/test_ref_pinning.py
+and to their vectors (tests/golden/ref_bio.npz) by tests/test_golden.py."""
 import ctypes
 import os
 import re

@@ -906,3 +906,61 @@ def test_hip_reproduces_reference_on_the_curvilinear_grid(config):
             h.close()
         diffs = util.compare_states(st_h, st_o)
         assert all(v <= (1e-10 if how[0] == "gls" else 1e-13) for v in diffs.values()), (key, diffs)
+
+
+# -------------------------------------------------- NPZD biology and the KPP bottom boundary layer: reference vectors --
+# tests/golden/ref_bio.npz and ref_bkpp.npz hold what the reference's own biology(ng, tile) (NPZD_POWELL) and
+# lmd_vmix(ng, tile) (LMD_BKPP) give on states of tests/test_gpu_bio.py / tests/test_gpu_bkpp.py.  Here the numpy
+# restatements reproduce them within the bound of tests/test_ref_pinning.py, 1e-13 of each stored array's maximum (numpy's
+# exp, sqrt and ** against the Fortran runtime's); -m gpu, the device does within 1e-10 (tests/test_gpu_bio.py,
+# tests/test_gpu_bkpp.py).
+BIO_CASES = [c.format(m) for c in ("PARTIAL-{}-sink", "N17-{}-sink", "N33-{}-sink", "N33-{}-default", "TINY-{}-constpar")
+             for m in ("plain", "island")]
+BKPP_CASES = [f"{g}-{m}-{bs}" for g in ("PARTIAL", "N32", "N33") for m in ("plain", "island") for bs in ("channel", "basin")]
+
+
+@pytest.mark.parametrize("case", BIO_CASES)
+def test_restatement_reproduces_reference_biology(case):
+    import bio_util as bu
+    mg = util.load_golden_maker("make_golden_bio")
+    g = np.load(os.path.join(HERE, "golden", "ref_bio.npz"))
+    st, par = mg.prepare(case)
+    mine = mg.pack(case, st, par, bu.expected(st, par), cols=g[f"{case}/cols"])
+    util.compare_packed(g, mine, 1e-13)
+    # the stored columns keep what they were chosen for: day and night, a negative pool, the shallowest and the deepest
+    a = bu.columns(st, par)
+    ci, cj = g[f"{case}/cols"].T
+    assert (a["srflx"][ci, cj] > 0.0).any() and (a["srflx"][ci, cj] <= 0.0).any() and (a["tS"][ci, cj] < 0.0).any()
+    depth = -a["z_w"][..., 0]
+    assert depth[ci, cj].min() == depth.min() and depth[ci, cj].max() == depth.max()
+
+
+@pytest.mark.parametrize("case", BKPP_CASES)
+def test_restatement_reproduces_reference_bottom_layer(case):
+    import bkpp_util as bk
+    import oracle
+    mg = util.load_golden_maker("make_golden_bkpp")
+    g = np.load(os.path.join(HERE, "golden", "ref_bkpp.npz"))
+    st, hprev = mg.prepare(case)
+    sa = st.copy()
+    oracle.Oracle(sa).call("lmd_vmix", util.step_idx())
+    r = bk.expected(st, sa["Akv"], sa["Akt"], sa["hsbl"], hprev)
+    I = bk.interior(st.b)
+    res = {"hbbl": r["hbbl"], "kbbl": r["kbbl"], "ksbl": r["ksbl"], "Akv": sa["Akv"].copy(), "Akt": sa["Akt"].copy()}
+    res["Akv"][I] = r["Akv"]
+    res["Akt"][I] = r["Akt"]
+    util.compare_packed(g, mg.pack(case, st, hprev, res, cols=g[f"{case}/cols"]), 1e-13)
+    assert int(g[f"{case}/kbbl"].max()) > 2 and len(g[f"{case}/cols"]) >= 5
+
+
+def test_bio_and_bkpp_fixtures_list_their_cases():
+    smallest_grid_fixture = os.path.getsize(os.path.join(HERE, "golden", "ref_atm_UPWELLING.npz"))
+    for maker, fixture, cases in (("make_golden_bio", "ref_bio.npz", BIO_CASES), ("make_golden_bkpp", "ref_bkpp.npz", BKPP_CASES)):
+        mg = util.load_golden_maker(maker)
+        assert list(mg.CASES) == cases
+        path = os.path.join(HERE, "golden", fixture)
+        g = np.load(path)
+        assert list(g["cases"]) == cases
+        assert {k.split("/")[0] for k in g.files if k != "cases"} == set(cases)
+        assert all(g[k].dtype == np.float64 for k in g.files if g[k].dtype.kind == "f")
+        assert os.path.getsize(path) < smallest_grid_fixture

@@ -1,9 +1,12 @@
 """-m gpu: the NPZD_POWELL biology on the device (roms_hip_set_biology, roms_hip_biology: k_npzd_powell) against the numpy
 restatement of npzd_Powell.h (tests/bio_util.py) on the cases whose continuity tests/test_bio.py asserts; the identities
 of the routine; whole steps against a host that does the biology itself; tiling; reuse of a context; the refusals.
-Parity status: UNPINNED -- no reference build with BIOLOGY exists under oracle/, and the yardstick is the restatement.
+Parity status: pinned -- the restatement equals the reference builds UPWELLING_BIO / UPWELLING_BIO_CPAR
+(tests/test_ref_pinning.py), and test_device_reproduces_reference_vectors compares the device with the reference's own
+vectors (tests/golden/ref_bio.npz).
 Measured on the MI355X: see DESIGN.md section 8 (the largest difference of the parity cases is recorded there)."""
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
@@ -70,6 +73,23 @@ def test_device_equals_restatement(case):
     if pset == "sink":
         ks = info["ksource_SDet"]
         assert (ks > np.arange(1, N + 1) + 1).any() and (ks[..., 0] == N).any() and (ks[..., 0] < N).any()
+
+
+# ------------------------------------------------------------------------------ 1b. device = reference vectors --
+def _fixture_cases():
+    return list(util.load_golden_maker("make_golden_bio").CASES)
+
+
+@pytest.mark.parametrize("case", _fixture_cases())
+def test_device_reproduces_reference_vectors(case):
+    """tests/golden/ref_bio.npz: t(nnew) of the reference's own biology(ng, tile) (UPWELLING_BIO / UPWELLING_BIO_CPAR of
+    oracle/build_ref.sh) at the stored columns and the column inventories, within TOL of each stored array's maximum; the
+    digest of the inputs asserts that the state is the one the reference ran."""
+    mg = util.load_golden_maker("make_golden_bio")
+    g = np.load(os.path.join(mg.HERE, "ref_bio.npz"))
+    st, par = mg.prepare(case)
+    got = _device(st, par)
+    util.compare_packed(g, mg.pack(case, st, par, got, cols=g[f"{case}/cols"]), TOL)
 
 
 # ----------------------------------------------------------------------------------------------- 2. identities --

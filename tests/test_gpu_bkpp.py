@@ -1,8 +1,11 @@
 """-m gpu: the KPP bottom boundary layer on the device (LMD_BKPP: roms_hip_set_kpp, k_lmd_bkpp inside roms_hip_lmd_vmix)
 against the numpy restatement of lmd_bkpp.F (tests/bkpp_util.py) on the states whose branch census and decision
 margins tests/test_bkpp.py asserts; the behaviour with the switch off; tiling; whole steps and the restart of hbbl; the
-refusals.  Parity status: unpinned -- no reference build with LMD_BKPP exists under oracle/."""
+refusals.  Parity status: pinned -- the restatement equals the reference builds BENCHMARK_BKPP / BENCHMARK_MASK_BKPP
+(tests/test_ref_pinning.py), and test_device_reproduces_reference_vectors compares the device with the reference's own
+vectors (tests/golden/ref_bkpp.npz)."""
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
@@ -73,6 +76,27 @@ def test_device_equals_restatement(case):
     # not vacuous: the bottom layer changed the profile of many columns, at several levels
     changed = (B["Akv"][I] != A["Akv"][I])
     assert changed.any(axis=2).sum() > 0.05 * changed.shape[0] * changed.shape[1] and r["kbbl"][I].max() > 2
+
+
+# ------------------------------------------------------------------------------ 1b. device = reference vectors --
+def _fixture_cases():
+    return list(util.load_golden_maker("make_golden_bkpp").CASES)
+
+
+@pytest.mark.parametrize("case", _fixture_cases())
+def test_device_reproduces_reference_vectors(case):
+    """tests/golden/ref_bkpp.npz: what the reference's own lmd_vmix(ng, tile) built with LMD_BKPP gives
+    (BENCHMARK_BKPP / BENCHMARK_MASK_BKPP of oracle/build_ref.sh): kbbl and ksbl identical on every interior column,
+    hbbl on every interior column, the Akv / Akt profiles at the stored columns and the column sums within TOL of each
+    stored array's maximum; hbbl's boundary values are bc_r2d_tile of its interior.  The digest of the inputs asserts
+    that the state is the one the reference ran."""
+    mg = util.load_golden_maker("make_golden_bkpp")
+    g = np.load(os.path.join(mg.HERE, "ref_bkpp.npz"))
+    st, hprev = mg.prepare(case)
+    B = _device(st, True, hprev)
+    util.compare_packed(g, mg.pack(case, st, hprev, B, cols=g[f"{case}/cols"]), TOL)
+    D = bk.defined_points(st.b)
+    _close(B["hbbl"][D], bk.bc_hbbl(st.b, B["hbbl"].copy())[D], "hbbl boundary values")
 
 
 # ----------------------------------------------------------------------------------------- 2. existing behaviour --

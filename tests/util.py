@@ -2,6 +2,7 @@
 states that exercise every stencil direction (BENCHMARK's
 zonal symmetry can hide x-direction bugs, hence the perturbations)."""
 import math
+import os
 
 import numpy as np
 
@@ -378,3 +379,35 @@ def river_sources(st, kind="walls", same_tracer=False, seed=3, at=()):
     st.p = type(st.p).from_buffer_copy(st.p)
     st.p.point_sources = (1 if any(d < 2.0 for d in D) else 0) | (2 if any(d == 2.0 for d in D) else 0)
     return st.sources
+
+
+def load_golden_maker(name):
+    """tests/golden/<name>.py as a module (the makers hold the case tables and the packing of their fixtures)"""
+    import importlib
+    import sys
+    gd = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    if gd not in sys.path:
+        sys.path.insert(0, gd)
+    return importlib.import_module(name)
+
+
+def compare_packed(g, mine, tol):
+    """A fixture of packed cases (tests/golden/make_golden_bio.py, make_golden_bkpp.py) against the same packing of a
+    candidate's result: strings (the digest of the inputs) and integer arrays identical, float arrays within tol of the
+    stored array's largest magnitude.  Prints each figure before it asserts; returns the largest ratio."""
+    worst = 0.0
+    for key, got in mine.items():
+        want = g[key]
+        assert want.shape == got.shape and want.dtype == got.dtype, (key, want.shape, got.shape, want.dtype, got.dtype)
+        if want.dtype.kind != "f":
+            assert np.array_equal(want, got), (key, "the inputs drifted from the fixture's" if key.endswith("/sha") else "")
+            continue
+        scale = float(np.abs(want).max())
+        err = float(np.abs(got - want).max())
+        print(f"{key}: max |diff| {err:.3e}, field max {scale:.3e}, ratio {err / scale:.3e}")
+        worst = max(worst, err / scale)
+    for key, got in mine.items():
+        want = g[key]
+        if want.dtype.kind == "f":
+            assert float(np.abs(got - want).max()) <= tol * float(np.abs(want).max()), key
+    return worst
