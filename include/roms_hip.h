@@ -142,6 +142,13 @@ typedef struct roms_bio_powell {
 #include "roms_bio.def"
 } roms_bio_powell_t;
 
+/* Parameters of the BIO_FENNEL ecosystem model (roms_hip_set_biology): roms_bio_fennel.def.  The CPP options of the
+ * reference are 0/1 members (bio_sediment, denitrification, oxygen, carbon, bulk_fluxes).  The device side of the model
+ * is not built yet (see BIOLOGY below): no entry takes this block. */
+typedef struct roms_bio_fennel {
+#include "roms_bio_fennel.def"
+} roms_bio_fennel_t;
+
 #undef ROMS_MEMBER
 #undef ROMS_MEMBER_A
 #undef ROMS_MEMBER_A2
@@ -295,6 +302,12 @@ int roms_hip_gls_corstep(const roms_step_idx_t *s);
  * name, leaving the previous setting in force: a call before bounds / params, a model that is not built or unknown,
  * another nbytes, an idbio entry outside NAT+1 .. NT or repeated, BioIter < 0, a sinking speed < 0.  BioIter = 0 is
  * accepted and roms_hip_biology then returns at once (npzd_Powell.h:180).  roms_hip_set_bounds drops the setting.
+ *
+ * ROMS_BIO_FENNEL (fennel.h:243-1577, pCO2_water :1913-2372) is NOT built on the device: the library refuses it by
+ * name like the other models.  Its parameter block, roms_bio_fennel_t above, is defined so that hosts, the Python
+ * mirror and the tests agree on it already.  Options without a member there will not be built with it: PO4, RIVER_DON,
+ * TALK_NONCONSERV, DIAGNOSTICS_BIO, pCO2_RZ, RW14_OXYGEN_SC, OCMIP_OXYGEN_SC, RW14_CO2_SC, PCO2AIR_DATA,
+ * PCO2AIR_SECULAR, the Newton solver of pCO2_water, LINEAR_CONTINUATION / NEUMANN.
  *
  * roms_hip_biology(s) uses s->nstp and s->nnew; refused before roms_hip_set_biology ("biology is not switched on") and
  * for N < 4.  Timer entry: "biology". */

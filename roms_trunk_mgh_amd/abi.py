@@ -103,7 +103,8 @@ def _parse_members(def_file):
 STRUCTS = {"roms_bounds_t": _parse_members("roms_bounds.def"),
            "roms_params_t": _parse_members("roms_params.def"),
            "roms_step_idx_t": _parse_members("roms_step_idx.def"),
-           "roms_bio_powell_t": _parse_members("roms_bio.def")}
+           "roms_bio_powell_t": _parse_members("roms_bio.def"),
+           "roms_bio_fennel_t": _parse_members("roms_bio_fennel.def")}
 _CTYPES = {"int": C.c_int, "double": C.c_double}
 
 
@@ -144,6 +145,12 @@ class StepIdx(C.Structure):
 class BioPowell(C.Structure):
     """roms_bio_powell_t -- the parameters of npzd_Powell_mod.h / npzd_Powell.in, idbio and Cp (roms_bio.def)."""
     _fields_ = _ctypes_fields(STRUCTS["roms_bio_powell_t"])
+
+
+class BioFennel(C.Structure):
+    """roms_bio_fennel_t -- the switches, idbio, the parameters of fennel_mod.h / bio_Fennel.in and Cp (roms_bio_fennel.def); the
+    library does not take it yet."""
+    _fields_ = _ctypes_fields(STRUCTS["roms_bio_fennel_t"])
 
 
 # enum roms_bio_model: the ecosystem models of the reference; only NPZD_POWELL is built

@@ -106,6 +106,14 @@ MODULE roms_hip_mod
     REAL(c_double) :: AttSW, AttPhy, PhyIS, Vm_NO3, PhyMRD, PhyMRN, K_NO3, Ivlev
     REAL(c_double) :: ZooGR, ZooEED, ZooEEN, ZooMRD, ZooMRN, DetRR, wPhy, wDet, PARfrac, Cp
   END TYPE roms_bio_powell_t
+  !  mirrors `roms_bio_fennel_t` (include/roms_bio_fennel.def): the BIO_FENNEL switches, idbio and the parameters of
+  !  mod_biology (fennel_mod.h) for grid ng, Cp of mod_scalars.  No entry takes it yet: BIO_FENNEL is refused by name.
+  TYPE, BIND(C), PUBLIC :: roms_bio_fennel_t
+    INTEGER(c_int) :: BioIter, bio_sediment, denitrification, oxygen, carbon, bulk_fluxes, idbio(12)
+    REAL(c_double) :: AttSW, AttChl, PARfrac, Vp0, I_thNH4, D_p5NH4, NitriR, K_NO3, K_NH4, K_Phy, Chl2C_m, ChlMin
+    REAL(c_double) :: PhyCN, PhyIS, PhyMin, PhyMR, ZooAE_N, ZooBM, ZooCN, ZooER, ZooGR, ZooMin, ZooMR
+    REAL(c_double) :: LDeRRN, LDeRRC, CoagR, SDeRRN, SDeRRC, wPhy, wLDet, wSDet, pCO2air, Cp
+  END TYPE roms_bio_fennel_t
   !  ecosystem models = enum roms_bio_model of include/roms_hip.h; only ROMS_BIO_NPZD_POWELL is built, the others are
   !  refused by name
   INTEGER(c_int), PARAMETER, PUBLIC :: ROMS_BIO_NONE = 0, ROMS_BIO_NPZD_POWELL = 1, ROMS_BIO_NPZD_FRANKS = 2
