@@ -652,6 +652,10 @@ int roms_hip_calib_stream(long n_doubles);
  * error naming the array otherwise (a kernel stored outside LBi:UBi,LBj:UBj at the first or last plane).
  * Reads in the band are harmless by construction and deliver NaN. */
 int roms_hip_check_guards(void);
+/* The arrays roms_hip_check_guards looks at -- every live guarded array, in allocation order: returns their number
+ * and, where buf is not NULL, writes their names into buf[cap] as one C string, a line each: NAME, or NAME[q] for
+ * the indexed scratch arrays (a buffer too small cuts the list).  -1 without roms_hip_init. */
+long roms_hip_guarded_arrays(char *buf, long cap);
 
 #ifdef __cplusplus
 }

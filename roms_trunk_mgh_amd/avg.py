@@ -1,7 +1,7 @@
 """Time-averaged fields (AVERAGES): the host-side image of what an application selects with the Aout switches of its
 roms_*.in and nAVG / ntsAVG, the table of the averages (include/roms_avg.def, the file the C side compiles) and the
 schedule of set_avg_tile (ROMS/Nonlinear/set_avg.F:237-240, :1264, :2298-2301) with that of set_avg_masks
-(ROMS/Utility/set_masks.F:466-468).  `phase` mirrors roms_hip_avg_phase of csrc/capi.hip; tests/test_avg.py holds both
+(ROMS/Utility/set_masks.F:466-468).  `phase` mirrors roms_hip_avg_phase of csrc/k_avg.hip; tests/test_avg.py holds both
 against a table written out by hand.
 
 Only the HIP path computes averages: main3d.Main3D(backend, averages=Averages(...)) issues set_avg after set_zeta

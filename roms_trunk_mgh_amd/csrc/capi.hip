@@ -12,7 +12,7 @@ static const int k_field_kind[FID_COUNT] = {
 #include "roms_fields.def"
 #undef ROMS_FIELD
 };
-static const char *k_field_name[FID_COUNT] = {
+const char *const k_field_name[FID_COUNT] = {
 #define ROMS_FIELD(name, kind, owner) #name,
 #include "roms_fields.def"
 #undef ROMS_FIELD
@@ -22,6 +22,26 @@ int roms_fail(const char *where, const char *what)
 {
   g_ctx.last_error = std::string(where) + ": " + what;
   return 8;   // ROMS exit_flag 8 = "Fatal algorithm result" (mod_scalars.F:523-532)
+}
+
+int roms_setup_check(const char *me)
+{
+  if (!g_ctx.inited || !g_ctx.have_bounds || !g_ctx.have_params)
+    return roms_fail(me, "roms_hip_init, roms_hip_set_bounds and roms_hip_set_params come first");
+  return 0;
+}
+
+int roms_copy_out(const char *me, const char *family, const char *name, const void *dev, long count, void *host,
+                  long host_count, size_t elem, const char *unit)
+{
+  if (host_count != count) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: %s has %ld %s, the host array %ld", family, name, count, unit, host_count);
+    return roms_fail(me, msg);
+  }
+  HIP_TRY(hipMemcpyAsync(host, dev, elem * count, hipMemcpyDeviceToHost, g_ctx.stream));
+  HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+  return 0;
 }
 
 long roms_field_count(int kind, const roms_bounds_t &b)
@@ -77,8 +97,6 @@ __global__ void __launch_bounds__(256) k_calib_stream(const double *__restrict__
   const long e = (long)blockIdx.x * 256 + threadIdx.x;
   if (e < n) dst[e] = src[e];
 }
-int roms_entry_check(const char *where);
-namespace { void sources_release(); void clima_release(); void avg_release(); }
 extern "C" int roms_hip_calib_stream(long n)
 {
   int rc = roms_entry_check("roms_hip_calib_stream");
@@ -107,66 +125,42 @@ __global__ void k_fill_guard(unsigned long long *p, long n, unsigned long long b
   if (e < n) p[e] = bits;
 }
 
-int guarded_alloc(double **user, double **base, long n)
+// Every live guarded array, in allocation order: guarded_alloc enters it and guarded_free takes it out, so that an
+// array cannot exist without being checked.  (Copies: a store may move its Guarded structs about.)
+static std::vector<Guarded> g_guarded;
+
+int guarded_alloc(Guarded *a, const char *name, int q, long n)
 {
   const long g = g_ctx.guard;
-  *user = *base = nullptr;
-  HIP_TRY(hipMalloc(base, sizeof(double) * (n + 2 * g)));
-  *user = *base + g;
+  *a = Guarded{};
+  HIP_TRY(hipMalloc(&a->base, sizeof(double) * (n + 2 * g)));
+  a->dev = a->base + g;
+  a->count = n;
+  a->name = name;
+  a->q = q;
+  g_guarded.push_back(*a);
   if (g > 0) {
     hipLaunchKernelGGL(k_fill_guard, dim3((unsigned)((g + 255) / 256)), dim3(256), 0, g_ctx.stream,
-                       (unsigned long long *)*base, g, k_guard_bits);
+                       (unsigned long long *)a->base, g, k_guard_bits);
     hipLaunchKernelGGL(k_fill_guard, dim3((unsigned)((g + 255) / 256)), dim3(256), 0, g_ctx.stream,
-                       (unsigned long long *)(*user + n), g, k_guard_bits);
+                       (unsigned long long *)(a->dev + n), g, k_guard_bits);
     KERNEL_CHECK("k_fill_guard");
   }
-  HIP_TRY(hipMemsetAsync(*user, 0, sizeof(double) * n, g_ctx.stream));
+  HIP_TRY(hipMemsetAsync(a->dev, 0, sizeof(double) * n, g_ctx.stream));
   return 0;
 }
 
-void guarded_free(double **user, double **base)
+void guarded_free(Guarded *a)
 {
-  if (*base) (void)hipFree(*base);
-  *user = *base = nullptr;
+  if (a->base) {
+    g_guarded.erase(std::find_if(g_guarded.begin(), g_guarded.end(), [a](const Guarded &t) { return t.base == a->base; }));
+    (void)hipFree(a->base);
+  }
+  *a = Guarded{};
 }
 
-// ---- AVERAGES: the lines of roms_avg.def and the library-owned arrays (roms_hip_set_averages below) ----
-enum { AVG_GT_r = GT_R, AVG_GT_u = GT_U, AVG_GT_v = GT_V, AVG_GT_w = GT_R, AVG_GT_p = GT_P };
-enum { AVG_CNT_p = 0, AVG_CNT_r, AVG_CNT_u, AVG_CNT_v };
-const AvgLine k_avg_line[AVG_COUNT] = {
-#define ROMS_AVG(name, aout, grid, shape, mask, range, expr, srcA, srcB, plane)                                       \
-  {#name, nullptr, AVG_GT_##grid, shape, FID_##mask, range, expr, FID_##srcA, FID_##srcB, plane, -1},
-#define ROMS_AVG_NOT_BUILT(name, aout, why) {#name, #aout ": " #why, 0, 0, 0, 0, 0, 0, 0, 0, -1},
-#define ROMS_AVG_COUNTER(name, grid) {#name, nullptr, AVG_GT_##grid, AVS_2D, 0, 0, 0, 0, 0, 0, AVG_CNT_##grid},
-#include "roms_avg.def"
-#undef ROMS_AVG
-#undef ROMS_AVG_NOT_BUILT
-#undef ROMS_AVG_COUNTER
-};
-AvgStore g_avg;
-// row of AoutT of a per-tracer line = its rank among the AVS_NT lines of the table; -1 otherwise
-static int avg_tkind(int id)
-{
-  const AvgLine &L = k_avg_line[id];
-  if (L.why || L.counter >= 0 || L.shape != AVS_NT) return -1;
-  int r = 0;
-  for (int q = 0; q < id; q++)
-    if (!k_avg_line[q].why && k_avg_line[q].counter < 0 && k_avg_line[q].shape == AVS_NT) r++;
-  return r;
-}
-
-// ---- climatology (mod_clima.F), roms_hip_set_clima: the eight device copies, each with its guard bands ----
-namespace {
-enum { CL_M2nudgcof = 0, CL_ubarclm, CL_vbarclm, CL_M3nudgcof, CL_uclm, CL_vclm, CL_Tnudgcof, CL_tclm, CL_COUNT };
-const char *const k_clima_name[CL_COUNT] = {"M2nudgcof", "ubarclm", "vbarclm", "M3nudgcof", "uclm", "vclm", "Tnudgcof", "tclm"};
-struct ClimaStore {
-  double *dev[CL_COUNT] = {nullptr}, *base[CL_COUNT] = {nullptr};
-  long count[CL_COUNT] = {0};
-} g_clima;
-}  // namespace
-
-// 0 = every guard band intact; otherwise an error naming the first damaged array (field name, or ws3[q] /
-// ws2[q] for scratch) and the distance of the first damaged word from the array.
+// 0 = every guard band intact; otherwise an error naming a damaged array (field name, or ws3[q] / ws2[q] for
+// scratch) and the distance of the first damaged word from the array.
 extern "C" int roms_hip_check_guards(void)
 {
   if (!g_ctx.inited || !g_ctx.have_bounds) return roms_fail("roms_hip_check_guards", "set_bounds first");
@@ -174,53 +168,33 @@ extern "C" int roms_hip_check_guards(void)
   if (g <= 0) return 0;
   HIP_TRY(hipStreamSynchronize(g_ctx.stream));
   std::vector<unsigned long long> h(2 * g);
-  const roms_bounds_t &b = g_ctx.b;
-  const long nij = (long)(b.UBi - b.LBi + 1) * (long)(b.UBj - b.LBj + 1);
-  auto check = [&](const char *name, int q, const double *base, long n) -> int {
-    if (!base) return 0;
-    HIP_TRY(hipMemcpy(h.data(), base, sizeof(double) * g, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(h.data() + g, base + g + n, sizeof(double) * g, hipMemcpyDeviceToHost));
+  for (const Guarded &a : g_guarded) {
+    HIP_TRY(hipMemcpy(h.data(), a.base, sizeof(double) * g, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h.data() + g, a.dev + a.count, sizeof(double) * g, hipMemcpyDeviceToHost));
     for (long e = 0; e < 2 * g; e++)
       if (h[e] != k_guard_bits) {
         char msg[200];
-        if (q >= 0) snprintf(msg, sizeof msg, "store outside %s[%d]: %ld doubles %s the array", name, q,
-                             e < g ? g - e : e - g + 1, e < g ? "before" : "behind");
-        else snprintf(msg, sizeof msg, "store outside field %s: %ld doubles %s the array", name,
+        if (a.q >= 0) snprintf(msg, sizeof msg, "store outside %s[%d]: %ld doubles %s the array", a.name, a.q,
+                               e < g ? g - e : e - g + 1, e < g ? "before" : "behind");
+        else snprintf(msg, sizeof msg, "store outside field %s: %ld doubles %s the array", a.name,
                       e < g ? g - e : e - g + 1, e < g ? "before" : "behind");
         return roms_fail("roms_hip_check_guards", msg);
       }
-    return 0;
-  };
-  int rc;
-  for (int id = 0; id < FID_COUNT; id++)
-    if ((rc = check(k_field_name[id], -1, g_ctx.dev_base[id], g_ctx.count[id]))) return rc;
-  for (int q = 0; q < CL_COUNT; q++)
-    if ((rc = check(k_clima_name[q], -1, g_clima.base[q], g_clima.count[q]))) return rc;
-  for (int q = 0; q < g_avg.n; q++)
-    if ((rc = check(k_avg_line[g_avg.arr[q].id].name, -1, g_avg.arr[q].base, g_avg.arr[q].count))) return rc;
-  for (int q = 0; q < 4; q++)
-    if ((rc = check(k_avg_line[AVG_pmask_avg + q].name, -1, g_avg.cnt_base[q], g_avg.nij))) return rc;
-  {
-    const char *name[4];
-    const double *base[4];
-    long count[4];
-    const int n = dia_arrays(name, base, count);
-    for (int q = 0; q < n; q++)
-      if ((rc = check(name[q], -1, base[q], count[q]))) return rc;
   }
-  {
-    const char *name[3];
-    const double *base[3];
-    long count[3];
-    const int n = kpp_arrays(name, base, count);
-    for (int q = 0; q < n; q++)
-      if ((rc = check(name[q], -1, base[q], count[q]))) return rc;
-  }
-  for (int q = 0; q < ROMS_NWS3; q++)
-    if ((rc = check("ws3", q, g_ctx.ws3_base[q], nij * (b.N + 1)))) return rc;
-  for (int q = 0; q < 32; q++)
-    if ((rc = check("ws2", q, g_ctx.ws2_base[q], nij))) return rc;
   return 0;
+}
+
+extern "C" long roms_hip_guarded_arrays(char *buf, long cap)
+{
+  if (!g_ctx.inited) return roms_fail("roms_hip_guarded_arrays", "library not initialised"), -1;
+  std::string s;
+  for (const Guarded &a : g_guarded) s += a.q >= 0 ? std::string(a.name) + "[" + std::to_string(a.q) + "]\n" : std::string(a.name) + "\n";
+  if (buf && cap > 0) {
+    const size_t n = std::min(s.size(), (size_t)cap - 1);     // (a buffer too small cuts the list; it stays a C string)
+    memcpy(buf, s.data(), n);
+    buf[n] = 0;
+  }
+  return (long)g_guarded.size();
 }
 
 // ------------------------------------------------------------- life cycle --
@@ -243,6 +217,14 @@ int halo_init();      // halo.hip
 int halo_finalize();
 void halo_bounds_changed();
 extern "C" int roms_hip_finalize(void);
+
+// The option stores: device memory outside the field registry that belongs to one set of bounds.  roms_hip_finalize
+// and roms_hip_set_bounds release them in this order; why the bounds invalidate a store is told at its release function.
+struct OptionStore { const char *name; void (*release)(); };
+static const OptionStore k_option_store[] = {
+  {"sources", sources_release}, {"clima", clima_release}, {"avg", avg_release}, {"floats", floats_release},
+  {"tides", tides_release}, {"data", data_release}, {"dia", dia_release}, {"kpp", kpp_release}, {"bio", bio_release},
+};
 
 extern "C" int roms_hip_init(int rank, int ntileI, int ntileJ, int device_id, const void *nccl_unique_id)
 {
@@ -294,21 +276,12 @@ extern "C" int roms_hip_finalize(void)
   halo_finalize();
   diag_release();
   for (int i = 0; i < FID_COUNT; i++) {
-    guarded_free(&g_ctx.dev[i], &g_ctx.dev_base[i]);
+    guarded_free(&g_ctx.field[i]);
     g_ctx.host[i] = nullptr;
-    g_ctx.count[i] = 0;
   }
-  for (int q = 0; q < ROMS_NWS3; q++) guarded_free(&g_ctx.hostc.ws3[q], &g_ctx.ws3_base[q]);
-  for (int q = 0; q < 32; q++) guarded_free(&g_ctx.hostc.ws2[q], &g_ctx.ws2_base[q]);
-  sources_release();
-  clima_release();
-  avg_release();
-  floats_release();
-  tides_release();
-  data_release();
-  dia_release();
-  kpp_release();
-  bio_release();
+  for (int q = 0; q < ROMS_NWS3; q++) { guarded_free(&g_ctx.ws3[q]); g_ctx.hostc.ws3[q] = nullptr; }
+  for (int q = 0; q < 32; q++) { guarded_free(&g_ctx.ws2[q]); g_ctx.hostc.ws2[q] = nullptr; }
+  for (const OptionStore &o : k_option_store) o.release();
   if (g_ctx.devc) (void)hipFree(g_ctx.devc);
   g_ctx.devc = nullptr;
   if (g_ctx.stream) (void)hipStreamDestroy(g_ctx.stream);
@@ -316,344 +289,6 @@ extern "C" int roms_hip_finalize(void)
   g_ctx.inited = false;
   g_ctx.have_bounds = g_ctx.have_params = false;
   return 0;
-}
-
-// ---- point sources (mod_sources.F), LuvSrc ----
-namespace {
-struct SrcStore {
-  int *geo = nullptr;        // device: I[n], J[n], D[n], umap[nij], vmap[nij]
-  double *val = nullptr;     // device: Qbar[n], Qsrc[n*N], Tsrc[n*N*NT]
-  int n = 0, N = 0, NT = 0;
-  long nij = 0;
-  std::vector<int> I, J, D;
-  bool given = false;
-} g_src;
-
-void sources_release()
-{
-  if (g_src.geo) (void)hipFree(g_src.geo);
-  if (g_src.val) (void)hipFree(g_src.val);
-  g_src = SrcStore{};
-  g_ctx.hostc.src = RomsSrc{};
-  g_ctx.devc_dirty = true;
-}
-}  // namespace
-
-bool roms_sources_given() { return g_src.given; }
-
-extern "C" int roms_hip_set_sources(int Nsrc, const int *Isrc, const int *Jsrc, const double *Dsrc, const double *Qbar,
-                                    const double *Qsrc, const double *Tsrc, const int *LtracerSrc)
-{
-  const char *me = "roms_hip_set_sources";
-  if (!g_ctx.inited || !g_ctx.have_bounds || !g_ctx.have_params)
-    return roms_fail(me, "roms_hip_init, roms_hip_set_bounds and roms_hip_set_params come first");
-  if (Nsrc < 0) return roms_fail(me, "Nsrc < 0");
-  if (!(g_ctx.p.point_sources & 3))
-    return roms_fail(me, "point sources: neither bit of roms_params_t.point_sources (LuvSrc, LwSrc) is set");
-  const bool luv = (g_ctx.p.point_sources & 1) != 0, lw = (g_ctx.p.point_sources & 2) != 0;
-  if (Nsrc == 0) {
-    HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-    step2d_graphs_release();               // captured source launches hold the freed table's size
-    sources_release();
-    g_src.given = true;
-    return 0;
-  }
-  if (!Isrc || !Jsrc || !Dsrc || !Qbar || !Qsrc || !Tsrc || !LtracerSrc) return roms_fail(me, "null argument");
-  const roms_bounds_t &b = g_ctx.b;
-  const int N = b.N, NT = b.NT;
-  const long ni = b.UBi - b.LBi + 1, nij = ni * (b.UBj - b.LBj + 1);
-  std::vector<int> D(Nsrc);
-  for (int is = 0; is < Nsrc; is++) {
-    D[is] = (int)Dsrc[is];
-    if (D[is] < 0 || D[is] > 2) return roms_fail(me, "point sources: Dsrc is 0 (u-face), 1 (v-face) or 2 (cell centre)");
-  }
-  const bool same = g_src.geo && g_src.n == Nsrc && g_src.N == N && g_src.NT == NT && g_src.nij == nij &&
-                    std::equal(g_src.I.begin(), g_src.I.end(), Isrc) && std::equal(g_src.J.begin(), g_src.J.end(), Jsrc) &&
-                    g_src.D == D;
-  const size_t nval = (size_t)Nsrc * (1 + (size_t)N + (size_t)N * NT);
-  if (!same) {
-    HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-    step2d_graphs_release();               // captured launches hold the old table's addresses
-    sources_release();
-    const size_t ngeo = 3 * (size_t)Nsrc + 3 * (size_t)nij + 2 * (size_t)Nsrc;
-    std::vector<int> geo(ngeo, 0);
-    int *umap = geo.data() + 3 * (size_t)Nsrc, *vmap = umap + nij, *wmap = vmap + nij, *cells = wmap + nij;
-    int ncell = 0;
-    for (int is = 0; is < Nsrc; is++) {
-      geo[is] = Isrc[is]; geo[Nsrc + is] = Jsrc[is]; geo[2 * (size_t)Nsrc + is] = D[is];
-      // a source of a kind the application has switched off is not looked at (IF (LuvSrc) / IF (LwSrc) in the reference)
-      if (D[is] == 2 ? !lw : !luv) continue;
-      // the face / cell maps: the last source of a face wins, as the sequential loops of the reference leave it
-      if (Isrc[is] >= b.LBi && Isrc[is] <= b.UBi && Jsrc[is] >= b.LBj && Jsrc[is] <= b.UBj)
-        (D[is] == 0 ? umap : D[is] == 1 ? vmap : wmap)[(long)(Isrc[is] - b.LBi) + (long)(Jsrc[is] - b.LBj) * ni] = is + 1;
-      // the two cells of the face (the one cell of a cell-centred source), where they are interior cells of this tile
-      // (each once)
-      for (int side = 0; side < (D[is] == 2 ? 1 : 2); side++) {
-        const int ci = Isrc[is] - (D[is] == 0 ? side : 0), cj = Jsrc[is] - (D[is] == 1 ? side : 0);
-        if (ci < b.Istr || ci > b.Iend || cj < b.Jstr || cj > b.Jend) continue;
-        const int cell = (int)((long)(ci - b.LBi) + (long)(cj - b.LBj) * ni);
-        if (std::find(cells, cells + ncell, cell) == cells + ncell) cells[ncell++] = cell;
-      }
-    }
-    HIP_TRY(hipMalloc(&g_src.geo, sizeof(int) * ngeo));
-    HIP_TRY(hipMalloc(&g_src.val, sizeof(double) * (nval + (size_t)Nsrc * N)));
-    HIP_TRY(hipMemcpy(g_src.geo, geo.data(), sizeof(int) * ngeo, hipMemcpyHostToDevice));
-    g_src.n = Nsrc; g_src.N = N; g_src.NT = NT; g_src.nij = nij;
-    g_src.I.assign(Isrc, Isrc + Nsrc); g_src.J.assign(Jsrc, Jsrc + Nsrc); g_src.D = D;
-    RomsSrc &S = g_ctx.hostc.src;
-    S.n = Nsrc;
-    S.I = g_src.geo; S.J = g_src.geo + Nsrc; S.D = g_src.geo + 2 * (size_t)Nsrc;
-    S.umap = g_src.geo + 3 * (size_t)Nsrc; S.vmap = S.umap + nij;
-    S.wmap = S.vmap + nij;
-    S.cells = S.wmap + nij; S.ncell = ncell;
-    S.Qbar = g_src.val; S.Qsrc = g_src.val + Nsrc; S.Tsrc = g_src.val + Nsrc + (size_t)Nsrc * N;
-    S.save = g_src.val + nval;
-  }
-  // the values change with every set_data: one staged copy (a few kB), in stream order after the kernels that read the old ones
-  std::vector<double> val(nval);
-  std::copy(Qbar, Qbar + Nsrc, val.begin());
-  std::copy(Qsrc, Qsrc + (size_t)Nsrc * N, val.begin() + Nsrc);
-  std::copy(Tsrc, Tsrc + (size_t)Nsrc * N * NT, val.begin() + Nsrc + (size_t)Nsrc * N);
-  HIP_TRY(hipMemcpyAsync(g_src.val, val.data(), sizeof(double) * nval, hipMemcpyHostToDevice, g_ctx.stream));
-  HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-  for (int it = 0; it < ROMS_MAXNT; it++) g_ctx.hostc.src.ltr[it] = it < NT ? (LtracerSrc[it] != 0) : 0;
-  g_src.given = true;
-  g_ctx.devc_dirty = true;
-  return 0;
-}
-
-// ---- climatology nudging (mod_clima.F:190-261), LnudgeM2CLM / LnudgeM3CLM / LnudgeTCLM ----
-namespace {
-void clima_release()
-{
-  for (int q = 0; q < CL_COUNT; q++) {
-    guarded_free(&g_clima.dev[q], &g_clima.base[q]);
-    g_clima.count[q] = 0;
-  }
-  g_ctx.hostc.clima = RomsClima{};
-  g_ctx.devc_dirty = true;
-}
-}  // namespace
-
-extern "C" int roms_hip_set_clima(int LnudgeM2CLM, const double *M2nudgcof, const double *ubarclm, const double *vbarclm,
-                                  int LnudgeM3CLM, const double *M3nudgcof, const double *uclm, const double *vclm,
-                                  const int *LnudgeTCLM, const double *Tnudgcof, const double *tclm, double obcfac)
-{
-  const char *me = "roms_hip_set_clima";
-  if (!g_ctx.inited || !g_ctx.have_bounds || !g_ctx.have_params)
-    return roms_fail(me, "roms_hip_init, roms_hip_set_bounds and roms_hip_set_params come first");
-  if (!(obcfac >= 0.0)) return roms_fail(me, "climatology: obcfac < 0");
-  const roms_bounds_t &b = g_ctx.b;
-  const long nij = (long)(b.UBi - b.LBi + 1) * (long)(b.UBj - b.LBj + 1);
-  RomsClima want{};
-  want.m2 = LnudgeM2CLM != 0;
-  want.m3 = LnudgeM3CLM != 0;
-  want.obcfac = obcfac;
-  for (int it = 0; it < b.NT; it++)
-    if (LnudgeTCLM && LnudgeTCLM[it]) {
-      want.itrc[want.nt] = it + 1;
-      want.ic[it] = ++want.nt;
-    }
-  const RomsClima &have = g_ctx.hostc.clima;
-  if (!want.m2 && !want.m3 && !want.nt) {              // all flags zero: release everything
-    if (have.m2 || have.m3 || have.nt) {
-      HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-      step2d_graphs_release();
-      clima_release();
-    }
-    return 0;
-  }
-  const bool same = want.m2 == have.m2 && want.m3 == have.m3 && std::equal(want.ic, want.ic + ROMS_MAXNT, have.ic);
-  const double *host[CL_COUNT] = {M2nudgcof, ubarclm, vbarclm, M3nudgcof, uclm, vclm, Tnudgcof, tclm};
-  const long n[CL_COUNT] = {nij, nij, nij, nij * b.N, nij * b.N, nij * b.N, nij * b.N * want.nt, nij * b.N * want.nt};
-  const bool on[CL_COUNT] = {want.m2 != 0, want.m2 != 0, want.m2 != 0, want.m3 != 0, want.m3 != 0, want.m3 != 0,
-                             want.nt != 0, want.nt != 0};
-  // a NULL array = "keep the copy you have": only with the flags of the call that gave it.  Nothing is touched
-  // before every argument has been looked at, so that a refused call leaves the library as it was.
-  for (int q = 0; q < CL_COUNT; q++)
-    if (on[q] && !host[q] && !(same && g_clima.dev[q])) {
-      const std::string m = std::string("climatology: the switch of ") + k_clima_name[q] + " is set but the array was never "
-                            "given (NULL keeps an earlier copy only after a call with the same switches that brought one)";
-      return roms_fail(me, m.c_str());
-    }
-  HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-  // the boundary-condition launches inside the captured LOOP_2D graphs hold the coefficient address and obcfac
-  if (!same || want.obcfac != have.obcfac) step2d_graphs_release();
-  if (!same) clima_release();
-  for (int q = 0; q < CL_COUNT; q++) {
-    if (!on[q] || !host[q]) continue;
-    if (!g_clima.dev[q]) {
-      int rc = guarded_alloc(&g_clima.dev[q], &g_clima.base[q], n[q]);
-      if (rc) { clima_release(); return rc; }
-      g_clima.count[q] = n[q];
-    }
-    HIP_TRY(hipMemcpyAsync(g_clima.dev[q], host[q], sizeof(double) * n[q], hipMemcpyHostToDevice, g_ctx.stream));
-  }
-  HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-  want.M2nudgcof = g_clima.dev[CL_M2nudgcof]; want.ubarclm = g_clima.dev[CL_ubarclm]; want.vbarclm = g_clima.dev[CL_vbarclm];
-  want.M3nudgcof = g_clima.dev[CL_M3nudgcof]; want.uclm = g_clima.dev[CL_uclm]; want.vclm = g_clima.dev[CL_vclm];
-  want.Tnudgcof = g_clima.dev[CL_Tnudgcof]; want.tclm = g_clima.dev[CL_tclm];
-  g_ctx.hostc.clima = want;
-  g_ctx.devc_dirty = true;
-  return 0;
-}
-
-// One of the eight device copies back to the host (tests; a host that writes the interpolated climatology out).
-extern "C" int roms_hip_get_clima(const char *name, double *host, long n_doubles)
-{
-  const char *me = "roms_hip_get_clima";
-  if (!g_ctx.inited) return roms_fail(me, "library not initialised");
-  if (!name || !host) return roms_fail(me, "climatology: null argument");
-  for (int q = 0; q < CL_COUNT; q++) {
-    if (strcmp(name, k_clima_name[q])) continue;
-    if (!g_clima.dev[q]) return roms_fail(me, (std::string("climatology: the library has no copy of ") + name + " (roms_hip_set_clima)").c_str());
-    if (n_doubles != g_clima.count[q]) {
-      char msg[200];
-      snprintf(msg, sizeof msg, "climatology: %s has %ld doubles, the host array %ld", name, g_clima.count[q], n_doubles);
-      return roms_fail(me, msg);
-    }
-    HIP_TRY(hipMemcpyAsync(host, g_clima.dev[q], sizeof(double) * n_doubles, hipMemcpyDeviceToHost, g_ctx.stream));
-    HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-    return 0;
-  }
-  return roms_fail(me, (std::string("climatology: unknown array ") + name).c_str());
-}
-
-// ---- time-averaged fields (AVERAGES; set_avg.F, mod_average.F) ----
-namespace {
-void avg_release()
-{
-  for (int q = 0; q < g_avg.n; q++) guarded_free(&g_avg.arr[q].dev, &g_avg.arr[q].base);
-  for (int q = 0; q < 4; q++) guarded_free(&g_avg.cnt[q], &g_avg.cnt_base[q]);
-  g_avg = AvgStore{};
-}
-}  // namespace
-
-// The schedule of set_avg_tile and set_avg_masks, stated once (mirror: roms_trunk_mgh_amd/avg.py, phase()).
-extern "C" int roms_hip_avg_phase(int iic, int nAVG, int ntsAVG, int ntstart, int nrrec)
-{
-  if (nAVG <= 0) return 0;                                                    // set_avg.F:189
-  int ph = 0;
-  const bool restart = nrrec > 0 && iic == ntstart;
-  if ((iic > ntsAVG && (iic - 1) % nAVG == 1) || (iic >= ntsAVG && nAVG == 1) || restart) ph |= AVP_SET;   // :237-240
-  else if (iic > ntsAVG) ph |= AVP_ADD;                                                                    // :1264
-  const bool window_end = iic > ntsAVG && (iic - 1) % nAVG == 0 && !restart;
-  if (window_end || (iic >= ntsAVG && nAVG == 1)) ph |= AVP_CLOSE;                                         // :2298-2301
-  if (window_end) ph |= AVP_MASKS;                                                                // set_masks.F:466-468
-  return ph;
-}
-
-extern "C" int roms_hip_set_averages(int nAVG, int ntsAVG, int ntstart, int nrrec, const int *Aout, const int *AoutT)
-{
-  const char *me = "roms_hip_set_averages";
-  if (!g_ctx.inited || !g_ctx.have_bounds || !g_ctx.have_params)
-    return roms_fail(me, "roms_hip_init, roms_hip_set_bounds and roms_hip_set_params come first");
-  if (nAVG < 0) return roms_fail(me, "averages: nAVG < 0");
-  if (nAVG == 0) {
-    if (g_avg.n || g_avg.cnt[0]) HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-    avg_release();
-    return 0;
-  }
-  if (!Aout) return roms_fail(me, "averages: Aout is NULL");
-  const roms_bounds_t &b = g_ctx.b;
-  const long nij = (long)(b.UBi - b.LBi + 1) * (long)(b.UBj - b.LBj + 1);
-  // the selection; nothing is touched before all of it has been looked at
-  AvgStore want;
-  want.nAVG = nAVG; want.ntsAVG = ntsAVG; want.ntstart = ntstart; want.nrrec = nrrec; want.nij = nij;
-  for (int id = 0; id < AVG_COUNT; id++) {
-    const AvgLine &L = k_avg_line[id];
-    if (L.counter >= 0) continue;
-    const int tk = avg_tkind(id);
-    for (int it = (tk >= 0 ? 1 : 0); it <= (tk >= 0 ? b.NT : 0); it++) {
-      if (tk >= 0 ? !(AoutT && AoutT[tk * b.NT + it - 1]) : !Aout[id]) continue;
-      if (L.why) {
-        const std::string m = std::string("averages: ") + L.name + " is not built (" + L.why + ")";
-        return roms_fail(me, m.c_str());
-      }
-      for (int fid : {L.srcA, L.srcB, L.expr == X_WPMPN ? (int)FID_pm : L.srcA, L.expr == X_WPMPN ? (int)FID_pn : L.srcA})
-        if (!g_ctx.dev[fid]) {
-          const std::string m = std::string("averages: ") + L.name + " reads " + k_field_name[fid] + ", which is not registered";
-          return roms_fail(me, m.c_str());
-        }
-      if (k_field_kind[L.srcA] == K_3DW_NAT && L.plane >= b.NAT) {
-        const std::string m = std::string("averages: ") + L.name + " reads tracer " + std::to_string(L.plane + 1) + " of " +
-                              k_field_name[L.srcA] + ", the tile has NAT = " + std::to_string(b.NAT);
-        return roms_fail(me, m.c_str());
-      }
-      if (k_field_kind[L.srcA] == K_2D_NT && L.plane >= b.NT) {
-        const std::string m = std::string("averages: ") + L.name + " reads tracer " + std::to_string(L.plane + 1) + " of " +
-                              k_field_name[L.srcA] + ", the tile has NT = " + std::to_string(b.NT);
-        return roms_fail(me, m.c_str());
-      }
-      AvgArray &a = want.arr[want.n++];
-      a.id = id; a.itrc = it;
-      a.nk = L.shape == AVS_2D ? 1 : L.shape == AVS_W ? b.N + 1 : b.N;
-      a.count = nij * a.nk;
-      a.dev = a.base = nullptr;
-    }
-  }
-  HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-  avg_release();
-  g_avg = want;
-  g_avg.n = 0;
-  for (int q = 0; q < want.n; q++) {                   // zero-filled, as the reference's allocation leaves them
-    AvgArray &a = g_avg.arr[q];
-    int rc = guarded_alloc(&a.dev, &a.base, a.count);
-    g_avg.n = q + 1;
-    if (rc) { avg_release(); return rc; }
-  }
-  if (g_ctx.p.wet_dry)
-    for (int q = 0; q < 4; q++) {
-      int rc = guarded_alloc(&g_avg.cnt[q], &g_avg.cnt_base[q], nij);
-      if (rc) { avg_release(); return rc; }
-    }
-  HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-  return 0;
-}
-
-// the array of (avg_id, itrc): an average or a counter; nullptr if it is not there
-static const AvgArray *avg_find(int id, int itrc, AvgArray *tmp)
-{
-  if (id < 0 || id >= AVG_COUNT) return nullptr;
-  const AvgLine &L = k_avg_line[id];
-  if (L.counter >= 0) {
-    if (!g_avg.cnt[L.counter]) return nullptr;
-    *tmp = AvgArray{id, 0, 1, g_avg.nij, g_avg.cnt[L.counter], g_avg.cnt_base[L.counter]};
-    return tmp;
-  }
-  const int want = avg_tkind(id) >= 0 ? itrc : 0;
-  for (int q = 0; q < g_avg.n; q++)
-    if (g_avg.arr[q].id == id && g_avg.arr[q].itrc == want) return &g_avg.arr[q];
-  return nullptr;
-}
-
-extern "C" int roms_hip_get_average(int avg_id, int itrc, double *host, long n_doubles)
-{
-  const char *me = "roms_hip_get_average";
-  if (!g_ctx.inited) return roms_fail(me, "library not initialised");
-  if (avg_id < 0 || avg_id >= AVG_COUNT) return roms_fail(me, "averages: bad id");
-  AvgArray tmp;
-  const AvgArray *a = avg_find(avg_id, itrc, &tmp);
-  if (!a) {
-    const std::string m = std::string("averages: ") + k_avg_line[avg_id].name + " is not selected (roms_hip_set_averages)";
-    return roms_fail(me, m.c_str());
-  }
-  if (!host) return roms_fail(me, "averages: host array is NULL");
-  if (n_doubles != a->count) {
-    char msg[200];
-    snprintf(msg, sizeof msg, "averages: %s has %ld doubles, the host array %ld", k_avg_line[avg_id].name, a->count, n_doubles);
-    return roms_fail(me, msg);
-  }
-  HIP_TRY(hipMemcpyAsync(host, a->dev, sizeof(double) * a->count, hipMemcpyDeviceToHost, g_ctx.stream));
-  HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-  return 0;
-}
-
-extern "C" double *roms_hip_average_device_ptr(int avg_id, int itrc)
-{
-  AvgArray tmp;
-  const AvgArray *a = g_ctx.inited ? avg_find(avg_id, itrc, &tmp) : nullptr;
-  return a ? a->dev : nullptr;
 }
 
 extern "C" int roms_hip_set_bounds(const roms_bounds_t *b)
@@ -664,15 +299,7 @@ extern "C" int roms_hip_set_bounds(const roms_bounds_t *b)
     return roms_fail("roms_hip_set_bounds", "tiling differs from roms_hip_init");
   step2d_graphs_release();
   roms_rowm_release();
-  sources_release();                       // the face maps are in the old bounds' index space
-  clima_release();                         // ... and the climatology has the old extents
-  avg_release();                           // ... and so have the averages
-  floats_release();                        // ... and the floats' coordinate arrays
-  tides_release();                         // ... and the tidal strips
-  data_release();                          // ... and the records of set_data
-  dia_release();                           // ... and the tracer diagnostics
-  kpp_release();                           // ... and hbbl, kbbl, ksbl of the bottom boundary layer
-  bio_release();                           // ... and the biology setting (its tracer indices belong to the old NT)
+  for (const OptionStore &o : k_option_store) o.release();   // each belongs to the old bounds
   halo_bounds_changed();                   // ... and the message plan has the old extents and ghost points
   g_ctx.b = *b;
   g_ctx.hostc.b = *b;
@@ -681,22 +308,23 @@ extern "C" int roms_hip_set_bounds(const roms_bounds_t *b)
   // new extents invalidate every mirror registered under the old ones
   for (int i = 0; i < FID_COUNT; i++) {
     snapshot_forget(i);
-    guarded_free(&g_ctx.dev[i], &g_ctx.dev_base[i]);
+    guarded_free(&g_ctx.field[i]);
     g_ctx.host[i] = nullptr;
-    g_ctx.count[i] = 0;
   }
   memset(&g_ctx.hostc.F, 0, sizeof g_ctx.hostc.F);
   // device scratch for the _tile routines' automatic arrays
   const long ni = b->UBi - b->LBi + 1, nij = ni * (long)(b->UBj - b->LBj + 1);
   g_ctx.guard = ((4 * ni + 31) / 32) * 32;
   for (int q = 0; q < ROMS_NWS3; q++) {
-    guarded_free(&g_ctx.hostc.ws3[q], &g_ctx.ws3_base[q]);
-    int rc = guarded_alloc(&g_ctx.hostc.ws3[q], &g_ctx.ws3_base[q], nij * (b->N + 1));
+    guarded_free(&g_ctx.ws3[q]);
+    int rc = guarded_alloc(&g_ctx.ws3[q], "ws3", q, nij * (b->N + 1));
+    g_ctx.hostc.ws3[q] = g_ctx.ws3[q].dev;
     if (rc) return rc;
   }
   for (int q = 0; q < 32; q++) {
-    guarded_free(&g_ctx.hostc.ws2[q], &g_ctx.ws2_base[q]);
-    int rc = guarded_alloc(&g_ctx.hostc.ws2[q], &g_ctx.ws2_base[q], nij);
+    guarded_free(&g_ctx.ws2[q]);
+    int rc = guarded_alloc(&g_ctx.ws2[q], "ws2", q, nij);
+    g_ctx.hostc.ws2[q] = g_ctx.ws2[q].dev;
     if (rc) return rc;
   }
   return 0;
@@ -719,13 +347,12 @@ extern "C" int roms_hip_set_params(const roms_params_t *p)
   // parameters.  One that the new parameters no longer allow (masking switched on, uv_vis4 ...) is dropped here so
   // that the next entry refuses the call with "field not registered" instead of running on the stale default.
   for (int id = 0; id < FID_COUNT; id++)
-    if (g_ctx.dev[id] && !g_ctx.host[id]) {
+    if (g_ctx.field[id].dev && !g_ctx.host[id]) {
       double value;
       if (!library_default(id, &value)) {
         (void)hipStreamSynchronize(g_ctx.stream);
         snapshot_forget(id);
-        guarded_free(&g_ctx.dev[id], &g_ctx.dev_base[id]);
-        g_ctx.count[id] = 0;
+        guarded_free(&g_ctx.field[id]);
         *(reinterpret_cast<double **>(&g_ctx.hostc.F) + id) = nullptr;
         if (roms_rowm_is_table_field(id)) roms_rowm_invalidate();
       }
@@ -758,24 +385,23 @@ extern "C" int roms_hip_register_field(int id, double *host_ptr, long n_doubles)
   step2d_graphs_release();
   if (roms_rowm_is_table_field(id)) roms_rowm_invalidate();
   snapshot_forget(id);          // staging / page-lock of a previous registration (other size or host array)
-  guarded_free(&g_ctx.dev[id], &g_ctx.dev_base[id]);
+  guarded_free(&g_ctx.field[id]);
   {
-    int rc = guarded_alloc(&g_ctx.dev[id], &g_ctx.dev_base[id], want);
+    int rc = guarded_alloc(&g_ctx.field[id], k_field_name[id], -1, want);
     if (rc) return rc;
   }
   g_ctx.host[id] = host_ptr;
-  g_ctx.count[id] = want;
   double **slot = reinterpret_cast<double **>(&g_ctx.hostc.F) + id;
-  *slot = g_ctx.dev[id];
+  *slot = g_ctx.field[id].dev;
   g_ctx.devc_dirty = true;
   return 0;
 }
 
 extern "C" int roms_hip_sync_to_device(int id)
 {
-  if (id < 0 || id >= FID_COUNT || !g_ctx.dev[id]) return roms_fail("roms_hip_sync_to_device", "field not registered");
+  if (id < 0 || id >= FID_COUNT || !g_ctx.field[id].dev) return roms_fail("roms_hip_sync_to_device", "field not registered");
   if (!g_ctx.host[id]) return roms_fail("roms_hip_sync_to_device", "field is kept by the library (no host array registered)");
-  HIP_TRY(hipMemcpyAsync(g_ctx.dev[id], g_ctx.host[id], sizeof(double) * g_ctx.count[id], hipMemcpyHostToDevice, g_ctx.stream));
+  HIP_TRY(hipMemcpyAsync(g_ctx.field[id].dev, g_ctx.host[id], sizeof(double) * g_ctx.field[id].count, hipMemcpyHostToDevice, g_ctx.stream));
   HIP_TRY(hipStreamSynchronize(g_ctx.stream));
   if (roms_rowm_is_table_field(id)) roms_rowm_invalidate();      // a grid-metric array may have changed
   return 0;
@@ -783,9 +409,9 @@ extern "C" int roms_hip_sync_to_device(int id)
 
 extern "C" int roms_hip_sync_to_host(int id)
 {
-  if (id < 0 || id >= FID_COUNT || !g_ctx.dev[id]) return roms_fail("roms_hip_sync_to_host", "field not registered");
+  if (id < 0 || id >= FID_COUNT || !g_ctx.field[id].dev) return roms_fail("roms_hip_sync_to_host", "field not registered");
   if (!g_ctx.host[id]) return roms_fail("roms_hip_sync_to_host", "field is kept by the library (no host array registered)");
-  HIP_TRY(hipMemcpyAsync(g_ctx.host[id], g_ctx.dev[id], sizeof(double) * g_ctx.count[id], hipMemcpyDeviceToHost, g_ctx.stream));
+  HIP_TRY(hipMemcpyAsync(g_ctx.host[id], g_ctx.field[id].dev, sizeof(double) * g_ctx.field[id].count, hipMemcpyDeviceToHost, g_ctx.stream));
   HIP_TRY(hipStreamSynchronize(g_ctx.stream));
   return 0;
 }
@@ -793,8 +419,8 @@ extern "C" int roms_hip_sync_to_host(int id)
 extern "C" int roms_hip_sync_all_to_device(void)
 {
   for (int id = 0; id < FID_COUNT; id++)
-    if (g_ctx.dev[id] && g_ctx.host[id])
-      HIP_TRY(hipMemcpyAsync(g_ctx.dev[id], g_ctx.host[id], sizeof(double) * g_ctx.count[id], hipMemcpyHostToDevice, g_ctx.stream));
+    if (g_ctx.field[id].dev && g_ctx.host[id])
+      HIP_TRY(hipMemcpyAsync(g_ctx.field[id].dev, g_ctx.host[id], sizeof(double) * g_ctx.field[id].count, hipMemcpyHostToDevice, g_ctx.stream));
   HIP_TRY(hipStreamSynchronize(g_ctx.stream));
   roms_rowm_invalidate();
   return 0;
@@ -803,8 +429,8 @@ extern "C" int roms_hip_sync_all_to_device(void)
 extern "C" int roms_hip_sync_all_to_host(void)
 {
   for (int id = 0; id < FID_COUNT; id++)
-    if (g_ctx.dev[id] && g_ctx.host[id])
-      HIP_TRY(hipMemcpyAsync(g_ctx.host[id], g_ctx.dev[id], sizeof(double) * g_ctx.count[id], hipMemcpyDeviceToHost, g_ctx.stream));
+    if (g_ctx.field[id].dev && g_ctx.host[id])
+      HIP_TRY(hipMemcpyAsync(g_ctx.host[id], g_ctx.field[id].dev, sizeof(double) * g_ctx.field[id].count, hipMemcpyDeviceToHost, g_ctx.stream));
   HIP_TRY(hipStreamSynchronize(g_ctx.stream));
   return 0;
 }
@@ -812,7 +438,7 @@ extern "C" int roms_hip_sync_all_to_host(void)
 extern "C" double *roms_hip_device_ptr(int id)
 {
   if (id < 0 || id >= FID_COUNT) return nullptr;
-  return g_ctx.dev[id];
+  return g_ctx.field[id].dev;
 }
 
 extern "C" int roms_hip_device_synchronize(void)
@@ -854,19 +480,18 @@ int roms_entry_check(const char *name)
   if ((g_ctx.p.point_sources & 3) && !roms_sources_given())
     return roms_fail(name, "point sources: LuvSrc / LwSrc is set but roms_hip_set_sources has not handed over SOURCES(ng)");
   for (int id = 0; id < FID_COUNT; id++)
-    if (!g_ctx.dev[id]) {
+    if (!g_ctx.field[id].dev) {
       double value;
       if (library_default(id, &value)) {
         const long want = roms_field_count(k_field_kind[id], g_ctx.b);
-        int rc = guarded_alloc(&g_ctx.dev[id], &g_ctx.dev_base[id], want);
+        int rc = guarded_alloc(&g_ctx.field[id], k_field_name[id], -1, want);
         if (rc) return rc;
         std::vector<double> fill((size_t)want, value);
         // on the library's (non-blocking) stream, behind guarded_alloc's memset of the same array
-        HIP_TRY(hipMemcpyAsync(g_ctx.dev[id], fill.data(), sizeof(double) * want, hipMemcpyHostToDevice, g_ctx.stream));
+        HIP_TRY(hipMemcpyAsync(g_ctx.field[id].dev, fill.data(), sizeof(double) * want, hipMemcpyHostToDevice, g_ctx.stream));
         HIP_TRY(hipStreamSynchronize(g_ctx.stream));
         g_ctx.host[id] = nullptr;
-        g_ctx.count[id] = want;
-        *(reinterpret_cast<double **>(&g_ctx.hostc.F) + id) = g_ctx.dev[id];
+        *(reinterpret_cast<double **>(&g_ctx.hostc.F) + id) = g_ctx.field[id].dev;
         g_ctx.devc_dirty = true;
         continue;
       }

@@ -583,13 +583,13 @@ int halo_allreduce_sum(double *A, long n)
 // trailing level when level > 0 and the field has time levels / tracers).
 extern "C" int roms_hip_exchange(int field_id, int level)
 {
-  if (!g_ctx.inited || field_id < 0 || field_id >= FID_COUNT || !g_ctx.dev[field_id])
+  if (!g_ctx.inited || field_id < 0 || field_id >= FID_COUNT || !g_ctx.field[field_id].dev)
     return roms_fail("roms_hip_exchange", "field not registered");
   int rc = roms_flush_consts();
   if (rc) return rc;
   const roms_bounds_t &b = g_ctx.b;
   const long nij = (long)(b.UBi - b.LBi + 1) * (long)(b.UBj - b.LBj + 1);
-  const int nk = (int)(g_ctx.count[field_id] / nij);
+  const int nk = (int)(g_ctx.field[field_id].count / nij);
   (void)level;
-  return halo_exchange3d(GT_R, nk, g_ctx.dev[field_id]);
+  return halo_exchange3d(GT_R, nk, g_ctx.field[field_id].dev);
 }

@@ -18,6 +18,39 @@
 #include "roms_dev.h"
 #include <algorithm>
 
+// ---- the lines of roms_avg.def and the library-owned arrays (roms_hip_set_averages below) ----
+struct AvgLine {
+  const char *name, *why;     // why != nullptr: not built
+  int gtype, shape, mask, range, expr, srcA, srcB, plane;
+  int counter;                // 0..3 = p, r, u, v counter; -1 = an average
+};
+struct AvgArray {
+  int id, itrc;               // line of the table, tracer (1-based; 0 = not per tracer)
+  int nk;                     // planes: 1, N or N+1
+  Guarded a;
+};
+#define ROMS_AVG_MAXARR (AVG_COUNT + ROMS_AVG_NTKINDS * ROMS_MAXNT)
+struct AvgStore {
+  int nAVG = 0, ntsAVG = 0, ntstart = 0, nrrec = 0;
+  int n = 0;
+  AvgArray arr[ROMS_AVG_MAXARR];
+  Guarded cnt[4];             // pmask_avg, rmask_avg, umask_avg, vmask_avg
+  long nij = 0;
+};
+enum { AVG_GT_r = GT_R, AVG_GT_u = GT_U, AVG_GT_v = GT_V, AVG_GT_w = GT_R, AVG_GT_p = GT_P };
+enum { AVG_CNT_p = 0, AVG_CNT_r, AVG_CNT_u, AVG_CNT_v };
+static const AvgLine k_avg_line[AVG_COUNT] = {
+#define ROMS_AVG(name, aout, grid, shape, mask, range, expr, srcA, srcB, plane)                                       \
+  {#name, nullptr, AVG_GT_##grid, shape, FID_##mask, range, expr, FID_##srcA, FID_##srcB, plane, -1},
+#define ROMS_AVG_NOT_BUILT(name, aout, why) {#name, #aout ": " #why, 0, 0, 0, 0, 0, 0, 0, 0, -1},
+#define ROMS_AVG_COUNTER(name, grid) {#name, nullptr, AVG_GT_##grid, AVS_2D, 0, 0, 0, 0, 0, 0, AVG_CNT_##grid},
+#include "roms_avg.def"
+#undef ROMS_AVG
+#undef ROMS_AVG_NOT_BUILT
+#undef ROMS_AVG_COUNTER
+};
+static AvgStore g_avg;
+
 namespace {
 
 const int k_kind[FID_COUNT] = {
@@ -130,7 +163,7 @@ const double *avg_source(int fid, const roms_step_idx_t *s, int itrc, int plane)
 {
   const roms_bounds_t &b = g_ctx.b;
   const long nij = (long)(b.UBi - b.LBi + 1) * (long)(b.UBj - b.LBj + 1);
-  const double *p = g_ctx.dev[fid];
+  const double *p = g_ctx.field[fid].dev;
   switch (k_kind[fid]) {
   case K_2D_T3: return p + (long)(s->kstp - 1) * nij;                                      // KOUT = kstp
   case K_3DR_T2: return p + (long)(s->nrhs - 1) * nij * b.N;                               // NOUT = nrhs
@@ -168,8 +201,8 @@ int avg_counters(int mode)
 {
   const roms_bounds_t &b = g_ctx.b;
   CntArgs c;
-  const double *full[4] = {g_ctx.dev[FID_pmask_full], g_ctx.dev[FID_rmask_full], g_ctx.dev[FID_umask_full],
-                           g_ctx.dev[FID_vmask_full]};
+  const double *full[4] = {g_ctx.field[FID_pmask_full].dev, g_ctx.field[FID_rmask_full].dev, g_ctx.field[FID_umask_full].dev,
+                           g_ctx.field[FID_vmask_full].dev};
   // p, r, u, v: set_avg.F:248-275 / :1272-1303; after the close set_masks.F:470-489
   const int i0[2][4] = {{b.Istr, b.IstrR, b.Istr, b.IstrR}, {b.IstrP, b.IstrT, b.IstrP, b.IstrT}};
   const int i1[2][4] = {{b.IendR, b.IendR, b.IendR, b.IendR}, {b.IendP, b.IendT, b.IendT, b.IendT}};
@@ -177,7 +210,7 @@ int avg_counters(int mode)
   const int j1[2][4] = {{b.JendR, b.JendR, b.JendR, b.JendR}, {b.JendP, b.JendT, b.JendT, b.JendT}};
   const int r = mode == 2;
   for (int q = 0; q < 4; q++) {
-    c.cnt[q] = g_avg.cnt[q];
+    c.cnt[q] = g_avg.cnt[q].dev;
     c.full[q] = full[q];
     // never outside the allocation, whatever the bounds say
     c.i0[q] = std::max(i0[r][q], b.LBi); c.i1[q] = std::min(i1[r][q], b.UBi);
@@ -194,7 +227,135 @@ int avg_counters(int mode)
 
 }  // namespace
 
-int roms_entry_check(const char *where);
+// row of AoutT of a per-tracer line = its rank among the AVS_NT lines of the table; -1 otherwise
+static int avg_tkind(int id)
+{
+  const AvgLine &L = k_avg_line[id];
+  if (L.why || L.counter >= 0 || L.shape != AVS_NT) return -1;
+  int r = 0;
+  for (int q = 0; q < id; q++)
+    if (!k_avg_line[q].why && k_avg_line[q].counter < 0 && k_avg_line[q].shape == AVS_NT) r++;
+  return r;
+}
+
+// (roms_hip_set_bounds: the averages have the old extents)
+void avg_release()
+{
+  for (int q = 0; q < g_avg.n; q++) guarded_free(&g_avg.arr[q].a);
+  for (int q = 0; q < 4; q++) guarded_free(&g_avg.cnt[q]);
+  g_avg = AvgStore{};
+}
+
+// The schedule of set_avg_tile and set_avg_masks, stated once (mirror: roms_trunk_mgh_amd/avg.py, phase()).
+extern "C" int roms_hip_avg_phase(int iic, int nAVG, int ntsAVG, int ntstart, int nrrec)
+{
+  if (nAVG <= 0) return 0;                                                    // set_avg.F:189
+  int ph = 0;
+  const bool restart = nrrec > 0 && iic == ntstart;
+  if ((iic > ntsAVG && (iic - 1) % nAVG == 1) || (iic >= ntsAVG && nAVG == 1) || restart) ph |= AVP_SET;   // :237-240
+  else if (iic > ntsAVG) ph |= AVP_ADD;                                                                    // :1264
+  const bool window_end = iic > ntsAVG && (iic - 1) % nAVG == 0 && !restart;
+  if (window_end || (iic >= ntsAVG && nAVG == 1)) ph |= AVP_CLOSE;                                         // :2298-2301
+  if (window_end) ph |= AVP_MASKS;                                                                // set_masks.F:466-468
+  return ph;
+}
+
+extern "C" int roms_hip_set_averages(int nAVG, int ntsAVG, int ntstart, int nrrec, const int *Aout, const int *AoutT)
+{
+  const char *me = "roms_hip_set_averages";
+  if (int rc = roms_setup_check(me)) return rc;
+  if (nAVG < 0) return roms_fail(me, "averages: nAVG < 0");
+  if (nAVG == 0) {
+    if (g_avg.n || g_avg.cnt[0].dev) HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+    avg_release();
+    return 0;
+  }
+  if (!Aout) return roms_fail(me, "averages: Aout is NULL");
+  const roms_bounds_t &b = g_ctx.b;
+  const long nij = (long)(b.UBi - b.LBi + 1) * (long)(b.UBj - b.LBj + 1);
+  // the selection; nothing is touched before all of it has been looked at
+  AvgStore want;
+  want.nAVG = nAVG; want.ntsAVG = ntsAVG; want.ntstart = ntstart; want.nrrec = nrrec; want.nij = nij;
+  for (int id = 0; id < AVG_COUNT; id++) {
+    const AvgLine &L = k_avg_line[id];
+    if (L.counter >= 0) continue;
+    const int tk = avg_tkind(id);
+    for (int it = (tk >= 0 ? 1 : 0); it <= (tk >= 0 ? b.NT : 0); it++) {
+      if (tk >= 0 ? !(AoutT && AoutT[tk * b.NT + it - 1]) : !Aout[id]) continue;
+      if (L.why) {
+        const std::string m = std::string("averages: ") + L.name + " is not built (" + L.why + ")";
+        return roms_fail(me, m.c_str());
+      }
+      for (int fid : {L.srcA, L.srcB, L.expr == X_WPMPN ? (int)FID_pm : L.srcA, L.expr == X_WPMPN ? (int)FID_pn : L.srcA})
+        if (!g_ctx.field[fid].dev) {
+          const std::string m = std::string("averages: ") + L.name + " reads " + k_field_name[fid] + ", which is not registered";
+          return roms_fail(me, m.c_str());
+        }
+      if (k_kind[L.srcA] == K_3DW_NAT && L.plane >= b.NAT) {
+        const std::string m = std::string("averages: ") + L.name + " reads tracer " + std::to_string(L.plane + 1) + " of " +
+                              k_field_name[L.srcA] + ", the tile has NAT = " + std::to_string(b.NAT);
+        return roms_fail(me, m.c_str());
+      }
+      if (k_kind[L.srcA] == K_2D_NT && L.plane >= b.NT) {
+        const std::string m = std::string("averages: ") + L.name + " reads tracer " + std::to_string(L.plane + 1) + " of " +
+                              k_field_name[L.srcA] + ", the tile has NT = " + std::to_string(b.NT);
+        return roms_fail(me, m.c_str());
+      }
+      AvgArray &a = want.arr[want.n++];
+      a.id = id; a.itrc = it;
+      a.nk = L.shape == AVS_2D ? 1 : L.shape == AVS_W ? b.N + 1 : b.N;
+    }
+  }
+  HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+  avg_release();
+  g_avg = want;
+  g_avg.n = 0;
+  for (int q = 0; q < want.n; q++) {                   // zero-filled, as the reference's allocation leaves them
+    AvgArray &a = g_avg.arr[q];
+    int rc = guarded_alloc(&a.a, k_avg_line[a.id].name, -1, nij * a.nk);
+    g_avg.n = q + 1;
+    if (rc) { avg_release(); return rc; }
+  }
+  if (g_ctx.p.wet_dry)
+    for (int q = 0; q < 4; q++) {
+      int rc = guarded_alloc(&g_avg.cnt[q], k_avg_line[AVG_pmask_avg + q].name, -1, nij);
+      if (rc) { avg_release(); return rc; }
+    }
+  HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+  return 0;
+}
+
+// the array of (avg_id, itrc): an average or a counter; nullptr if it is not there
+static const Guarded *avg_find(int id, int itrc)
+{
+  if (id < 0 || id >= AVG_COUNT) return nullptr;
+  const AvgLine &L = k_avg_line[id];
+  if (L.counter >= 0) return g_avg.cnt[L.counter].dev ? &g_avg.cnt[L.counter] : nullptr;
+  const int want = avg_tkind(id) >= 0 ? itrc : 0;
+  for (int q = 0; q < g_avg.n; q++)
+    if (g_avg.arr[q].id == id && g_avg.arr[q].itrc == want) return &g_avg.arr[q].a;
+  return nullptr;
+}
+
+extern "C" int roms_hip_get_average(int avg_id, int itrc, double *host, long n_doubles)
+{
+  const char *me = "roms_hip_get_average";
+  if (!g_ctx.inited) return roms_fail(me, "library not initialised");
+  if (avg_id < 0 || avg_id >= AVG_COUNT) return roms_fail(me, "averages: bad id");
+  const Guarded *a = avg_find(avg_id, itrc);
+  if (!a) {
+    const std::string m = std::string("averages: ") + k_avg_line[avg_id].name + " is not selected (roms_hip_set_averages)";
+    return roms_fail(me, m.c_str());
+  }
+  if (!host) return roms_fail(me, "averages: host array is NULL");
+  return roms_copy_out(me, "averages", k_avg_line[avg_id].name, a->dev, a->count, host, n_doubles);
+}
+
+extern "C" double *roms_hip_average_device_ptr(int avg_id, int itrc)
+{
+  const Guarded *a = g_ctx.inited ? avg_find(avg_id, itrc) : nullptr;
+  return a ? a->dev : nullptr;
+}
 
 extern "C" int roms_hip_set_avg(const roms_step_idx_t *s)
 {
@@ -209,7 +370,7 @@ extern "C" int roms_hip_set_avg(const roms_step_idx_t *s)
   if (s->kstp < 1 || s->kstp > 3 || s->nrhs < 1 || s->nrhs > 2) return roms_fail(me, "averages: kstp outside 1..3 or nrhs outside 1..2");
   const roms_bounds_t &b = g_ctx.b;
   const bool wet = g_ctx.p.wet_dry != 0;
-  if (wet && !g_avg.cnt[0])
+  if (wet && !g_avg.cnt[0].dev)
     return roms_fail(me, "averages: wet_dry was switched on after roms_hip_set_averages; call it again");
   const long ni = b.UBi - b.LBi + 1, nj = b.UBj - b.LBj + 1, nij = ni * nj;
   if (nij != g_avg.nij) return roms_fail(me, "averages: the arrays have other extents than the bounds");
@@ -224,7 +385,7 @@ extern "C" int roms_hip_set_avg(const roms_step_idx_t *s)
   for (int f0 = 0; f0 < g_avg.n; f0 += AVG_MAXDESC) {
     AvgArgs a;
     a.n = std::min(g_avg.n - f0, AVG_MAXDESC);
-    a.pm = g_ctx.dev[FID_pm]; a.pn = g_ctx.dev[FID_pn];
+    a.pm = g_ctx.field[FID_pm].dev; a.pn = g_ctx.field[FID_pn].dev;
     a.fac = 1.0 / (double)g_avg.nAVG;
     a.ni = ni; a.nij = nij; a.LBi = b.LBi; a.LBj = b.LBj;
     int nktot = 0;
@@ -232,11 +393,11 @@ extern "C" int roms_hip_set_avg(const roms_step_idx_t *s)
       const AvgArray &A = g_avg.arr[f0 + f];
       const AvgLine &L = k_avg_line[A.id];
       AvgDesc &d = a.d[f];
-      d.dst = A.dev;
+      d.dst = A.a.dev;
       d.a = avg_source(L.srcA, s, A.itrc, L.plane);
       d.b = avg_source(L.srcB, s, A.itrc, L.plane);
-      d.mask = wet ? g_ctx.dev[L.mask] : nullptr;
-      d.cnt = wet ? g_avg.cnt[L.mask == FID_rmask_full ? 1 : L.mask == FID_umask_full ? 2 : 3] : nullptr;
+      d.mask = wet ? g_ctx.field[L.mask].dev : nullptr;
+      d.cnt = wet ? g_avg.cnt[L.mask == FID_rmask_full ? 1 : L.mask == FID_umask_full ? 2 : 3].dev : nullptr;
       d.expr = L.expr;
       d.koff = nktot;
       avg_range(L.range, &d.i0, &d.i1, &d.j0, &d.j1);
@@ -255,7 +416,7 @@ extern "C" int roms_hip_set_avg(const roms_step_idx_t *s)
   // same after every field: exchange_*_tile, mp_exchange inside the same IF)
   if (close && (b.EWperiodic || b.NSperiodic) && g_avg.n) {
     halo_batch_begin();
-    for (int q = 0; q < g_avg.n; q++) halo_exchange3d(k_avg_line[g_avg.arr[q].id].gtype, g_avg.arr[q].nk, g_avg.arr[q].dev);
+    for (int q = 0; q < g_avg.n; q++) halo_exchange3d(k_avg_line[g_avg.arr[q].id].gtype, g_avg.arr[q].nk, g_avg.arr[q].a.dev);
     rc = halo_batch_end();
     if (rc) return rc;
   }
@@ -266,7 +427,7 @@ extern "C" int roms_hip_set_avg(const roms_step_idx_t *s)
     if (rc) return rc;
     const int gt[4] = {GT_P, GT_R, GT_U, GT_V};
     halo_batch_begin();
-    for (int q = 0; q < 4; q++) halo_exchange2d(gt[q], g_avg.cnt[q]);
+    for (int q = 0; q < 4; q++) halo_exchange2d(gt[q], g_avg.cnt[q].dev);
     rc = halo_batch_end();
     if (rc) return rc;
   }

@@ -6,8 +6,6 @@
 // wavefront is one contiguous 512-byte segment.
 #include "roms_dev.h"
 
-int roms_entry_check(const char *name);
-
 // Effective boundary-condition code (enum roms_lbc) of variable v (enum roms_lbc_var) on side sd.
 int lbc_code(const roms_params_t &p, int sd, int v)
 {
@@ -439,27 +437,27 @@ static bool needs_know(const BcArgs &a)
 
 int bc_zeta(int kout, const roms_step_idx_t *s)
 {
-  BcArgs a = bc_args(LBV_ZETA, g_ctx.dev[FID_zeta] + (long)(kout - 1) * nij_host(), 1);
+  BcArgs a = bc_args(LBV_ZETA, g_ctx.field[FID_zeta].dev + (long)(kout - 1) * nij_host(), 1);
   int know = kout; double dt2d = 0.0;
   if (s) bc_know(s, &know, &dt2d);
   else if (needs_know(a)) return roms_fail("bc_zeta", "this condition needs the barotropic time indices");
-  a.Xold = g_ctx.dev[FID_zeta] + (long)(know - 1) * nij_host();
-  a.D = g_ctx.dev[FID_zeta_bry];
+  a.Xold = g_ctx.field[FID_zeta].dev + (long)(know - 1) * nij_host();
+  a.D = g_ctx.field[FID_zeta_bry].dev;
   a.dt2d = dt2d;
   return edge_bc(a);
 }
 int bc_u2d(int kout, const roms_step_idx_t *s)
 {
-  BcArgs a = bc_args(LBV_UBAR, g_ctx.dev[FID_ubar] + (long)(kout - 1) * nij_host(), 1);
+  BcArgs a = bc_args(LBV_UBAR, g_ctx.field[FID_ubar].dev + (long)(kout - 1) * nij_host(), 1);
   int know = kout; double dt2d = 0.0;
   if (s) bc_know(s, &know, &dt2d);
   else if (needs_know(a)) return roms_fail("bc_u2d", "this condition needs the barotropic time indices");
-  a.Xold = g_ctx.dev[FID_ubar] + (long)(know - 1) * nij_host();
-  a.D = g_ctx.dev[FID_ubar_bry];
-  a.Z = g_ctx.dev[FID_zeta] + (long)(know - 1) * nij_host();
-  a.Zb = g_ctx.dev[FID_zeta_bry];
-  a.Zn = g_ctx.dev[FID_zeta] + (long)(kout - 1) * nij_host();
-  a.T = g_ctx.dev[FID_vbar] + (long)(know - 1) * nij_host();
+  a.Xold = g_ctx.field[FID_ubar].dev + (long)(know - 1) * nij_host();
+  a.D = g_ctx.field[FID_ubar_bry].dev;
+  a.Z = g_ctx.field[FID_zeta].dev + (long)(know - 1) * nij_host();
+  a.Zb = g_ctx.field[FID_zeta_bry].dev;
+  a.Zn = g_ctx.field[FID_zeta].dev + (long)(kout - 1) * nij_host();
+  a.T = g_ctx.field[FID_vbar].dev + (long)(know - 1) * nij_host();
   a.ssh_only = g_ctx.hostc.tides.ssh_only;
   bc_acquire(a);
   a.dt2d = dt2d;
@@ -467,16 +465,16 @@ int bc_u2d(int kout, const roms_step_idx_t *s)
 }
 int bc_v2d(int kout, const roms_step_idx_t *s)
 {
-  BcArgs a = bc_args(LBV_VBAR, g_ctx.dev[FID_vbar] + (long)(kout - 1) * nij_host(), 1);
+  BcArgs a = bc_args(LBV_VBAR, g_ctx.field[FID_vbar].dev + (long)(kout - 1) * nij_host(), 1);
   int know = kout; double dt2d = 0.0;
   if (s) bc_know(s, &know, &dt2d);
   else if (needs_know(a)) return roms_fail("bc_v2d", "this condition needs the barotropic time indices");
-  a.Xold = g_ctx.dev[FID_vbar] + (long)(know - 1) * nij_host();
-  a.D = g_ctx.dev[FID_vbar_bry];
-  a.Zn = g_ctx.dev[FID_zeta] + (long)(kout - 1) * nij_host();
-  a.Z = g_ctx.dev[FID_zeta] + (long)(know - 1) * nij_host();
-  a.Zb = g_ctx.dev[FID_zeta_bry];
-  a.T = g_ctx.dev[FID_ubar] + (long)(know - 1) * nij_host();
+  a.Xold = g_ctx.field[FID_vbar].dev + (long)(know - 1) * nij_host();
+  a.D = g_ctx.field[FID_vbar_bry].dev;
+  a.Zn = g_ctx.field[FID_zeta].dev + (long)(kout - 1) * nij_host();
+  a.Z = g_ctx.field[FID_zeta].dev + (long)(know - 1) * nij_host();
+  a.Zb = g_ctx.field[FID_zeta_bry].dev;
+  a.T = g_ctx.field[FID_ubar].dev + (long)(know - 1) * nij_host();
   a.ssh_only = g_ctx.hostc.tides.ssh_only;
   bc_acquire(a);
   a.dt2d = dt2d;
@@ -485,25 +483,25 @@ int bc_v2d(int kout, const roms_step_idx_t *s)
 int bc_u3d(int nout, int nstp)
 {
   const long n3r = nij_host() * g_ctx.b.N;
-  BcArgs a = bc_args(LBV_U, g_ctx.dev[FID_u] + (long)(nout - 1) * n3r, g_ctx.b.N);
-  a.Xold = g_ctx.dev[FID_u] + (long)(nstp - 1) * n3r;
-  a.D = g_ctx.dev[FID_u_bry];
+  BcArgs a = bc_args(LBV_U, g_ctx.field[FID_u].dev + (long)(nout - 1) * n3r, g_ctx.b.N);
+  a.Xold = g_ctx.field[FID_u].dev + (long)(nstp - 1) * n3r;
+  a.D = g_ctx.field[FID_u_bry].dev;
   return edge_bc(a);
 }
 int bc_v3d(int nout, int nstp)
 {
   const long n3r = nij_host() * g_ctx.b.N;
-  BcArgs a = bc_args(LBV_V, g_ctx.dev[FID_v] + (long)(nout - 1) * n3r, g_ctx.b.N);
-  a.Xold = g_ctx.dev[FID_v] + (long)(nstp - 1) * n3r;
-  a.D = g_ctx.dev[FID_v_bry];
+  BcArgs a = bc_args(LBV_V, g_ctx.field[FID_v].dev + (long)(nout - 1) * n3r, g_ctx.b.N);
+  a.Xold = g_ctx.field[FID_v].dev + (long)(nstp - 1) * n3r;
+  a.D = g_ctx.field[FID_v_bry].dev;
   return edge_bc(a);
 }
 int bc_t3d(int nout, int itrc, int nstp)
 {
   const long n3r = nij_host() * g_ctx.b.N;
-  BcArgs a = bc_args(LBV_T, g_ctx.dev[FID_t] + ((long)(nout - 1) + 3L * (itrc - 1)) * n3r, g_ctx.b.N);
-  a.Xold = g_ctx.dev[FID_t] + ((long)(nstp - 1) + 3L * (itrc - 1)) * n3r;
-  a.D = g_ctx.dev[FID_t_bry] + (long)(itrc - 1) * n3r;
+  BcArgs a = bc_args(LBV_T, g_ctx.field[FID_t].dev + ((long)(nout - 1) + 3L * (itrc - 1)) * n3r, g_ctx.b.N);
+  a.Xold = g_ctx.field[FID_t].dev + ((long)(nstp - 1) + 3L * (itrc - 1)) * n3r;
+  a.D = g_ctx.field[FID_t_bry].dev + (long)(itrc - 1) * n3r;
   // the compact index the callers of t3dbc_tile count (step3d_t.F:1551-1560, pre_step3d.F:1126-1130, ini_fields.F:602-607)
   const int ic = g_ctx.hostc.clima.ic[itrc - 1];
   if (ic > 0) a.C = g_ctx.hostc.clima.Tnudgcof + (long)(ic - 1) * n3r;
@@ -551,8 +549,8 @@ extern "C" int roms_hip_set_massflux(const roms_step_idx_t *s)
   hipLaunchKernelGGL(k_set_massflux, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs);
   KERNEL_CHECK("k_set_massflux");
   halo_batch_begin();
-  halo_exchange3d(GT_U, b.N, g_ctx.dev[FID_Huon]);
-  halo_exchange3d(GT_V, b.N, g_ctx.dev[FID_Hvom]);
+  halo_exchange3d(GT_U, b.N, g_ctx.field[FID_Huon].dev);
+  halo_exchange3d(GT_V, b.N, g_ctx.field[FID_Hvom].dev);
   return halo_batch_end();
 }
 
@@ -639,7 +637,7 @@ extern "C" int roms_hip_omega(const roms_step_idx_t *s)
     hipLaunchKernelGGL(k_src_omega, dim3((g_ctx.hostc.src.n + 63) / 64), dim3(64), 0, g_ctx.stream, g_ctx.devc);
     KERNEL_CHECK("k_src_omega");
   }
-  return bc_w3d(g_ctx.dev[FID_W]);
+  return bc_w3d(g_ctx.field[FID_W].dev);
 }
 
 // ---------------------------------------------------------------------------
@@ -668,7 +666,7 @@ extern "C" int roms_hip_set_zeta(const roms_step_idx_t *s)
                      g_ctx.stream, g_ctx.devc);
   KERNEL_CHECK("k_set_zeta");
   // both time levels travel in one exchange (mp_exchange2d Nvar=2, set_zeta.F:118)
-  return halo_exchange3d(GT_R, 2, g_ctx.dev[FID_zeta]);
+  return halo_exchange3d(GT_R, 2, g_ctx.field[FID_zeta].dev);
 }
 
 // ---------------------------------------------------------------------------
@@ -736,9 +734,9 @@ extern "C" int roms_hip_set_depth(const roms_step_idx_t *s)
                      g_ctx.stream, g_ctx.devc);
   KERNEL_CHECK("k_set_depth");
   halo_batch_begin();
-  halo_exchange2d(GT_R, g_ctx.dev[FID_h]);
-  halo_exchange3d(GT_R, b.N + 1, g_ctx.dev[FID_z_w]);
-  halo_exchange3d(GT_R, b.N, g_ctx.dev[FID_z_r]);
-  halo_exchange3d(GT_R, b.N, g_ctx.dev[FID_Hz]);
+  halo_exchange2d(GT_R, g_ctx.field[FID_h].dev);
+  halo_exchange3d(GT_R, b.N + 1, g_ctx.field[FID_z_w].dev);
+  halo_exchange3d(GT_R, b.N, g_ctx.field[FID_z_r].dev);
+  halo_exchange3d(GT_R, b.N, g_ctx.field[FID_Hz].dev);
   return halo_batch_end();
 }

@@ -6,8 +6,6 @@
 #include "roms_dev.h"
 #include "bio_sink.h"
 
-int roms_entry_check(const char *name);
-
 namespace {
 
 // Positive-definite concentrations, npzd_Powell.h:237-251 for one time level: v = the four pools in the order of idbio.
@@ -172,6 +170,7 @@ const char *const k_bio_name[] = {"NONE", "NPZD_POWELL", "NPZD_FRANKS", "NPZD_IR
 
 }  // namespace
 
+// (roms_hip_set_bounds: the tracer indices of the biology setting belong to the old NT)
 void bio_release()
 {
   g_ctx.hostc.bio = RomsBio{};
@@ -181,8 +180,7 @@ void bio_release()
 extern "C" int roms_hip_set_biology(int model, const void *par, long nbytes)
 {
   const char *me = "roms_hip_set_biology";
-  if (!g_ctx.inited || !g_ctx.have_bounds || !g_ctx.have_params)
-    return roms_fail(me, "roms_hip_init, roms_hip_set_bounds and roms_hip_set_params come first");
+  if (int rc = roms_setup_check(me)) return rc;
   char msg[200];
   if (model < ROMS_BIO_NONE || model > ROMS_BIO_RED_TIDE) {
     snprintf(msg, sizeof msg, "biology: unknown model %d", model);

@@ -9,8 +9,6 @@
 // mp_reduce2 MAXLOC; diag.F:398-420) stays with the caller.
 #include "roms_dev.h"
 
-int roms_entry_check(const char *name);
-
 namespace {
 
 // ---------------------------------------------------------------------------------------------------
@@ -284,8 +282,8 @@ extern "C" int roms_hip_wvelocity(const roms_step_idx_t *s)
   if (b.N < 3) return roms_fail("roms_hip_wvelocity", "needs N >= 3");
   // wvelocity.F:119-135: the exchanges of DU_avg1, DV_avg1 come first (intent inout there as well)
   halo_batch_begin();
-  halo_exchange2d(GT_U, g_ctx.dev[FID_DU_avg1]);
-  halo_exchange2d(GT_V, g_ctx.dev[FID_DV_avg1]);
+  halo_exchange2d(GT_U, g_ctx.field[FID_DU_avg1].dev);
+  halo_exchange2d(GT_V, g_ctx.field[FID_DV_avg1].dev);
   if ((rc = halo_batch_end())) return rc;
   {
     ScopedTimer tm("wvelocity");
@@ -293,7 +291,7 @@ extern "C" int roms_hip_wvelocity(const roms_step_idx_t *s)
                        g_ctx.devc, s->nstp);
     KERNEL_CHECK("k_wvelocity");
   }
-  return bc_w3d(g_ctx.dev[FID_wvel]);       // bc_w3d_tile + exchange, :237-250
+  return bc_w3d(g_ctx.field[FID_wvel].dev);       // bc_w3d_tile + exchange, :237-250
 }
 
 extern "C" int roms_hip_diag(const roms_step_idx_t *s, double *out12)

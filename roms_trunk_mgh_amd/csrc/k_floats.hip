@@ -18,8 +18,6 @@
 #include "roms_dev.h"
 #include <vector>
 
-int roms_entry_check(const char *where);
-
 namespace {
 // mod_floats.F:80-90 (1-based rows of track) and :125-127
 enum { itstr = 0, ixgrd = 1, iygrd = 2, izgrd = 3, iflon = 4, iflat = 5, idpth = 6, ixrhs = 7, iyrhs = 8, izrhs = 9, ifden = 10 };
@@ -448,6 +446,7 @@ __global__ void __launch_bounds__(64) k_floats_bounded(const double *__restrict_
 }
 
 // ------------------------------------------------------------------------------------------------ the C ABI --
+// (roms_hip_set_bounds: the floats' coordinate arrays have the old extents)
 void floats_release()
 {
   if (g_flt.trk) (void)hipFree(g_flt.trk);
@@ -464,8 +463,7 @@ extern "C" int roms_hip_set_floats(int Nfloats, const int *Ftype, const double *
                                    const double *xcoord, const double *ycoord)
 {
   const char *me = "roms_hip_set_floats";
-  if (!g_ctx.inited || !g_ctx.have_bounds || !g_ctx.have_params)
-    return roms_fail(me, "roms_hip_init, roms_hip_set_bounds and roms_hip_set_params come first");
+  if (int rc = roms_setup_check(me)) return rc;
   if (Nfloats < 0) return roms_fail(me, "floats: Nfloats < 0");
   if (Nfloats == 0) {
     if (g_flt.n) HIP_TRY(hipStreamSynchronize(g_ctx.stream));

@@ -22,8 +22,6 @@
 #include "roms_dev.h"
 #include "gls.h"
 
-int roms_entry_check(const char *name);
-
 namespace {
 
 struct GlsConst {            // initialize_scalars, mod_scalars.F:1686-1712, :1756-1768, :4450-4490
@@ -663,8 +661,8 @@ extern "C" int roms_hip_gls_prestep(const roms_step_idx_t *s)
   KERNEL_CHECK("k_gls_prestep");
   if ((rc = tke_bc(3))) return rc;
   halo_batch_begin();
-  halo_exchange3d(GT_R, b.N + 1, g_ctx.dev[FID_tke] + 2L * n3w);
-  halo_exchange3d(GT_R, b.N + 1, g_ctx.dev[FID_gls] + 2L * n3w);
+  halo_exchange3d(GT_R, b.N + 1, g_ctx.field[FID_tke].dev + 2L * n3w);
+  halo_exchange3d(GT_R, b.N + 1, g_ctx.field[FID_gls].dev + 2L * n3w);
   return halo_batch_end();
 }
 
@@ -701,9 +699,9 @@ extern "C" int roms_hip_gls_corstep(const roms_step_idx_t *s)
   }
   if ((rc = tke_bc(s->nnew))) return rc;
   halo_batch_begin();
-  halo_exchange3d(GT_R, b.N + 1, g_ctx.dev[FID_tke] + (long)(s->nnew - 1) * n3w);
-  halo_exchange3d(GT_R, b.N + 1, g_ctx.dev[FID_gls] + (long)(s->nnew - 1) * n3w);
-  halo_exchange3d(GT_R, b.N + 1, g_ctx.dev[FID_Akv]);
-  for (int it = 0; it < b.NAT; it++) halo_exchange3d(GT_R, b.N + 1, g_ctx.dev[FID_Akt] + (long)it * n3w);
+  halo_exchange3d(GT_R, b.N + 1, g_ctx.field[FID_tke].dev + (long)(s->nnew - 1) * n3w);
+  halo_exchange3d(GT_R, b.N + 1, g_ctx.field[FID_gls].dev + (long)(s->nnew - 1) * n3w);
+  halo_exchange3d(GT_R, b.N + 1, g_ctx.field[FID_Akv].dev);
+  for (int it = 0; it < b.NAT; it++) halo_exchange3d(GT_R, b.N + 1, g_ctx.field[FID_Akt].dev + (long)it * n3w);
   return halo_batch_end();
 }

@@ -5,8 +5,6 @@
 // WET_DRY.  Run once per simulation: plain kernels, one thread per column.
 #include "roms_dev.h"
 
-int roms_entry_check(const char *name);
-
 namespace {
 
 struct IniArgs { int kstp, knew, nstp, nnew, i0, i1, j0, j1; };
@@ -155,12 +153,12 @@ extern "C" int roms_hip_ini_zeta(const roms_step_idx_t *s)
     if ((rc = bc_zeta(s->knew, s))) return rc;
   }
   halo_batch_begin();
-  halo_exchange2d(GT_R, g_ctx.dev[FID_zeta] + (long)(s->kstp - 1) * nij);
-  if (s->knew != s->kstp) halo_exchange2d(GT_R, g_ctx.dev[FID_zeta] + (long)(s->knew - 1) * nij);
+  halo_exchange2d(GT_R, g_ctx.field[FID_zeta].dev + (long)(s->kstp - 1) * nij);
+  if (s->knew != s->kstp) halo_exchange2d(GT_R, g_ctx.field[FID_zeta].dev + (long)(s->knew - 1) * nij);
   if ((rc = halo_batch_end())) return rc;
   hipLaunchKernelGGL(k_ini_zavg, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, a);
   KERNEL_CHECK("k_ini_zavg");
-  return halo_exchange2d(GT_R, g_ctx.dev[FID_Zt_avg1]);
+  return halo_exchange2d(GT_R, g_ctx.field[FID_Zt_avg1].dev);
 }
 
 extern "C" int roms_hip_ini_fields(const roms_step_idx_t *s)
@@ -174,7 +172,7 @@ extern "C" int roms_hip_ini_fields(const roms_step_idx_t *s)
   const long nij = (long)(b.UBi - b.LBi + 1) * (long)(b.UBj - b.LBj + 1), n3r = nij * b.N;
   const IniArgs a = ini_args(s);
   const dim3 grid = grid2d(b.IendB - b.IstrB + 1, b.JendB - b.JstrB + 1);
-  double *u = g_ctx.dev[FID_u], *v = g_ctx.dev[FID_v], *t = g_ctx.dev[FID_t];
+  double *u = g_ctx.field[FID_u].dev, *v = g_ctx.field[FID_v].dev, *t = g_ctx.field[FID_t].dev;
   hipLaunchKernelGGL(k_ini_3d, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, a);
   KERNEL_CHECK("k_ini_3d");
   // u3dbc / v3dbc on both levels (:322-343), t3dbc per tracer (:626-637); the conditions of different variables
@@ -205,11 +203,11 @@ extern "C" int roms_hip_ini_fields(const roms_step_idx_t *s)
     if ((rc = bc_u2d(s->knew, s)) || (rc = bc_v2d(s->knew, s))) return rc;
   }
   halo_batch_begin();
-  halo_exchange2d(GT_U, g_ctx.dev[FID_ubar] + (long)(s->kstp - 1) * nij);
-  halo_exchange2d(GT_V, g_ctx.dev[FID_vbar] + (long)(s->kstp - 1) * nij);
+  halo_exchange2d(GT_U, g_ctx.field[FID_ubar].dev + (long)(s->kstp - 1) * nij);
+  halo_exchange2d(GT_V, g_ctx.field[FID_vbar].dev + (long)(s->kstp - 1) * nij);
   if (s->knew != s->kstp) {
-    halo_exchange2d(GT_U, g_ctx.dev[FID_ubar] + (long)(s->knew - 1) * nij);
-    halo_exchange2d(GT_V, g_ctx.dev[FID_vbar] + (long)(s->knew - 1) * nij);
+    halo_exchange2d(GT_U, g_ctx.field[FID_ubar].dev + (long)(s->knew - 1) * nij);
+    halo_exchange2d(GT_V, g_ctx.field[FID_vbar].dev + (long)(s->knew - 1) * nij);
   }
   return halo_batch_end();
 }

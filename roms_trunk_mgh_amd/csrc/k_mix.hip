@@ -19,8 +19,6 @@
 #include "advect.h"
 #include "tmix.h"
 
-int roms_entry_check(const char *name);
-
 namespace {
 
 // MODE 0: t3dmix2_geo (all tracers of the launch).  MODE 1 / 2: first / second operator of t3dmix4_geo for tracer

@@ -18,8 +18,6 @@
 #include <cstdlib>
 #include "roms_dev.h"
 
-int roms_entry_check(const char *name);
-
 namespace {
 
 #define EPS_MP  1.0E-18
@@ -820,7 +818,7 @@ int roms_launch_step3d_t_mpdata(int nnew, int itrc0, int n)
     // three-point footprint: refresh the ghost points of t(nnew) first, step3d_t.F:369-386
     halo_batch_begin();
     for (int q = 0; q < nb; q++)
-      halo_exchange3d(GT_R, b.N, g_ctx.dev[FID_t] + ((long)(nnew - 1) + 3L * (itrc0 + q0 + q - 1)) * n3r);
+      halo_exchange3d(GT_R, b.N, g_ctx.field[FID_t].dev + ((long)(nnew - 1) + 3L * (itrc0 + q0 + q - 1)) * n3r);
     if ((rc = halo_batch_end())) return rc;
     m.itrc = itrc0 + q0;
     m.nb = nb;

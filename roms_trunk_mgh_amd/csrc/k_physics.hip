@@ -9,8 +9,6 @@
 #include "roms_dev.h"
 #include <cmath>
 
-int roms_entry_check(const char *name);
-
 namespace {
 
 __global__ void __launch_bounds__(BLK_X *BLK_Y)
@@ -362,13 +360,13 @@ extern "C" int roms_hip_set_vbc(const roms_step_idx_t *s)
     // closed-wall rule of an E-W periodic channel on its own rows; everything else -- western / eastern edges,
     // corners, open edges (zero gradient), the mask of the wall points -- through the generic edge kernel
     if (!b.EWperiodic || g_ctx.p.masking || !lbc2d_all_closed()) {
-      if ((rc = bc_generic(LBV_UBAR, LBV_UBAR, g_ctx.dev[FID_bustr], 1))) return rc;
-      if ((rc = bc_generic(LBV_VBAR, LBV_VBAR, g_ctx.dev[FID_bvstr], 1))) return rc;
+      if ((rc = bc_generic(LBV_UBAR, LBV_UBAR, g_ctx.field[FID_bustr].dev, 1))) return rc;
+      if ((rc = bc_generic(LBV_VBAR, LBV_VBAR, g_ctx.field[FID_bvstr].dev, 1))) return rc;
     }
   }
   halo_batch_begin();
-  halo_exchange2d(GT_U, g_ctx.dev[FID_bustr]);
-  halo_exchange2d(GT_V, g_ctx.dev[FID_bvstr]);
+  halo_exchange2d(GT_U, g_ctx.field[FID_bustr].dev);
+  halo_exchange2d(GT_V, g_ctx.field[FID_bvstr].dev);
   return halo_batch_end();
 }
 
@@ -389,16 +387,16 @@ extern "C" int roms_hip_bulk_flux(const roms_step_idx_t *s)
     KERNEL_CHECK("k_bulk_stress");
   }
   halo_batch_begin();
-  halo_exchange2d(GT_R, g_ctx.dev[FID_lrflx]);
-  halo_exchange2d(GT_R, g_ctx.dev[FID_lhflx]);
-  halo_exchange2d(GT_R, g_ctx.dev[FID_shflx]);
-  halo_exchange2d(GT_R, g_ctx.dev[FID_stflux]);        // first plane = itemp
+  halo_exchange2d(GT_R, g_ctx.field[FID_lrflx].dev);
+  halo_exchange2d(GT_R, g_ctx.field[FID_lhflx].dev);
+  halo_exchange2d(GT_R, g_ctx.field[FID_shflx].dev);
+  halo_exchange2d(GT_R, g_ctx.field[FID_stflux].dev);        // first plane = itemp
   if (g_ctx.p.eminusp) {                               // bulk_flux.F:945-952
-    halo_exchange2d(GT_R, g_ctx.dev[FID_evap]);
-    halo_exchange2d(GT_R, g_ctx.dev[FID_stflux] + (long)(g_ctx.b.UBi - g_ctx.b.LBi + 1) * (g_ctx.b.UBj - g_ctx.b.LBj + 1));
+    halo_exchange2d(GT_R, g_ctx.field[FID_evap].dev);
+    halo_exchange2d(GT_R, g_ctx.field[FID_stflux].dev + (long)(g_ctx.b.UBi - g_ctx.b.LBi + 1) * (g_ctx.b.UBj - g_ctx.b.LBj + 1));
   }
-  halo_exchange2d(GT_U, g_ctx.dev[FID_sustr]);
-  halo_exchange2d(GT_V, g_ctx.dev[FID_svstr]);
+  halo_exchange2d(GT_U, g_ctx.field[FID_sustr].dev);
+  halo_exchange2d(GT_V, g_ctx.field[FID_svstr].dev);
   return halo_batch_end();
 }
 
@@ -1079,38 +1077,27 @@ __global__ void k_lmd_edges(const RomsDev *__restrict__ c, int phase)
 namespace {
 const char *const k_kpp_name[3] = {"hbbl", "kbbl", "ksbl"};
 struct KppStore {
-  double *dev[3] = {nullptr, nullptr, nullptr}, *base[3] = {nullptr, nullptr, nullptr};
-  long count[3] = {0, 0, 0};                                     // doubles of the allocation (two ints per double)
+  Guarded a[3];                                                  // (count: doubles of the allocation, two ints per double)
   long nij = 0;
 } g_kpp;
 }  // namespace
 
+// (roms_hip_set_bounds: hbbl, kbbl, ksbl of the bottom boundary layer have the old extents)
 void kpp_release()
 {
-  for (int q = 0; q < 3; q++) {
-    guarded_free(&g_kpp.dev[q], &g_kpp.base[q]);
-    g_kpp.count[q] = 0;
-  }
+  for (int q = 0; q < 3; q++) guarded_free(&g_kpp.a[q]);
   g_kpp.nij = 0;
   g_ctx.hostc.kpp = RomsKpp{};
   g_ctx.devc_dirty = true;
 }
 
-int kpp_arrays(const char *name[3], const double *base[3], long count[3])
-{
-  if (!g_kpp.dev[0]) return 0;
-  for (int q = 0; q < 3; q++) { name[q] = k_kpp_name[q]; base[q] = g_kpp.base[q]; count[q] = g_kpp.count[q]; }
-  return 3;
-}
-
 extern "C" int roms_hip_set_kpp(int lmd_bkpp, const double *hbbl)
 {
   const char *me = "roms_hip_set_kpp";
-  if (!g_ctx.inited || !g_ctx.have_bounds || !g_ctx.have_params)
-    return roms_fail(me, "roms_hip_init, roms_hip_set_bounds and roms_hip_set_params come first");
+  if (int rc = roms_setup_check(me)) return rc;
   if (lmd_bkpp != 0 && lmd_bkpp != 1) return roms_fail(me, "kpp: lmd_bkpp is 0 or 1");
   if (lmd_bkpp == 0) {
-    if (g_kpp.dev[0]) HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+    if (g_kpp.a[0].dev) HIP_TRY(hipStreamSynchronize(g_ctx.stream));
     kpp_release();
     return 0;
   }
@@ -1118,25 +1105,24 @@ extern "C" int roms_hip_set_kpp(int lmd_bkpp, const double *hbbl)
   if (b.NAT < 2 || !g_ctx.p.salinity) return roms_fail(me, "kpp: LMD_BKPP is built for the SALINITY set-up (NAT = 2)");
   const long nij = (long)(b.UBi - b.LBi + 1) * (long)(b.UBj - b.LBj + 1);
   HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-  if (!g_kpp.dev[0]) {
+  if (!g_kpp.a[0].dev) {
     const long n[3] = {nij, (nij + 1) / 2, (nij + 1) / 2};
     for (int q = 0; q < 3; q++) {
-      int rc = guarded_alloc(&g_kpp.dev[q], &g_kpp.base[q], n[q]);
+      int rc = guarded_alloc(&g_kpp.a[q], k_kpp_name[q], -1, n[q]);
       if (rc) { kpp_release(); return rc; }
-      g_kpp.count[q] = n[q];
     }
     g_kpp.nij = nij;
   }
   // hbbl of the restart file, or zero as mod_mixing.F leaves it; kbbl and ksbl are outputs and start at zero
-  if (hbbl) HIP_TRY(hipMemcpyAsync(g_kpp.dev[0], hbbl, sizeof(double) * nij, hipMemcpyHostToDevice, g_ctx.stream));
-  else HIP_TRY(hipMemsetAsync(g_kpp.dev[0], 0, sizeof(double) * nij, g_ctx.stream));
-  for (int q = 1; q < 3; q++) HIP_TRY(hipMemsetAsync(g_kpp.dev[q], 0, sizeof(double) * g_kpp.count[q], g_ctx.stream));
+  if (hbbl) HIP_TRY(hipMemcpyAsync(g_kpp.a[0].dev, hbbl, sizeof(double) * nij, hipMemcpyHostToDevice, g_ctx.stream));
+  else HIP_TRY(hipMemsetAsync(g_kpp.a[0].dev, 0, sizeof(double) * nij, g_ctx.stream));
+  for (int q = 1; q < 3; q++) HIP_TRY(hipMemsetAsync(g_kpp.a[q].dev, 0, sizeof(double) * g_kpp.a[q].count, g_ctx.stream));
   HIP_TRY(hipStreamSynchronize(g_ctx.stream));
   RomsKpp &K = g_ctx.hostc.kpp;
   K.bkpp = 1;
-  K.hbbl = g_kpp.dev[0];
-  K.kbbl = reinterpret_cast<int *>(g_kpp.dev[1]);
-  K.ksbl = reinterpret_cast<int *>(g_kpp.dev[2]);
+  K.hbbl = g_kpp.a[0].dev;
+  K.kbbl = reinterpret_cast<int *>(g_kpp.a[1].dev);
+  K.ksbl = reinterpret_cast<int *>(g_kpp.a[2].dev);
   g_ctx.devc_dirty = true;
   return 0;
 }
@@ -1148,15 +1134,8 @@ extern "C" int roms_hip_get_kpp(const char *name, void *host, long n)
   if (!name || !host) return roms_fail(me, "kpp: null argument");
   for (int q = 0; q < 3; q++) {
     if (strcmp(name, k_kpp_name[q])) continue;
-    if (!g_kpp.dev[q]) return roms_fail(me, "kpp: LMD_BKPP is not switched on (roms_hip_set_kpp)");
-    if (n != g_kpp.nij) {
-      char msg[200];
-      snprintf(msg, sizeof msg, "kpp: %s has %ld elements, the host array %ld", name, g_kpp.nij, n);
-      return roms_fail(me, msg);
-    }
-    HIP_TRY(hipMemcpyAsync(host, g_kpp.dev[q], (q == 0 ? sizeof(double) : sizeof(int)) * n, hipMemcpyDeviceToHost, g_ctx.stream));
-    HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-    return 0;
+    if (!g_kpp.a[q].dev) return roms_fail(me, "kpp: LMD_BKPP is not switched on (roms_hip_set_kpp)");
+    return roms_copy_out(me, "kpp", name, g_kpp.a[q].dev, g_kpp.nij, host, n, q == 0 ? sizeof(double) : sizeof(int), "elements");
   }
   return roms_fail(me, (std::string("kpp: unknown array ") + name).c_str());
 }
@@ -1209,14 +1188,14 @@ extern "C" int roms_hip_lmd_vmix(const roms_step_idx_t *s)
   }
   // bc_r2d_tile(hsbl) (the kernel wrote the wall rows of a channel; western / eastern edges and corners through the
   // generic edge kernel) + exchange; bc_w3d_tile(Akv), bc_w3d_tile(Akt(:,:,:,itrc)): wall rows + exchange
-  if (!b.EWperiodic && (rc = bc_generic(LBV_ZETA, LBV_ZETA, g_ctx.dev[FID_hsbl], 1))) return rc;
-  if ((rc = halo_exchange2d(GT_R, g_ctx.dev[FID_hsbl]))) return rc;
+  if (!b.EWperiodic && (rc = bc_generic(LBV_ZETA, LBV_ZETA, g_ctx.field[FID_hsbl].dev, 1))) return rc;
+  if ((rc = halo_exchange2d(GT_R, g_ctx.field[FID_hsbl].dev))) return rc;
   if (bkpp) {                                                    // bc_r2d_tile(hbbl) + exchange, lmd_bkpp.F:577-586
-    if (!b.EWperiodic && (rc = bc_generic(LBV_ZETA, LBV_ZETA, g_kpp.dev[0], 1))) return rc;
-    if ((rc = halo_exchange2d(GT_R, g_kpp.dev[0]))) return rc;
+    if (!b.EWperiodic && (rc = bc_generic(LBV_ZETA, LBV_ZETA, g_kpp.a[0].dev, 1))) return rc;
+    if ((rc = halo_exchange2d(GT_R, g_kpp.a[0].dev))) return rc;
   }
-  if ((rc = bc_w3d(g_ctx.dev[FID_Akv]))) return rc;
+  if ((rc = bc_w3d(g_ctx.field[FID_Akv].dev))) return rc;
   for (int it = 0; it < b.NAT; it++)
-    if ((rc = bc_w3d(g_ctx.dev[FID_Akt] + (long)it * n3w))) return rc;
+    if ((rc = bc_w3d(g_ctx.field[FID_Akt].dev + (long)it * n3w))) return rc;
   return 0;
 }

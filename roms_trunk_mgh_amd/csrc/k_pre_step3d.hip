@@ -19,8 +19,6 @@
 #include "roms_dev.h"
 #include "advect.h"
 
-int roms_entry_check(const char *name);
-
 namespace {
 
 // MASK: MASKING applications, first differences times umask / vmask of their face (pre_step3d.F:398, :463)
@@ -304,7 +302,7 @@ static int pre_step3d_tracers(const roms_step_idx_t *s, bool fused)
   for (int it = 1; it <= b.NT; it++)
     if ((rc = bc_t3d(3, it, s->nstp))) return rc;
   halo_batch_begin();
-  for (int it = 1; it <= b.NT; it++) halo_exchange3d(GT_R, b.N, g_ctx.dev[FID_t] + (2L + 3L * (it - 1)) * n3r);
+  for (int it = 1; it <= b.NT; it++) halo_exchange3d(GT_R, b.N, g_ctx.field[FID_t].dev + (2L + 3L * (it - 1)) * n3r);
   return halo_batch_end();
 }
 

@@ -12,8 +12,6 @@
 // momentum start inside (roms_hip_rhs3d): + u, v(nstp), ru, rv of both levels read, u, v(nnew) written = 13 passes.
 #include "roms_dev.h"
 
-int roms_entry_check(const char *name);
-
 namespace {
 
 __device__ __forceinline__ double harm(double a, double bq, double eps)

@@ -10,8 +10,6 @@
 #include "roms_dev.h"
 #include "roms_eoscoef.h"
 
-int roms_entry_check(const char *name);
-
 namespace {
 
 struct EosPt {
@@ -184,14 +182,14 @@ extern "C" int roms_hip_rho_eos(const roms_step_idx_t *s)
     hipLaunchKernelGGL(k_rho_eos_lin, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs);
   KERNEL_CHECK("k_rho_eos");
   halo_batch_begin();
-  halo_exchange3d(GT_R, b.N, g_ctx.dev[FID_rho]);
-  halo_exchange3d(GT_R, b.N, g_ctx.dev[FID_pden]);
-  halo_exchange2d(GT_R, g_ctx.dev[FID_rhoA]);
-  halo_exchange2d(GT_R, g_ctx.dev[FID_rhoS]);
+  halo_exchange3d(GT_R, b.N, g_ctx.field[FID_rho].dev);
+  halo_exchange3d(GT_R, b.N, g_ctx.field[FID_pden].dev);
+  halo_exchange2d(GT_R, g_ctx.field[FID_rhoA].dev);
+  halo_exchange2d(GT_R, g_ctx.field[FID_rhoS].dev);
   if (g_ctx.p.nonlin_eos) {
-    halo_exchange2d(GT_R, g_ctx.dev[FID_alpha]);
-    halo_exchange2d(GT_R, g_ctx.dev[FID_beta]);
-    halo_exchange3d(GT_R, b.N + 1, g_ctx.dev[FID_bvf]);
+    halo_exchange2d(GT_R, g_ctx.field[FID_alpha].dev);
+    halo_exchange2d(GT_R, g_ctx.field[FID_beta].dev);
+    halo_exchange3d(GT_R, b.N + 1, g_ctx.field[FID_bvf].dev);
   }
   return halo_batch_end();
 }

@@ -427,8 +427,6 @@ k_rhs3d_vspline(const RomsDev *__restrict__ c, int nrhs)
 
 }  // namespace
 
-int roms_entry_check(const char *name);
-
 // roms_params_t.uv_adv: 0, or one of the six scheme pairs the reference can be compiled to (roms_hip.h)
 int roms_uv_adv_check(const char *where)
 {

@@ -77,6 +77,7 @@ void tab_release()
 }
 }  // namespace
 
+// (roms_hip_set_bounds: the records of set_data have the old extents)
 void data_release()
 {
   for (DataRec &r : g_recs)
@@ -212,8 +213,7 @@ double *clima_copy(int target, int index)
 // edge target on a side that is not a physical edge of this tile.
 int data_validate(const char *me, int target, int index, int side, int slot, bool point, long *n, bool *skip)
 {
-  if (!g_ctx.inited || !g_ctx.have_bounds || !g_ctx.have_params)
-    return roms_fail(me, "roms_hip_init, roms_hip_set_bounds and roms_hip_set_params come first");
+  if (int rc = roms_setup_check(me)) return rc;
   if (target < 0 || target >= DATA_COUNT) return roms_fail(me, "set_data: unknown target (enum roms_data_id)");
   const DataLine &T = k_data_line[target];
   const roms_bounds_t &b = g_ctx.b;
@@ -235,7 +235,7 @@ int data_validate(const char *me, int target, int index, int side, int slot, boo
   if (T.dest == DD_CLIMA && !clima_copy(target, index))
     return fail(std::string("the library has no device copy of it") + (T.shape == DS_NC ? " for ic = " + std::to_string(index) : std::string()) +
                 ": hand the climatology over with roms_hip_set_clima first (its switch is off)");
-  if ((T.dest == DD_FIELD || T.dest == DD_BRY) && !g_ctx.dev[T.fid]) return fail("the field is not registered");
+  if ((T.dest == DD_FIELD || T.dest == DD_BRY) && !g_ctx.field[T.fid].dev) return fail("the field is not registered");
   if (is_edge_shape(T.shape)) {
     const bool edge = side == LBS_WEST ? b.west_edge : side == LBS_EAST ? b.east_edge : side == LBS_SOUTH ? b.south_edge : b.north_edge;
     const bool periodic = side <= LBS_EAST ? b.EWperiodic : b.NSperiodic;
@@ -332,8 +332,7 @@ extern "C" int roms_hip_set_data_point(int target, int index, int slot, double T
 extern "C" int roms_hip_set_data(double time, double dt, int *synchro)
 {
   const char *me = "roms_hip_set_data";
-  if (!g_ctx.inited || !g_ctx.have_bounds || !g_ctx.have_params)
-    return roms_fail(me, "roms_hip_init, roms_hip_set_bounds and roms_hip_set_params come first");
+  if (int rc = roms_setup_check(me)) return rc;
   if (synchro) *synchro = 0;
   if (g_recs.empty()) return 0;
   const roms_bounds_t &b = g_ctx.b;
@@ -369,7 +368,7 @@ extern "C" int roms_hip_set_data(double time, double dt, int *synchro)
       if (!(base = clima_copy(r.target, r.index)))
         return fail("the library has no device copy of it any more: hand the climatology over with roms_hip_set_clima");
     } else {
-      if (!(base = g_ctx.dev[T.fid])) return fail("the field is not registered");
+      if (!(base = g_ctx.field[T.fid].dev)) return fail("the field is not registered");
       if (T.shape == DS_2DT) base += (long)(r.index - 1) * nij;
       if (T.shape == DS_ENT) base += (long)(r.index - 1) * nij * N;
       if (TD.ntc > 0 && TD.add_fs && r.target == DATA_zeta_bry) base = const_cast<double *>(TD.zeta_base);
@@ -421,8 +420,8 @@ extern "C" int roms_hip_set_data(double time, double dt, int *synchro)
       d.dstep = we ? ni : 1;
       d.s1 = s1 ? s1 + (a0 - lb) : nullptr; d.s2 = s2 ? s2 + (a0 - lb) : nullptr; d.dst = base + o;
       if (p.wet_dry && r.target == DATA_zeta_bry) {                      // set_data.F:928-1003
-        if (!g_ctx.dev[FID_h]) return fail("wet_dry: field not registered: h");
-        d.hclip = g_ctx.dev[FID_h] + o;
+        if (!g_ctx.field[FID_h].dev) return fail("wet_dry: field not registered: h");
+        d.hclip = g_ctx.field[FID_h].dev + o;
         d.dcrit = p.Dcrit;
         d.clip0 = (we ? b.JstrR : b.IstrR) - a0;
         d.clip1 = (we ? b.JendR : b.IendR) - a0;

@@ -11,18 +11,13 @@
 #include "roms_dev.h"
 #include <algorithm>
 
-int roms_entry_check(const char *name);
-
 namespace {
 
 struct DiaStore {
   int nDIA = 0, ntsDIA = 0, ntstart = 0, nrrec = 0;
   int ndt = 0, NT = 0, N = 0;
   long nij = 0;
-  double *wrk = nullptr, *wrk_base = nullptr;        // DiaTwrk
-  double *trc = nullptr, *trc_base = nullptr;        // DiaTrc
-  double *zeta = nullptr, *zeta_base = nullptr;      // avgzeta
-  double *cnt = nullptr, *cnt_base = nullptr;        // rmask_dia (wet_dry)
+  Guarded wrk, trc, zeta, cnt;                       // DiaTwrk, DiaTrc, avgzeta, rmask_dia (wet_dry)
 } g_dia;
 
 const int k_dia_group[DIA_COUNT] = {
@@ -133,12 +128,10 @@ extern "C" int roms_hip_dia_index(int dia_id, int hdif, int rotated)
   return dia_id < DIA_COUNT ? n + 1 : n;
 }
 
+// (roms_hip_set_bounds: the tracer diagnostics have the old extents)
 void dia_release()
 {
-  guarded_free(&g_dia.wrk, &g_dia.wrk_base);
-  guarded_free(&g_dia.trc, &g_dia.trc_base);
-  guarded_free(&g_dia.zeta, &g_dia.zeta_base);
-  guarded_free(&g_dia.cnt, &g_dia.cnt_base);
+  for (Guarded *a : {&g_dia.wrk, &g_dia.trc, &g_dia.zeta, &g_dia.cnt}) guarded_free(a);
   g_dia = DiaStore{};
   if (g_ctx.hostc.dia.wrk) {
     memset(&g_ctx.hostc.dia, 0, sizeof g_ctx.hostc.dia);
@@ -146,18 +139,7 @@ void dia_release()
   }
 }
 
-bool dia_on() { return g_dia.wrk != nullptr; }
-
-int dia_arrays(const char *name[4], const double *base[4], long count[4])
-{
-  if (!dia_on()) return 0;
-  const long n4 = g_dia.nij * g_dia.N * g_dia.NT * g_dia.ndt;
-  name[0] = "DiaTwrk"; base[0] = g_dia.wrk_base; count[0] = n4;
-  name[1] = "DiaTrc"; base[1] = g_dia.trc_base; count[1] = n4;
-  name[2] = "avgzeta (diagnostics)"; base[2] = g_dia.zeta_base; count[2] = g_dia.nij;
-  name[3] = "rmask_dia"; base[3] = g_dia.cnt_base; count[3] = g_dia.nij;      // (no base without wet_dry: skipped)
-  return 4;
-}
+bool dia_on() { return g_dia.wrk.dev != nullptr; }
 
 int dia_check(const char *where)
 {
@@ -184,8 +166,7 @@ int dia_rate(int nnew)
 extern "C" int roms_hip_set_diagnostics(int nDIA, int ntsDIA, int ntstart, int nrrec)
 {
   const char *me = "roms_hip_set_diagnostics";
-  if (!g_ctx.inited || !g_ctx.have_bounds || !g_ctx.have_params)
-    return roms_fail(me, "roms_hip_init, roms_hip_set_bounds and roms_hip_set_params come first");
+  if (int rc = roms_setup_check(me)) return rc;
   if (nDIA < 0) return roms_fail(me, "diagnostics: nDIA < 0");
   if (nDIA == 0) {                                        // set_diags.F:113
     if (dia_on()) HIP_TRY(hipStreamSynchronize(g_ctx.stream));
@@ -203,14 +184,14 @@ extern "C" int roms_hip_set_diagnostics(int nDIA, int ntsDIA, int ntstart, int n
   g_dia.ndt = roms_hip_dia_index(DIA_COUNT, p.ts_dif2, 0);
   g_dia.NT = b.NT; g_dia.N = b.N; g_dia.nij = nij;
   const long n4 = nij * b.N * b.NT * g_dia.ndt;
-  int rc = guarded_alloc(&g_dia.wrk, &g_dia.wrk_base, n4);      // zeroed, as mod_diags.F allocates them
-  if (!rc) rc = guarded_alloc(&g_dia.trc, &g_dia.trc_base, n4);
-  if (!rc) rc = guarded_alloc(&g_dia.zeta, &g_dia.zeta_base, nij);
-  if (!rc && p.wet_dry) rc = guarded_alloc(&g_dia.cnt, &g_dia.cnt_base, nij);
+  int rc = guarded_alloc(&g_dia.wrk, "DiaTwrk", -1, n4);      // zeroed, as mod_diags.F allocates them
+  if (!rc) rc = guarded_alloc(&g_dia.trc, "DiaTrc", -1, n4);
+  if (!rc) rc = guarded_alloc(&g_dia.zeta, "avgzeta (diagnostics)", -1, nij);
+  if (!rc && p.wet_dry) rc = guarded_alloc(&g_dia.cnt, "rmask_dia", -1, nij);
   if (rc) { dia_release(); return rc; }
   HIP_TRY(hipStreamSynchronize(g_ctx.stream));
   RomsDia &d = g_ctx.hostc.dia;
-  d.wrk = g_dia.wrk;
+  d.wrk = g_dia.wrk.dev;
   d.ndt = g_dia.ndt;
   for (int id = 0; id < DIA_COUNT; id++) d.ix[id] = roms_hip_dia_index(id, p.ts_dif2, 0) - 1;
   g_ctx.devc_dirty = true;
@@ -234,14 +215,14 @@ extern "C" int roms_hip_set_diags(const roms_step_idx_t *s)
   const bool wet = g_ctx.p.wet_dry != 0;
   const long ni = b.UBi - b.LBi + 1, nij = ni * (long)(b.UBj - b.LBj + 1);
   if (nij != g_dia.nij || b.N != g_dia.N || b.NT != g_dia.NT) return roms_fail(me, "diagnostics: the arrays have other extents than the bounds");
-  if (wet && !g_dia.cnt) return roms_fail(me, "diagnostics: wet_dry was switched on after roms_hip_set_diagnostics; call it again");
-  if (!g_ctx.dev[FID_zeta]) return roms_fail(me, "diagnostics: zeta is not registered");
-  if (wet && !g_ctx.dev[FID_rmask_full]) return roms_fail(me, "diagnostics: rmask_full is not registered");
+  if (wet && !g_dia.cnt.dev) return roms_fail(me, "diagnostics: wet_dry was switched on after roms_hip_set_diagnostics; call it again");
+  if (!g_ctx.field[FID_zeta].dev) return roms_fail(me, "diagnostics: zeta is not registered");
+  if (wet && !g_ctx.field[FID_rmask_full].dev) return roms_fail(me, "diagnostics: rmask_full is not registered");
   ScopedTimer tm("set_diags");
   DiaArgs a;
-  a.wrk = g_dia.wrk; a.trc = g_dia.trc; a.avgzeta = g_dia.zeta; a.cnt = g_dia.cnt;
-  a.zeta = g_ctx.dev[FID_zeta] + (long)(s->kstp - 1) * nij;          // KOUT = kstp
-  a.full = wet ? g_ctx.dev[FID_rmask_full] : nullptr;
+  a.wrk = g_dia.wrk.dev; a.trc = g_dia.trc.dev; a.avgzeta = g_dia.zeta.dev; a.cnt = g_dia.cnt.dev;
+  a.zeta = g_ctx.field[FID_zeta].dev + (long)(s->kstp - 1) * nij;          // KOUT = kstp
+  a.full = wet ? g_ctx.field[FID_rmask_full].dev : nullptr;
   a.ni = ni; a.nij = nij; a.LBi = b.LBi; a.LBj = b.LBj;
   a.nplanes = g_dia.ndt * b.NT * b.N;
   // never outside the allocation, whatever the bounds say
@@ -269,10 +250,10 @@ extern "C" int roms_hip_get_diagnostic(int dia_id, int itrc, int accumulated, do
   if (!dia_on()) return roms_fail(me, "diagnostics: not switched on (roms_hip_set_diagnostics)");
   const double *src;
   long n;
-  if (dia_id == DIA_avgzeta) { src = g_dia.zeta; n = g_dia.nij; }
+  if (dia_id == DIA_avgzeta) { src = g_dia.zeta.dev; n = g_dia.nij; }
   else if (dia_id == DIA_rmask_dia) {
-    if (!g_dia.cnt) return roms_fail(me, "diagnostics: rmask_dia exists with wet_dry only");
-    src = g_dia.cnt; n = g_dia.nij;
+    if (!g_dia.cnt.dev) return roms_fail(me, "diagnostics: rmask_dia exists with wet_dry only");
+    src = g_dia.cnt.dev; n = g_dia.nij;
   } else {
     const int ix = g_ctx.hostc.dia.ix[dia_id];
     if (ix < 0) {
@@ -282,15 +263,8 @@ extern "C" int roms_hip_get_diagnostic(int dia_id, int itrc, int accumulated, do
     }
     if (itrc < 1 || itrc > g_dia.NT) return roms_fail(me, "diagnostics: itrc outside 1..NT");
     n = g_dia.nij * g_dia.N;
-    src = (accumulated ? g_dia.trc : g_dia.wrk) + ((long)ix * g_dia.NT + (itrc - 1)) * n;
+    src = (accumulated ? g_dia.trc : g_dia.wrk).dev + ((long)ix * g_dia.NT + (itrc - 1)) * n;
   }
   if (!host) return roms_fail(me, "diagnostics: host array is NULL");
-  if (n_doubles != n) {
-    char msg[200];
-    snprintf(msg, sizeof msg, "diagnostics: %s has %ld doubles, the host array %ld", k_dia_name[dia_id], n, n_doubles);
-    return roms_fail(me, msg);
-  }
-  HIP_TRY(hipMemcpyAsync(host, src, sizeof(double) * n, hipMemcpyDeviceToHost, g_ctx.stream));
-  HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-  return 0;
+  return roms_copy_out(me, "diagnostics", k_dia_name[dia_id], src, n, host, n_doubles);
 }

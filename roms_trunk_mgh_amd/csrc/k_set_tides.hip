@@ -21,8 +21,6 @@
 #include "roms_dev.h"
 #include <vector>
 
-int roms_entry_check(const char *name);
-
 namespace {
 enum { TS_amp = 0, TS_eph, TS_ang, TS_uph, TS_maj, TS_mnr, TS_angler, TS_rmask, TS_umask, TS_vmask, TS_zbase, TS_ubase,
        TS_vbase, TS_COUNT };
@@ -31,6 +29,7 @@ struct TidesStore {
 } g_tides;
 }  // namespace
 
+// (roms_hip_set_bounds: the tidal strips have the old extents)
 void tides_release()
 {
   for (int q = 0; q < TS_COUNT; q++) {
@@ -153,8 +152,7 @@ extern "C" int roms_hip_set_tides(int NTC, int MTC, const double *Tperiod, const
                                   const double *ubar_base, const double *vbar_base)
 {
   const char *me = "roms_hip_set_tides";
-  if (!g_ctx.inited || !g_ctx.have_bounds || !g_ctx.have_params)
-    return roms_fail(me, "roms_hip_init, roms_hip_set_bounds and roms_hip_set_params come first");
+  if (int rc = roms_setup_check(me)) return rc;
   if (NTC < 0) return roms_fail(me, "tides: NTC < 0");
   if (NTC > MTC) return roms_fail(me, "tides: NTC > MTC");
   if (NTC > ROMS_MAXTC) return roms_fail(me, "tides: NTC > ROMS_MAXTC constituents");
@@ -184,7 +182,7 @@ extern "C" int roms_hip_set_tides(int NTC, int MTC, const double *Tperiod, const
   const roms_bounds_t &b = g_ctx.b;
   if (b.NSperiodic) return roms_fail(me, "tides: N-S periodic grids are not implemented on this path");
   const bool masked = g_ctx.p.masking != 0;
-  if (masked && !(g_ctx.dev[FID_rmask] && g_ctx.dev[FID_umask] && g_ctx.dev[FID_vmask]))
+  if (masked && !(g_ctx.field[FID_rmask].dev && g_ctx.field[FID_umask].dev && g_ctx.field[FID_vmask].dev))
     return roms_fail(me, "tides: masking = 1 but rmask, umask, vmask are not registered yet");
   const long ni = b.UBi - b.LBi + 1, nj = b.UBj - b.LBj + 1, nij = ni * nj;
 
@@ -255,7 +253,7 @@ extern "C" int roms_hip_set_tides(int NTC, int MTC, const double *Tperiod, const
     std::vector<double> plane((size_t)nij);
     const int fid[3] = {FID_rmask, FID_umask, FID_vmask};
     for (int q = 0; q < 3; q++) {
-      TIDES_TRY(hipMemcpy(plane.data(), g_ctx.dev[fid[q]], sizeof(double) * nij, hipMemcpyDeviceToHost));
+      TIDES_TRY(hipMemcpy(plane.data(), g_ctx.field[fid[q]].dev, sizeof(double) * nij, hipMemcpyDeviceToHost));
       const long n = q == 0 ? tot : tot / 2;
       if (q == 0) gather_rho(plane.data());
       else gather_line(plane.data(), q == 1 ? ul : vl);

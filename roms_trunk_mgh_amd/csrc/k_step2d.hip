@@ -18,7 +18,6 @@
 #include <cstdlib>
 #include <map>
 
-int roms_entry_check(const char *name);
 int roms_launch_step2d_visc4(int krhs);      // k_uv3dmix2.hip
 int roms_uv_adv_check(const char *where);    // k_rhs3d.hip
 
@@ -189,16 +188,16 @@ static int wetdry_launch(int mode, int first, int kstp)
                      g_ctx.devc, mode, first, kstp);
   KERNEL_CHECK("k2d_wetdry");
   halo_batch_begin();
-  halo_exchange2d(GT_P, g_ctx.dev[FID_pmask_wet]);
-  halo_exchange2d(GT_R, g_ctx.dev[FID_rmask_wet]);
-  halo_exchange2d(GT_U, g_ctx.dev[FID_umask_wet]);
-  halo_exchange2d(GT_V, g_ctx.dev[FID_vmask_wet]);
-  if (mode == 0) halo_exchange2d(GT_R, g_ctx.dev[FID_rmask_wet_avg]);
+  halo_exchange2d(GT_P, g_ctx.field[FID_pmask_wet].dev);
+  halo_exchange2d(GT_R, g_ctx.field[FID_rmask_wet].dev);
+  halo_exchange2d(GT_U, g_ctx.field[FID_umask_wet].dev);
+  halo_exchange2d(GT_V, g_ctx.field[FID_vmask_wet].dev);
+  if (mode == 0) halo_exchange2d(GT_R, g_ctx.field[FID_rmask_wet_avg].dev);
   else {
-    halo_exchange2d(GT_P, g_ctx.dev[FID_pmask_full]);
-    halo_exchange2d(GT_R, g_ctx.dev[FID_rmask_full]);
-    halo_exchange2d(GT_U, g_ctx.dev[FID_umask_full]);
-    halo_exchange2d(GT_V, g_ctx.dev[FID_vmask_full]);
+    halo_exchange2d(GT_P, g_ctx.field[FID_pmask_full].dev);
+    halo_exchange2d(GT_R, g_ctx.field[FID_rmask_full].dev);
+    halo_exchange2d(GT_U, g_ctx.field[FID_umask_full].dev);
+    halo_exchange2d(GT_V, g_ctx.field[FID_vmask_full].dev);
   }
   return halo_batch_end();
 }
@@ -278,9 +277,9 @@ int step2d_impl(const roms_step_idx_t *si, bool in_loop)
                        g_ctx.devc, s);
     KERNEL_CHECK("k2d_avg_last");
     if (s.predictor) {
-      if ((rc = halo_exchange2d(GT_R, g_ctx.dev[FID_Zt_avg1]))) return rc;
-      if ((rc = halo_exchange2d(GT_U, g_ctx.dev[FID_DU_avg1]))) return rc;
-      if ((rc = halo_exchange2d(GT_V, g_ctx.dev[FID_DV_avg1]))) return rc;
+      if ((rc = halo_exchange2d(GT_R, g_ctx.field[FID_Zt_avg1].dev))) return rc;
+      if ((rc = halo_exchange2d(GT_U, g_ctx.field[FID_DU_avg1].dev))) return rc;
+      if ((rc = halo_exchange2d(GT_V, g_ctx.field[FID_DV_avg1].dev))) return rc;
     }
     return 0;
   }
@@ -307,10 +306,10 @@ int step2d_impl(const roms_step_idx_t *si, bool in_loop)
     // ONE compute launch + ONE exchange per call
     if ((rc = roms_launch_k2d_mom_lds(s, K2dLaunch::FusedTiles, DUon, DVom, nullptr, nullptr, DUnext, DVnext))) return rc;
     halo_batch_begin();
-    if (s.predictor) halo_exchange2d(GT_R, g_ctx.dev[FID_rzeta] + (long)(s.krhs - 1) * nij);
-    halo_exchange2d(GT_R, g_ctx.dev[FID_zeta] + (long)(s.knew - 1) * nij);
-    halo_exchange2d(GT_U, g_ctx.dev[FID_ubar] + (long)(s.knew - 1) * nij);
-    halo_exchange2d(GT_V, g_ctx.dev[FID_vbar] + (long)(s.knew - 1) * nij);
+    if (s.predictor) halo_exchange2d(GT_R, g_ctx.field[FID_rzeta].dev + (long)(s.krhs - 1) * nij);
+    halo_exchange2d(GT_R, g_ctx.field[FID_zeta].dev + (long)(s.knew - 1) * nij);
+    halo_exchange2d(GT_U, g_ctx.field[FID_ubar].dev + (long)(s.knew - 1) * nij);
+    halo_exchange2d(GT_V, g_ctx.field[FID_vbar].dev + (long)(s.knew - 1) * nij);
     halo_exchange2d(GT_U, DUnext);
     halo_exchange2d(GT_V, DVnext);
     if ((rc = halo_batch_end())) return rc;
@@ -325,9 +324,9 @@ int step2d_impl(const roms_step_idx_t *si, bool in_loop)
   KERNEL_CHECK("k2d_zeta");
   if (s.iif == p.nfast + 1 && s.predictor) {
     halo_batch_begin();
-    halo_exchange2d(GT_R, g_ctx.dev[FID_Zt_avg1]);
-    halo_exchange2d(GT_U, g_ctx.dev[FID_DU_avg1]);
-    halo_exchange2d(GT_V, g_ctx.dev[FID_DV_avg1]);
+    halo_exchange2d(GT_R, g_ctx.field[FID_Zt_avg1].dev);
+    halo_exchange2d(GT_U, g_ctx.field[FID_DU_avg1].dev);
+    halo_exchange2d(GT_V, g_ctx.field[FID_DV_avg1].dev);
     if ((rc = halo_batch_end())) return rc;
   }
   // WET_DRY: the new wet/dry masks, :729-749 (after the averages and their exchange, before the return below)
@@ -347,10 +346,10 @@ int step2d_impl(const roms_step_idx_t *si, bool in_loop)
     KERNEL_CHECK("k2d_src_bar");
   }
   halo_batch_begin();
-  if (s.predictor) halo_exchange2d(GT_R, g_ctx.dev[FID_rzeta] + (long)(s.krhs - 1) * nij);
-  halo_exchange2d(GT_R, g_ctx.dev[FID_zeta] + (long)(s.knew - 1) * nij);
-  halo_exchange2d(GT_U, g_ctx.dev[FID_ubar] + (long)(s.knew - 1) * nij);
-  halo_exchange2d(GT_V, g_ctx.dev[FID_vbar] + (long)(s.knew - 1) * nij);
+  if (s.predictor) halo_exchange2d(GT_R, g_ctx.field[FID_rzeta].dev + (long)(s.krhs - 1) * nij);
+  halo_exchange2d(GT_R, g_ctx.field[FID_zeta].dev + (long)(s.knew - 1) * nij);
+  halo_exchange2d(GT_U, g_ctx.field[FID_ubar].dev + (long)(s.knew - 1) * nij);
+  halo_exchange2d(GT_V, g_ctx.field[FID_vbar].dev + (long)(s.knew - 1) * nij);
   return halo_batch_end();
 }
 

@@ -24,7 +24,6 @@
 #include "roms_dev.h"
 #include <cstdlib>
 
-int roms_entry_check(const char *name);
 int roms_launch_step3d_t_mpdata(int nnew, int itrc0, int n);         // k_mpdata.hip
 
 #include "advect.h"
@@ -571,7 +570,7 @@ extern "C" int roms_hip_step3d_t(const roms_step_idx_t *s)
         const long n3r_ = (long)(b.UBi - b.LBi + 1) * (b.UBj - b.LBj + 1) * b.N;
         halo_batch_begin();
         for (int q = 0; q < n; q++)
-          halo_exchange3d(GT_R, b.N, g_ctx.dev[FID_t] + ((long)(s->nnew - 1) + 3L * (it + q - 1)) * n3r_);
+          halo_exchange3d(GT_R, b.N, g_ctx.field[FID_t].dev + ((long)(s->nnew - 1) + 3L * (it + q - 1)) * n3r_);
         if ((rc = halo_batch_end())) return rc;
         rc = launch_hsimt<ADV_HSIMT>(s->nnew, it, n);
         break;
@@ -605,6 +604,6 @@ extern "C" int roms_hip_step3d_t(const roms_step_idx_t *s)
   const long n3r = (long)(b.UBi - b.LBi + 1) * (b.UBj - b.LBj + 1) * b.N;
   halo_batch_begin();
   for (int it = 1; it <= b.NT; it++)
-    halo_exchange3d(GT_R, b.N, g_ctx.dev[FID_t] + ((long)(s->nnew - 1) + 3L * (it - 1)) * n3r);
+    halo_exchange3d(GT_R, b.N, g_ctx.field[FID_t].dev + ((long)(s->nnew - 1) + 3L * (it - 1)) * n3r);
   return halo_batch_end();
 }

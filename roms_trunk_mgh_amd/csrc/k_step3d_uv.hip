@@ -20,8 +20,6 @@
 // Huon,Hvom = 12 passes.
 #include "roms_dev.h"
 
-int roms_entry_check(const char *name);
-
 namespace {
 
 // uv_column: rows per segment of the Thomas re-run, and levels the first sweep requests ahead
@@ -546,11 +544,11 @@ extern "C" int roms_hip_step3d_uv(const roms_step_idx_t *s)
   const long nij = (long)(b.UBi - b.LBi + 1) * (b.UBj - b.LBj + 1);
   const long n3r = nij * b.N;
   halo_batch_begin();
-  halo_exchange3d(GT_U, b.N, g_ctx.dev[FID_u] + (long)(s->nnew - 1) * n3r);
-  halo_exchange3d(GT_V, b.N, g_ctx.dev[FID_v] + (long)(s->nnew - 1) * n3r);
-  halo_exchange3d(GT_U, b.N, g_ctx.dev[FID_Huon]);
-  halo_exchange3d(GT_V, b.N, g_ctx.dev[FID_Hvom]);
-  halo_exchange3d(GT_U, 2, g_ctx.dev[FID_ubar]);
-  halo_exchange3d(GT_V, 2, g_ctx.dev[FID_vbar]);
+  halo_exchange3d(GT_U, b.N, g_ctx.field[FID_u].dev + (long)(s->nnew - 1) * n3r);
+  halo_exchange3d(GT_V, b.N, g_ctx.field[FID_v].dev + (long)(s->nnew - 1) * n3r);
+  halo_exchange3d(GT_U, b.N, g_ctx.field[FID_Huon].dev);
+  halo_exchange3d(GT_V, b.N, g_ctx.field[FID_Hvom].dev);
+  halo_exchange3d(GT_U, 2, g_ctx.field[FID_ubar].dev);
+  halo_exchange3d(GT_V, 2, g_ctx.field[FID_vbar].dev);
   return halo_batch_end();
 }

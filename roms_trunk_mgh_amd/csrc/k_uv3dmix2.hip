@@ -365,8 +365,6 @@ int roms_launch_step2d_visc4(int krhs)
   return 0;
 }
 
-int roms_entry_check(const char *name);
-
 extern "C" int roms_hip_uv3dmix2(const roms_step_idx_t *s)
 {
   int rc = roms_entry_check("roms_hip_uv3dmix2");

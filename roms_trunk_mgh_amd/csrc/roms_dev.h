@@ -74,32 +74,21 @@ struct RomsTides {
   const double *zeta_base, *ubar_base, *vbar_base;   // [nij] sub-tidal boundary data of the ADD options
 };
 
-// AVERAGES (roms_hip_set_averages, roms_hip_set_avg): the columns of include/roms_avg.def and the library-owned arrays.
+// One device array between two guard bands (guarded_alloc, capi.hip): dev = the array the kernels see, base = the start
+// of the allocation (the band in front of dev; nullptr = not allocated), count = its doubles.  name is a static string
+// and q the index of an indexed scratch array (ws3[q], ws2[q]), -1 otherwise: what roms_hip_check_guards reports.
+struct Guarded {
+  double *dev = nullptr, *base = nullptr;
+  long count = 0;
+  const char *name = nullptr;
+  int q = -1;
+};
+
+// AVERAGES (roms_hip_set_averages, roms_hip_set_avg; k_avg.hip): the columns of include/roms_avg.def.
 enum { AVS_2D = 0, AVS_N, AVS_W, AVS_NT };
 enum { RNG_RR = 0, RNG_UR, RNG_VR, RNG_II, RNG_UI, RNG_VI };
 enum { X_COPY = 0, X_SQ, X_WPMPN, X_UV, X_UT, X_VT };
 enum { AVP_SET = 1, AVP_ADD = 2, AVP_CLOSE = 4, AVP_MASKS = 8 };      // roms_hip_avg_phase
-struct AvgLine {
-  const char *name, *why;     // why != nullptr: not built
-  int gtype, shape, mask, range, expr, srcA, srcB, plane;
-  int counter;                // 0..3 = p, r, u, v counter; -1 = an average
-};
-extern const AvgLine k_avg_line[AVG_COUNT];
-struct AvgArray {
-  int id, itrc;               // line of the table, tracer (1-based; 0 = not per tracer)
-  int nk;                     // planes: 1, N or N+1
-  long count;
-  double *dev, *base;
-};
-#define ROMS_AVG_MAXARR (AVG_COUNT + ROMS_AVG_NTKINDS * ROMS_MAXNT)
-struct AvgStore {
-  int nAVG = 0, ntsAVG = 0, ntstart = 0, nrrec = 0;
-  int n = 0;
-  AvgArray arr[ROMS_AVG_MAXARR];
-  double *cnt[4] = {nullptr, nullptr, nullptr, nullptr}, *cnt_base[4] = {nullptr, nullptr, nullptr, nullptr};   // pmask_avg, rmask_avg, umask_avg, vmask_avg
-  long nij = 0;
-};
-extern AvgStore g_avg;
 
 // DIAGNOSTICS_TS (roms_hip_set_diagnostics, k_set_diags.hip): DiaTwrk(LBi:UBi, LBj:UBj, N, NT, NDT) of mod_diags.F on
 // the device, plane-major like the tracer itself (consecutive lanes along i store consecutive doubles of one term's
@@ -153,11 +142,8 @@ struct RomsCtx {
   roms_params_t p{};
   bool have_bounds = false, have_params = false;
   double *host[FID_COUNT] = {nullptr};
-  double *dev[FID_COUNT] = {nullptr};
-  double *dev_base[FID_COUNT] = {nullptr};   // start of the allocation (guard band in front of dev[])
-  long count[FID_COUNT] = {0};
-  double *ws3_base[ROMS_NWS3] = {nullptr};
-  double *ws2_base[32] = {nullptr};
+  Guarded field[FID_COUNT];     // the device mirrors
+  Guarded ws3[ROMS_NWS3], ws2[32];   // the scratch arrays behind hostc.ws3 / hostc.ws2
   long guard = 0;               // doubles of guard band on either side of every mirror / scratch array
   RomsDev hostc{};            // host copy of the constant block
   RomsDev *devc = nullptr;    // device copy
@@ -183,7 +169,14 @@ struct RomsCtx {
 extern RomsCtx g_ctx;
 
 int  roms_fail(const char *where, const char *what);
+int  roms_setup_check(const char *me);    // every roms_hip_set_* entry: init, set_bounds and set_params came first
+// every roms_hip_get_* entry: `count` elements of `elem` bytes from the device to the host, refused where the host
+// array has another size ("FAMILY: NAME has COUNT UNIT, the host array HOST_COUNT")
+int  roms_copy_out(const char *me, const char *family, const char *name, const void *dev, long count, void *host,
+                   long host_count, size_t elem = sizeof(double), const char *unit = "doubles");
 int  roms_flush_consts();                 // upload hostc -> devc when dirty
+int  roms_entry_check(const char *where); // every kernel entry calls this first
+extern const char *const k_field_name[FID_COUNT];
 long roms_field_count(int kind, const roms_bounds_t &b);
 
 #define HIP_TRY(expr)                                                         \
@@ -443,18 +436,22 @@ int halo_exchange3d(int gtype, int nk, double *A);
 void halo_batch_begin();                  // record the exchanges that follow ...
 int halo_batch_end();                     // ... and run them as one message per neighbour and phase
 int halo_allreduce_sum(double *A, long n); // mp_collect: SUM over all tiles of a device array, in place (halo.hip)
+// capi.hip: n zeroed doubles between two guard bands, entered into the table roms_hip_check_guards walks, and out of it
+int guarded_alloc(Guarded *a, const char *name, int q, long n);
+void guarded_free(Guarded *a);
+// the option stores (k_option_store, capi.hip): what roms_hip_finalize and roms_hip_set_bounds release, in this order
+void sources_release();                   // sources.hip: frees what roms_hip_set_sources allocated
+bool roms_sources_given();                // ... a table (Nsrc = 0 included) was handed over
+void clima_release();                     // clima.hip: frees what roms_hip_set_clima allocated
+void avg_release();                       // k_avg.hip: frees what roms_hip_set_averages allocated
 void floats_release();                    // k_floats.hip: frees what roms_hip_set_floats allocated
 void tides_release();                     // k_set_tides.hip: frees what roms_hip_set_tides allocated
 void data_release();                      // k_set_data.hip: drops every record of roms_hip_set_data_record / _point
-int guarded_alloc(double **user, double **base, long n);   // capi.hip: n zeroed doubles between two guard bands
-void guarded_free(double **user, double **base);
 void dia_release();                       // k_set_diags.hip: frees what roms_hip_set_diagnostics allocated
 bool dia_on();                            // ... diagnostics are switched on (the DIA instantiations run)
 int dia_check(const char *where);         // ... and what they are not built with, refused by name (0 when off)
 int dia_rate(int nnew);                   // ... step3d_t.F:1598-1611 on IstrR:IendR, JstrR:JendR (k_dia_rate)
-int dia_arrays(const char *name[4], const double *base[4], long count[4]);   // ... its arrays, for roms_hip_check_guards
 void kpp_release();                       // k_physics.hip: frees what roms_hip_set_kpp allocated
-int kpp_arrays(const char *name[3], const double *base[3], long count[3]);   // ... its arrays, for roms_hip_check_guards
 void bio_release();                       // k_biology.hip: drops the setting of roms_hip_set_biology
 // lateral boundary conditions on the S/N edges (k_base.hip); s = the barotropic time indices (Chapman, Flather),
 // nstp = the time level the radiation condition compares with

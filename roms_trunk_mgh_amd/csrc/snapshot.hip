@@ -15,8 +15,6 @@
 #include <vector>
 #include "roms_dev.h"
 
-int roms_entry_check(const char *name);
-
 namespace {
 
 struct SnapItem { int id; double *stage; double *bounce; };
@@ -67,21 +65,21 @@ extern "C" int roms_hip_snapshot_begin(const int *field_ids, int n)
   if (!g_snap_event) HIP_TRY(hipEventCreateWithFlags(&g_snap_event, hipEventDisableTiming));
   for (int q = 0; q < n; q++) {
     const int id = field_ids[q];
-    if (id < 0 || id >= FID_COUNT || !g_ctx.dev[id]) return roms_fail("roms_hip_snapshot_begin", "field not registered");
-    const size_t bytes = sizeof(double) * g_ctx.count[id];
+    if (id < 0 || id >= FID_COUNT || !g_ctx.field[id].dev) return roms_fail("roms_hip_snapshot_begin", "field not registered");
+    const size_t bytes = sizeof(double) * g_ctx.field[id].count;
     if (!g_stage[id]) HIP_TRY(hipMalloc(&g_stage[id], bytes));
     if (!g_registered[id] && !g_register_failed[id]) {
       if (hipHostRegister(g_ctx.host[id], bytes, hipHostRegisterDefault) == hipSuccess) g_registered[id] = true;
       else { (void)hipGetLastError(); g_register_failed[id] = true; }
     }
     if (!g_registered[id] && !g_bounce[id]) HIP_TRY(hipHostMalloc(&g_bounce[id], bytes, hipHostMallocDefault));
-    HIP_TRY(hipMemcpyAsync(g_stage[id], g_ctx.dev[id], bytes, hipMemcpyDeviceToDevice, g_ctx.stream));
+    HIP_TRY(hipMemcpyAsync(g_stage[id], g_ctx.field[id].dev, bytes, hipMemcpyDeviceToDevice, g_ctx.stream));
   }
   HIP_TRY(hipEventRecord(g_snap_event, g_ctx.stream));
   HIP_TRY(hipStreamWaitEvent(g_copy_stream, g_snap_event, 0));
   for (int q = 0; q < n; q++) {
     const int id = field_ids[q];
-    const size_t bytes = sizeof(double) * g_ctx.count[id];
+    const size_t bytes = sizeof(double) * g_ctx.field[id].count;
     double *dst = g_registered[id] ? g_ctx.host[id] : g_bounce[id];
     HIP_TRY(hipMemcpyAsync(dst, g_stage[id], bytes, hipMemcpyDeviceToHost, g_copy_stream));
     g_pending.push_back(SnapItem{id, g_stage[id], g_registered[id] ? nullptr : g_bounce[id]});
@@ -96,7 +94,7 @@ extern "C" int roms_hip_snapshot_end(void)
   if (g_pending.empty()) return 0;
   HIP_TRY(hipStreamSynchronize(g_copy_stream));
   for (const SnapItem &it : g_pending)
-    if (it.bounce) std::memcpy(g_ctx.host[it.id], it.bounce, sizeof(double) * g_ctx.count[it.id]);
+    if (it.bounce) std::memcpy(g_ctx.host[it.id], it.bounce, sizeof(double) * g_ctx.field[it.id].count);
   g_pending.clear();
   return 0;
 }

@@ -40,7 +40,7 @@ DECLARED_SYMBOLS = (
      "roms_hip_step2d_loop", "roms_hip_exchange", "roms_hip_timing_enable",
      "roms_hip_timing_last_ms", "roms_hip_calib_stream", "roms_hip_set_halo_relay", "roms_hip_diag",
      "roms_hip_snapshot_begin", "roms_hip_snapshot_end", "roms_hip_halo_plan",
-     "roms_hip_ana_srflux", "roms_hip_check_guards", "roms_hip_row_metrics_state",
+     "roms_hip_ana_srflux", "roms_hip_check_guards", "roms_hip_guarded_arrays", "roms_hip_row_metrics_state",
      "roms_hip_graph_exchanges", "roms_hip_graph_exchanges_state", "roms_hip_set_sources",
      "roms_hip_set_clima", "roms_hip_set_averages", "roms_hip_get_average", "roms_hip_average_device_ptr",
      "roms_hip_avg_phase", "roms_hip_set_floats", "roms_hip_floats_put", "roms_hip_floats_get",
@@ -88,6 +88,8 @@ def load():
     if hasattr(lib, "roms_hip_step2d_loop"):
         lib.roms_hip_step2d_loop.argtypes = [C.POINTER(abi.StepIdx), C.POINTER(C.c_int)]
     lib.roms_hip_calib_stream.argtypes = [C.c_long]
+    lib.roms_hip_guarded_arrays.restype = C.c_long
+    lib.roms_hip_guarded_arrays.argtypes = [C.c_char_p, C.c_long]
     _ip = C.POINTER(C.c_int)
     lib.roms_hip_set_sources.argtypes = [C.c_int, _ip, _ip, _DP, _DP, _DP, _DP, _ip]
     lib.roms_hip_set_clima.argtypes = [C.c_int, _DP, _DP, _DP, C.c_int, _DP, _DP, _DP, _ip, _DP, _DP, C.c_double]
@@ -475,6 +477,16 @@ class RomsHip:
     def check_guards(self):
         """Raise if a kernel stored outside one of the device arrays (roms_hip_check_guards)."""
         self._chk(self.l.roms_hip_check_guards(), "check_guards")
+
+    def guarded_arrays(self):
+        """The names of the arrays check_guards looks at, in allocation order: NAME, or NAME[q] for the scratch arrays
+        (roms_hip_guarded_arrays)."""
+        n = self.l.roms_hip_guarded_arrays(None, 0)
+        if n < 0:
+            self._chk(8, "guarded_arrays")
+        buf = C.create_string_buffer(64 * n + 1)
+        assert self.l.roms_hip_guarded_arrays(buf, len(buf)) == n
+        return buf.value.decode().split("\n")[:-1] if n else []
 
     def close(self):
         # the library holds ONE context per process: only its current owner may tear it down

@@ -134,6 +134,16 @@ def test_entries_refuse_uninitialised_library():
     assert b"not initialised" in lib.roms_hip_last_error()
 
 
+def test_guarded_arrays_is_exported_and_refuses_uninitialised_library():
+    lib = hip.load()
+    assert hasattr(lib, "roms_hip_guarded_arrays") and "roms_hip_guarded_arrays" in hip.DECLARED_SYMBOLS
+    lib.roms_hip_finalize()
+    buf = ctypes.create_string_buffer(64)
+    assert lib.roms_hip_guarded_arrays(None, 0) < 0
+    assert b"roms_hip_guarded_arrays" in lib.roms_hip_last_error() and b"not initialised" in lib.roms_hip_last_error()
+    assert lib.roms_hip_guarded_arrays(buf, len(buf)) < 0 and buf.value == b""
+
+
 def test_tile_neighbors_matches_python_mirror():
     from roms_trunk_mgh_amd import halo
     for (nI, nJ) in [(1, 1), (2, 1), (4, 1), (4, 2), (2, 2), (1, 2), (3, 3)]:

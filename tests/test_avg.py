@@ -41,7 +41,7 @@ def test_schedule_equals_the_table_written_by_hand(key):
     for iic in steps:
         want = table.get(iic, 0)
         assert avg.phase(iic, *key) == want, ("avg.py", key, iic)
-        assert lib.roms_hip_avg_phase(iic, *key) == want, ("capi.hip", key, iic)
+        assert lib.roms_hip_avg_phase(iic, *key) == want, ("k_avg.hip", key, iic)
         ini, acc, close, masks = au.schedule(iic, *key)
         assert (S * ini) | (A * acc) | (C * close) | (M * masks) == want, ("avg_util", key, iic)
     assert avg.phase(5, 0, 1, 1, 0) == lib.roms_hip_avg_phase(5, 0, 1, 1, 0) == 0          # nAVG = 0: set_avg.F:189
