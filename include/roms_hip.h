@@ -259,8 +259,8 @@ int roms_hip_set_vbc(const roms_step_idx_t *s);
 int roms_hip_lmd_vmix(const roms_step_idx_t *s);
 /* LMD_BKPP: the K-profile bottom boundary layer, lmd_bkpp(ng,tile), ROMS/Nonlinear/lmd_bkpp.F:44 -> lmd_bkpp_tile
  * (:95, the text :233-804), which lmd_vmix calls between lmd_skpp and lmd_finish (lmd_vmix.F:83-89).  Built as the file
- * is (its own SASHA) with RI_SPLINES and SALINITY, MASKING at run time; not built: LMD_SHAPIRO, LMD_DDMIX, the form
- * without RI_SPLINES, LIMIT_VDIFF / LIMIT_VVISC, the average avghbbl.
+ * is (its own SASHA) with RI_SPLINES and SALINITY, MASKING at run time; not built: LMD_SHAPIRO, the form without
+ * RI_SPLINES, LIMIT_VDIFF / LIMIT_VVISC, the average avghbbl.
  *
  * roms_hip_set_kpp(1, hbbl) switches it on: the library allocates hbbl (double), kbbl and ksbl (int) of mod_mixing.F on
  * (LBi:UBi, LBj:UBj); hbbl is set from the host array (a restart: get_state.F reads it, and the depth of the previous
@@ -276,6 +276,21 @@ int roms_hip_lmd_vmix(const roms_step_idx_t *s);
  * writes hbbl: the host fetches it here. */
 int roms_hip_set_kpp(int lmd_bkpp, const double *hbbl);
 int roms_hip_get_kpp(const char *name, void *host, long n);
+/* LMD_DDMIX: the double-diffusive mixing of the KPP interior, lmd_vmix.F:360-430 (salt fingering and diffusive
+ * convection from the density ratio Rrho = alfaobeta * dT / dS of t(nstp); constants of mod_scalars.F:1553-1577), with
+ * alfaobeta = Tcof / Scof of every level out of rho_eos (rho_eos.F:427-465 nonlinear, :782-797 linear).
+ *
+ * roms_hip_set_ddmix(1) switches it on: the library allocates alfaobeta of mod_mixing.F on (LBi:UBi, LBj:UBj, 0:N), zero
+ * as mod_mixing.F leaves it (level 0 is never written; the value of rho-level k sits at index k, as in the reference).
+ * From then on roms_hip_rho_eos stores it on IstrT:IendT, JstrT:JendT and roms_hip_lmd_vmix adds nu_ddt to Akt(itemp) and
+ * nu_dds to Akt(isalt) at the interior W-levels before the boundary layers match to them.  The reference exchanges
+ * alfaobeta (rho_eos.F:499-503, :538-544); its only reader, lmd_vmix_tile, reads interior points, so the library does not:
+ * the array is defined on the computed range only.  roms_hip_set_ddmix(0) releases the array and both entries launch what
+ * they launched before; roms_hip_set_bounds drops it.  Independent of roms_hip_set_kpp.  Refused by name, leaving the
+ * library as it was: a call before bounds / params, a value other than 0 / 1, NAT < 2 or no salinity (the block reads
+ * t(isalt) unconditionally).  roms_hip_get_kpp("alfaobeta", host, n) copies it out, n = points x (N+1) doubles; refused
+ * while the option is off. */
+int roms_hip_set_ddmix(int lmd_ddmix);
 /* ana_srflux(ng,tile,model)        ROMS/Functionals/ana_srflux.h:2, the ALBEDO branch (:120-150) the BENCHMARK
  * application uses: shortwave radiation from the zenith angle at (lonr, latr) for the day of the year and the
  * hour that caldate (ROMS/Utility/dateclock.F:73) returns for tdays(ng) -- the host passes those two numbers --

@@ -224,6 +224,7 @@ struct OptionStore { const char *name; void (*release)(); };
 static const OptionStore k_option_store[] = {
   {"sources", sources_release}, {"clima", clima_release}, {"avg", avg_release}, {"floats", floats_release},
   {"tides", tides_release}, {"data", data_release}, {"dia", dia_release}, {"kpp", kpp_release}, {"bio", bio_release},
+  {"ddmix", ddmix_release},
 };
 
 extern "C" int roms_hip_init(int rank, int ntileI, int ntileJ, int device_id, const void *nccl_unique_id)

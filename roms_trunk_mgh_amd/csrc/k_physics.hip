@@ -442,6 +442,33 @@ __device__ __forceinline__ void wscale(double Ustar, double sigma, double Bf, do
   }
 }
 
+// LMD_DDMIX: the double-diffusive increments at a W-level from t, s of the rho-levels below (A) and above (B) and
+// alfaobeta of the level below: lmd_vmix.F:371-419, constants of mod_scalars.F:1553-1577.  (A function, not a lambda of
+// the kernel: the kernel's lambdas keep the numbering they have without the option.)
+__device__ __forceinline__ void lmd_nu_dd(double tA, double tB, double sA, double sB, double aob, double &nu_ddt, double &nu_dds)
+{
+  const double lmd_Rrho0 = 1.9, lmd_nuf = 10.0E-4, lmd_fdd = 0.7, lmd_nu = 1.5E-6;
+  const double lmd_tdd1 = 0.909, lmd_tdd2 = 4.6, lmd_tdd3 = 0.54, lmd_sdd1 = 0.15, lmd_sdd2 = 1.85, lmd_sdd3 = 0.85;
+  const double ddDT = tB - tA;
+  double ddDS = sB - sA;
+  ddDS = copysign(1.0, ddDS) * fmax(fabs(ddDS), 1.0E-14);
+  double Rrho = aob * ddDT / ddDS;
+  if ((Rrho > 1.0) && (ddDS > 0.0)) {                          // salt fingering
+    Rrho = fmin(Rrho, lmd_Rrho0);
+    const double r = (Rrho - 1.0) / (lmd_Rrho0 - 1.0);
+    nu_dds = 1.0 - r * r;
+    nu_dds = lmd_nuf * nu_dds * nu_dds * nu_dds;
+    nu_ddt = lmd_fdd * nu_dds;
+  } else if ((0.0 < Rrho) && (Rrho < 1.0) && (ddDS < 0.0)) {   // diffusive convection
+    nu_ddt = lmd_nu * lmd_tdd1 * exp(lmd_tdd2 * exp(-lmd_tdd3 * ((1.0 / Rrho) - 1.0)));
+    if (Rrho < 0.5) nu_dds = nu_ddt * lmd_sdd1 * Rrho;
+    else nu_dds = nu_ddt * (lmd_sdd2 * Rrho - lmd_sdd3);
+  } else {
+    nu_ddt = 0.0;
+    nu_dds = 0.0;
+  }
+}
+
 // The forward recurrences of the three splines are NOT stored per level: the upward sweep keeps only their values at
 // every LMD_SEG-th level (checkpoints, in registers); the downward sweep takes the column segment by segment from the
 // top, re-runs the recurrence of a segment from its checkpoint and consumes it in descending order.  Same operations
@@ -453,7 +480,11 @@ __device__ __forceinline__ void wscale(double Ustar, double sigma, double Bf, do
 
 // BKPP (LMD_BKPP, roms_hip_set_kpp): lmd_bkpp runs between lmd_skpp and lmd_finish (lmd_vmix.F:83-89), so the last sweep
 // stores Akv / Akt without the lmd_finish increment -- k_lmd_bkpp adds it -- and ksbl goes to the library's array.
-template <int NMAX, bool BKPP = false>
+// DDMIX (LMD_DDMIX, roms_hip_set_ddmix): the double-diffusive increments nu_ddt / nu_dds of lmd_vmix.F:360-430 join the
+// interior Akt(itemp) / Akt(isalt), which then differ.  They are never stored: the last sweep forms them from t, s(nstp)
+// of the segment it loads anyway (LMD_SEG + 1 rho-levels per round trip) and alfaobeta of rho_eos, and the match at the
+// boundary-layer depth recomputes them at its two levels.
+template <int NMAX, bool BKPP = false, bool DDMIX = false>
 __global__ void __launch_bounds__(BLK_X *BLK_Y, 2)
 k_lmd_vmix(const RomsDev *__restrict__ c, int nstp, double lmd_Cg, double Vtc)
 {
@@ -476,6 +507,10 @@ k_lmd_vmix(const RomsDev *__restrict__ c, int nstp, double lmd_Cg, double Vtc)
   const gd_t ghT = (gd_t)c->F.ghats, ghS = (gd_t)(c->F.ghats + n3w);
   auto r3i = [&](int k) { return a + (long)(k - 1) * nij; };     // rho-type level k = 1..N
   auto w3i = [&](int k) { return a + (long)k * nij; };           // W-type level k = 0..N
+  // DDMIX: t(:,:,:,nstp,itemp), t(:,:,:,nstp,isalt) and alfaobeta (0:N, the value of rho-level k at index k)
+  const gcd_t ddT = DDMIX ? (gcd_t)(c->F.t + (long)(nstp - 1) * n3r) : nullptr;
+  const gcd_t ddS = DDMIX ? (gcd_t)(c->F.t + ((long)(nstp - 1) + 3L) * n3r) : nullptr;
+  const gcd_t ddA = DDMIX ? (gcd_t)c->ddmix.alfaobeta : nullptr;
   // the shear function nu_sx of W-levels 1..N-1 waits in LDS ([level][thread]) for the last sweep -- it used to be
   // parked in Akv: one field written and read back for nothing (0.13 GB each way on BENCHMARK3)
   constexpr int NTH = BLK_X * BLK_Y;
@@ -723,7 +758,17 @@ k_lmd_vmix(const RomsDev *__restrict__ c, int nstp, double lmd_Cg, double Vtc)
     const double bv_k = bvf[w3i(k)], bv_m = bvf[w3i(k - 1)];
     const double nu_k = (k <= N - 1) ? nu_col[(k - 1) * NTH] : (double)Akv[w3i(k)], nu_m = nu_col[(k - 2) * NTH];
     const double akv_k = (k <= N - 1) ? akv_a(nu_k, bv_k) : nu_k, akv_m = akv_a(nu_m, bv_m);
-    const double akt_k = (k <= N - 1) ? akt_a(nu_k, bv_k) : (double)AkT[w3i(k)], akt_m = akt_a(nu_m, bv_m);
+    // DDMIX: the increments of the two levels, recomputed (level N keeps the array's own values)
+    double ddt_k = 0.0, dds_k = 0.0, ddt_m = 0.0, dds_m = 0.0;
+    if constexpr (DDMIX) {
+      const long q0 = r3i(k - 1), q1 = r3i(k), q2 = r3i(min(k + 1, N));
+      const double tt0 = ddT[q0], tt1 = ddT[q1], tt2 = ddT[q2], ts0 = ddS[q0], ts1 = ddS[q1], ts2 = ddS[q2];
+      const double ab_m = ddA[w3i(k - 1)], ab_k = ddA[w3i(min(k, N - 1))];
+      lmd_nu_dd(tt0, tt1, ts0, ts1, ab_m, ddt_m, dds_m);
+      lmd_nu_dd(tt1, tt2, ts1, ts2, ab_k, ddt_k, dds_k);
+    }
+    const double akt_k = (k <= N - 1) ? (DDMIX ? akt_a(nu_k, bv_k) + ddt_k : akt_a(nu_k, bv_k)) : (double)AkT[w3i(k)],
+                 akt_m = DDMIX ? akt_a(nu_m, bv_m) + ddt_m : akt_a(nu_m, bv_m);
     double K_bl = cff_dn * akv_k + cff_up * akv_m;
     double dK_bl = cff * (akv_k - akv_m);
     Gm1 = K_bl / (zbl * wm + eps);
@@ -734,8 +779,10 @@ k_lmd_vmix(const RomsDev *__restrict__ c, int nstp, double lmd_Cg, double Vtc)
     Gt1 = K_bl / (zbl * ws + eps);
     if (masking) Gt1 = Gt1 * mr;                                 // :765
     dGt1dS = fmin(0.0, -dK_bl / (ws + eps) - K_bl * f1);
-    // salinity: Akt(isalt) = Akt(itemp) at the interior levels (lmd_vmix.F:296-297); level N was not touched
-    const double aks_k = (k <= N - 1) ? akt_k : (double)AkS[w3i(k)], aks_km1 = akt_m;
+    // salinity: Akt(isalt) = Akt(itemp) at the interior levels (lmd_vmix.F:296-297), with DDMIX plus its own increment;
+    // level N was not touched
+    const double aks_k = (k <= N - 1) ? (DDMIX ? akt_a(nu_k, bv_k) + dds_k : akt_k) : (double)AkS[w3i(k)],
+                 aks_km1 = DDMIX ? akt_a(nu_m, bv_m) + dds_m : akt_m;
     K_bl = cff_dn * aks_k + cff_up * aks_km1;
     dK_bl = cff * (aks_k - aks_km1);
     Gs1 = K_bl / (zbl * ws + eps);
@@ -766,12 +813,34 @@ k_lmd_vmix(const RomsDev *__restrict__ c, int nstp, double lmd_Cg, double Vtc)
       const long q3 = w3i(min(kb + t, N - 1));
       nuA[t] = nu_col[(min(kb + t, N - 1) - 1) * NTH]; zwA[t] = z_w[q3]; bvA[t] = bvf[q3];
     }
+    // DDMIX: rho-levels kb .. kb+SEG, alfaobeta of kb .. kb+SEG-1, with the segment's other loads; the increments themselves
+    // (two exp) are formed only at the levels the boundary layer leaves alone, k <= ksbl.  (Initialised, though every
+    // element read is loaded first: with plain declarations the instantiations without the option lose their identity
+    // with the code the kernel had before the option existed -- same instructions, other registers.)
+    double ttA[LMD_SEG + 1] = {}, tsA[LMD_SEG + 1] = {}, abA[LMD_SEG] = {};
+    if constexpr (DDMIX) {
+#pragma unroll
+      for (int t = 0; t <= LMD_SEG; t++) {
+        const long q = r3i(min(kb + t, N));
+        ttA[t] = ddT[q]; tsA[t] = ddS[q];
+      }
+#pragma unroll
+      for (int t = 0; t < LMD_SEG; t++) abA[t] = ddA[w3i(min(kb + t, N - 1))];
+    }
 #pragma unroll
     for (int t = 0; t < LMD_SEG; t++) {
       const int k = kb + t;
       if (k <= N - 1) {
         const double zwk = zwA[t], bvk = bvA[t];
         double akv = akv_a(nuA[t], bvk), akt = akt_a(nuA[t], bvk), aks = akt;
+        if constexpr (DDMIX) {
+          if (k <= ksbl) {                     // (above ksbl the boundary-layer profile replaces akt / aks)
+            double nut, nus;
+            lmd_nu_dd(ttA[t], ttA[t + 1], tsA[t], tsA[t + 1], abA[t], nut, nus);
+            akt = akt + nut;
+            aks = aks + nus;
+          }
+        }
         if (k > ksbl) {
           const double depth = zwN - zwk;
           double gT, gS;
@@ -1127,11 +1196,55 @@ extern "C" int roms_hip_set_kpp(int lmd_bkpp, const double *hbbl)
   return 0;
 }
 
+// ---- LMD_DDMIX: the switch and alfaobeta of mod_mixing.F (roms_hip_set_ddmix; read through roms_hip_get_kpp) ----
+namespace {
+struct DdmixStore {
+  Guarded a;                                                     // alfaobeta (LBi:UBi, LBj:UBj, 0:N)
+  long n3w = 0;
+} g_ddmix;
+}  // namespace
+
+// (roms_hip_set_bounds: alfaobeta has the old extents)
+void ddmix_release()
+{
+  guarded_free(&g_ddmix.a);
+  g_ddmix.n3w = 0;
+  g_ctx.hostc.ddmix = RomsDdmix{};
+  g_ctx.devc_dirty = true;
+}
+
+extern "C" int roms_hip_set_ddmix(int lmd_ddmix)
+{
+  const char *me = "roms_hip_set_ddmix";
+  if (int rc = roms_setup_check(me)) return rc;
+  if (lmd_ddmix != 0 && lmd_ddmix != 1) return roms_fail(me, "ddmix: lmd_ddmix is 0 or 1");
+  if (lmd_ddmix == 0) {
+    if (g_ddmix.a.dev) HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+    ddmix_release();
+    return 0;
+  }
+  const roms_bounds_t &b = g_ctx.b;
+  // lmd_vmix.F:376 reads t(isalt) without a SALINITY guard
+  if (b.NAT < 2 || !g_ctx.p.salinity) return roms_fail(me, "ddmix: LMD_DDMIX reads salinity: built for the SALINITY set-up (NAT = 2)");
+  if (g_ddmix.a.dev) return 0;                                   // already on: alfaobeta stays what rho_eos left
+  const long n3w = (long)(b.UBi - b.LBi + 1) * (long)(b.UBj - b.LBj + 1) * (long)(b.N + 1);
+  HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+  if (int rc = guarded_alloc(&g_ddmix.a, "alfaobeta", -1, n3w)) { ddmix_release(); return rc; }   // zeroed, as mod_mixing.F leaves it
+  g_ddmix.n3w = n3w;
+  g_ctx.hostc.ddmix.alfaobeta = g_ddmix.a.dev;
+  g_ctx.devc_dirty = true;
+  return 0;
+}
+
 extern "C" int roms_hip_get_kpp(const char *name, void *host, long n)
 {
   const char *me = "roms_hip_get_kpp";
   if (!g_ctx.inited) return roms_fail(me, "library not initialised");
   if (!name || !host) return roms_fail(me, "kpp: null argument");
+  if (!strcmp(name, "alfaobeta")) {
+    if (!g_ddmix.a.dev) return roms_fail(me, "kpp: LMD_DDMIX is not switched on (roms_hip_set_ddmix)");
+    return roms_copy_out(me, "kpp", name, g_ddmix.a.dev, g_ddmix.n3w, host, n);
+  }
   for (int q = 0; q < 3; q++) {
     if (strcmp(name, k_kpp_name[q])) continue;
     if (!g_kpp.a[q].dev) return roms_fail(me, "kpp: LMD_BKPP is not switched on (roms_hip_set_kpp)");
@@ -1150,6 +1263,7 @@ extern "C" int roms_hip_lmd_vmix(const roms_step_idx_t *s)
   const long nij = (long)(b.UBi - b.LBi + 1) * (b.UBj - b.LBj + 1);
   const long n3w = nij * (b.N + 1);
   const bool bkpp = g_ctx.hostc.kpp.bkpp != 0;
+  const bool ddmix = g_ctx.hostc.ddmix.alfaobeta != nullptr;
   {
     ScopedTimer tm("lmd_vmix");
     // run-time constants of mod_scalars.F:4330 (lmd_Cg) and lmd_skpp.F:300 (Vtc), evaluated on the host
@@ -1159,22 +1273,19 @@ extern "C" int roms_hip_lmd_vmix(const roms_step_idx_t *s)
     const double Vtc = lmd_Cv * sqrt(-lmd_betaT) / (sqrt(lmd_cs * lmd_epsilon) * lmd_Ric * vonKar * vonKar);
     const dim3 grid = grid2d(b.Iend - b.Istr + 1, b.Jend - b.Jstr + 1);
     if (b.N > ROMS_MAXN) return roms_fail("roms_hip_lmd_vmix", "N > 64 not instantiated");
-    if (!bkpp) {
-      if (b.N <= 32) hipLaunchKernelGGL(k_lmd_vmix<32>, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nstp, lmd_Cg, Vtc);
-      else hipLaunchKernelGGL(k_lmd_vmix<ROMS_MAXN>, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nstp, lmd_Cg, Vtc);
-      KERNEL_CHECK("k_lmd_vmix");
-    } else {
+    // <32 | ROMS_MAXN> x <BKPP> x <DDMIX>
+    void (*kern)(const RomsDev *, int, double, double);
+    if (b.N <= 32) kern = bkpp ? (ddmix ? k_lmd_vmix<32, true, true> : k_lmd_vmix<32, true, false>)
+                               : (ddmix ? k_lmd_vmix<32, false, true> : k_lmd_vmix<32, false, false>);
+    else kern = bkpp ? (ddmix ? k_lmd_vmix<ROMS_MAXN, true, true> : k_lmd_vmix<ROMS_MAXN, true, false>)
+                     : (ddmix ? k_lmd_vmix<ROMS_MAXN, false, true> : k_lmd_vmix<ROMS_MAXN, false, false>);
+    hipLaunchKernelGGL(kern, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nstp, lmd_Cg, Vtc);
+    KERNEL_CHECK("k_lmd_vmix");
+    if (bkpp) {
       // LMD_BKPP, lmd_vmix.F:83-89: lmd_skpp without the lmd_finish increment, then lmd_bkpp, which adds it (the Vtc of
-      // lmd_bkpp.F:233 is the expression of lmd_skpp.F:300)
-      if (b.N <= 32) {
-        hipLaunchKernelGGL((k_lmd_vmix<32, true>), grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nstp, lmd_Cg, Vtc);
-        KERNEL_CHECK("k_lmd_vmix");
-        hipLaunchKernelGGL(k_lmd_bkpp<32>, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nstp, Vtc);
-      } else {
-        hipLaunchKernelGGL((k_lmd_vmix<ROMS_MAXN, true>), grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nstp, lmd_Cg, Vtc);
-        KERNEL_CHECK("k_lmd_vmix");
-        hipLaunchKernelGGL(k_lmd_bkpp<ROMS_MAXN>, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nstp, Vtc);
-      }
+      // lmd_bkpp.F:233 is the expression of lmd_skpp.F:300); it reads AkT and AkS separately, LMD_DDMIX changes nothing in it
+      if (b.N <= 32) hipLaunchKernelGGL(k_lmd_bkpp<32>, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nstp, Vtc);
+      else hipLaunchKernelGGL(k_lmd_bkpp<ROMS_MAXN>, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nstp, Vtc);
       KERNEL_CHECK("k_lmd_bkpp");
     }
     const int nj = b.Jend - b.Jstr + 1, ni_ = b.Iend - b.Istr + 1;

@@ -62,6 +62,20 @@ __device__ __forceinline__ EosPt eos_point(double tt, double ts, double Tp)
   return o;
 }
 
+// thermal expansion and saline contraction at one point, rho_eos.F:436-452: Tcof, Scof and wrk from the point's EosPt e
+// (DERIV) and depth zr; alpha = Tcof / wrk, beta = Scof / wrk (level N), alfaobeta = Tcof / Scof (LMD_DDMIX, every level)
+#define EOS_COF(e, zr)                                               \
+      const double Tpr10 = 0.1 * zr;                                 \
+      const double cff = e.bulk + Tpr10;                             \
+      const double cff1 = Tpr10 * e.den1;                            \
+      const double cff2 = e.bulk * cff;                              \
+      const double wrk = (e.den + 1000.0) * cff * cff;               \
+      const double Tcof = -(e.DbulkDT * cff1 + e.Dden1DT * cff2);    \
+      const double Scof = (e.DbulkDS * cff1 + e.Dden1DS * cff2);
+
+// DDMIX (LMD_DDMIX, roms_hip_set_ddmix): the coefficient loop runs over every level (rho_eos.F:427-431) and stores
+// alfaobeta(i,j,k) = Tcof / Scof; the array is (0:N), level 0 is never written and rho-level k sits at index k.
+template <bool DDMIX>
 __global__ void __launch_bounds__(BLK_X *BLK_Y)
 k_rho_eos_nonlin(const RomsDev *__restrict__ c, int nrhs)
 {
@@ -78,6 +92,7 @@ k_rho_eos_nonlin(const RomsDev *__restrict__ c, int nrhs)
   const gcd_t z_w = (gcd_t)(c->F.z_w);
   const gcd_t Hz = (gcd_t)(c->F.Hz);
   const double g = c->p.g;
+  const gd_t aob = DDMIX ? (gd_t)c->ddmix.alfaobeta : nullptr;
   double rhoA = 0.0, rhoS = 0.0;
   EosPt up{};
   double zr_up = 0.0;
@@ -92,23 +107,22 @@ k_rho_eos_nonlin(const RomsDev *__restrict__ c, int nrhs)
       e = eos_point<true>(tt, ts, zr);
       if (masking) e.den = e.den * rm;                      // MASKING, rho_eos.F:356
       // surface thermal expansion / saline contraction, rho_eos.F:480-520
-      const double Tpr10 = 0.1 * zr;
-      const double cff = e.bulk + Tpr10;
-      const double cff1 = Tpr10 * e.den1;
-      const double cff2 = e.bulk * cff;
-      const double wrk = (e.den + 1000.0) * cff * cff;
-      const double Tcof = -(e.DbulkDT * cff1 + e.Dden1DT * cff2);
-      const double Scof = (e.DbulkDS * cff1 + e.Dden1DS * cff2);
+      EOS_COF(e, zr)
       const double r = 1.0 / wrk;
       GF(alpha)[c0] = r * Tcof;
       GF(beta)[c0] = r * Scof;
+      if constexpr (DDMIX) aob[c0 + (long)k * nij] = Tcof / Scof;
       const double cf1 = e.den * hz;
       rhoS = 0.5 * cf1 * hz;
       rhoA = cf1;
       GF(bvf)[c0 + (long)N * nij] = 0.0;
     } else {
-      e = eos_point<false>(tt, ts, zr);
+      e = eos_point<DDMIX>(tt, ts, zr);
       if (masking) e.den = e.den * rm;
+      if constexpr (DDMIX) {
+        EOS_COF(e, zr)
+        aob[c0 + (long)k * nij] = Tcof / Scof;
+      }
       const double cf1 = e.den * hz;
       rhoS = rhoS + hz * (rhoA + 0.5 * cf1);
       rhoA = rhoA + cf1;
@@ -134,6 +148,7 @@ k_rho_eos_nonlin(const RomsDev *__restrict__ c, int nrhs)
   GF(rhoS)[c0] = 2.0 * cff1 * cff1 * cff2 * rhoS;
 }
 
+template <bool DDMIX>
 __global__ void __launch_bounds__(BLK_X *BLK_Y)
 k_rho_eos_lin(const RomsDev *__restrict__ c, int nrhs)
 {
@@ -148,8 +163,11 @@ k_rho_eos_lin(const RomsDev *__restrict__ c, int nrhs)
   const bool salt = c->p.salinity != 0 && b.NT >= 2;
   const double R0 = c->p.R0, T0 = c->p.T0, S0 = c->p.S0, Tcoef = c->p.Tcoef, Scoef = c->p.Scoef;
   double rhoA = 0.0, rhoS = 0.0;
+  // LMD_DDMIX, rho_eos.F:782-797: the ratio of the two constants at every level
+  const double aob = ((Scoef == 0.0) ? 1.0 : 1.0 / Scoef) * Tcoef;
   for (int k = N; k >= 1; k--) {
     const long ck = c0 + (long)(k - 1) * nij;
+    if constexpr (DDMIX) ((gd_t)c->ddmix.alfaobeta)[c0 + (long)k * nij] = aob;
     double r = R0 - R0 * Tcoef * (T[ck] - T0);
     if (salt) r = r + R0 * Scoef * (S[ck] - S0);
     r = r - 1000.0;
@@ -167,6 +185,8 @@ k_rho_eos_lin(const RomsDev *__restrict__ c, int nrhs)
   GF(rhoS)[c0] = 2.0 * cff1 * cff1 * cff2 * rhoS;
 }
 
+#undef EOS_COF
+
 }  // namespace
 
 extern "C" int roms_hip_rho_eos(const roms_step_idx_t *s)
@@ -176,10 +196,12 @@ extern "C" int roms_hip_rho_eos(const roms_step_idx_t *s)
   ScopedTimer tm("rho_eos");
   const roms_bounds_t &b = g_ctx.b;
   dim3 grid = grid2d(b.IendT - b.IstrT + 1, b.JendT - b.JstrT + 1);
-  if (g_ctx.p.nonlin_eos)
-    hipLaunchKernelGGL(k_rho_eos_nonlin, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs);
-  else
-    hipLaunchKernelGGL(k_rho_eos_lin, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs);
+  // LMD_DDMIX (roms_hip_set_ddmix): the instantiations that store alfaobeta as well.  The reference exchanges it
+  // (rho_eos.F:499-503, :538-544); its only reader, lmd_vmix_tile, reads interior points, so it is not exchanged here
+  const bool ddmix = g_ctx.hostc.ddmix.alfaobeta != nullptr;
+  void (*kern)(const RomsDev *, int) =
+      g_ctx.p.nonlin_eos ? (ddmix ? k_rho_eos_nonlin<true> : k_rho_eos_nonlin<false>) : (ddmix ? k_rho_eos_lin<true> : k_rho_eos_lin<false>);
+  hipLaunchKernelGGL(kern, grid, block2d(), 0, g_ctx.stream, g_ctx.devc, s->nrhs);
   KERNEL_CHECK("k_rho_eos");
   halo_batch_begin();
   halo_exchange3d(GT_R, b.N, g_ctx.field[FID_rho].dev);

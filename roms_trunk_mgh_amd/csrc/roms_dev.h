@@ -118,6 +118,13 @@ struct RomsBio {
   roms_bio_powell_t powell;
 };
 
+// LMD_DDMIX (roms_hip_set_ddmix, k_physics.hip): alfaobeta (LBi:UBi, LBj:UBj, 0:N) of mod_mixing.F, library-owned, written
+// by rho_eos on IstrT:IendT, JstrT:JendT and read by lmd_vmix at interior points.  nullptr: off, and no kernel reads this
+// block.  Last in RomsDev: the members before it keep their offsets.
+struct RomsDdmix {
+  double *alfaobeta;
+};
+
 struct RomsDev {
   roms_bounds_t b;
   roms_params_t p;
@@ -132,6 +139,7 @@ struct RomsDev {
   RomsDia dia;          // tracer diagnostics, wrk = nullptr without
   RomsKpp kpp;          // KPP bottom boundary layer, bkpp = 0 without
   RomsBio bio;          // biology, model = ROMS_BIO_NONE without
+  RomsDdmix ddmix;      // KPP double-diffusive mixing, alfaobeta = nullptr without
 };
 
 struct RomsCtx {
@@ -453,6 +461,7 @@ int dia_check(const char *where);         // ... and what they are not built wit
 int dia_rate(int nnew);                   // ... step3d_t.F:1598-1611 on IstrR:IendR, JstrR:JendR (k_dia_rate)
 void kpp_release();                       // k_physics.hip: frees what roms_hip_set_kpp allocated
 void bio_release();                       // k_biology.hip: drops the setting of roms_hip_set_biology
+void ddmix_release();                     // k_physics.hip: frees what roms_hip_set_ddmix allocated
 // lateral boundary conditions on the S/N edges (k_base.hip); s = the barotropic time indices (Chapman, Flather),
 // nstp = the time level the radiation condition compares with
 int bc_zeta(int kout, const roms_step_idx_t *s);

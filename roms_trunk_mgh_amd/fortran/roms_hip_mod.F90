@@ -328,6 +328,13 @@ MODULE roms_hip_mod
       TYPE(c_ptr), VALUE :: host
       INTEGER(c_long), VALUE :: n
     END FUNCTION
+    !  LMD_DDMIX: once after roms_hip_set_params, lmd_ddmix = 1; roms_hip_rho_eos then stores alfaobeta (library-owned,
+    !  MIXING(ng)%alfaobeta need not be uploaded; roms_hip_get_kpp with 'alfaobeta'//C_NULL_CHAR, n = points x (N+1), reads
+    !  it) and roms_hip_lmd_vmix adds the double-diffusive increments
+    INTEGER(c_int) FUNCTION roms_hip_set_ddmix (lmd_ddmix) BIND(C, name='roms_hip_set_ddmix')
+      IMPORT :: c_int
+      INTEGER(c_int), VALUE :: lmd_ddmix
+    END FUNCTION
     !  BIOLOGY (NPZD_POWELL): once after roms_hip_set_params, model = ROMS_BIO_NPZD_POWELL, par = C_LOC of a TARGET
     !  roms_bio_powell_t, nbytes = C_SIZEOF of it (ROMS_BIO_NONE with C_NULL_PTR drops the setting); roms_hip_biology
     !  in the place of CALL biology (ng, tile), main3d.F:795-797
@@ -540,7 +547,7 @@ MODULE roms_hip_mod
   PUBLIC :: roms_hip_step3d_uv, roms_hip_step3d_t, roms_hip_bulk_flux, roms_hip_set_vbc, roms_hip_lmd_vmix
   PUBLIC :: roms_hip_ana_srflux, roms_hip_wvelocity, roms_hip_diag, roms_hip_snapshot_begin, roms_hip_snapshot_end
   PUBLIC :: roms_hip_ini_zeta, roms_hip_ini_fields, roms_hip_gls_prestep, roms_hip_gls_corstep, roms_hip_wetdry
-  PUBLIC :: roms_hip_set_sources, roms_hip_set_clima, roms_hip_set_kpp, roms_hip_get_kpp
+  PUBLIC :: roms_hip_set_sources, roms_hip_set_clima, roms_hip_set_kpp, roms_hip_get_kpp, roms_hip_set_ddmix
   PUBLIC :: roms_hip_set_biology, roms_hip_biology
   PUBLIC :: roms_hip_set_averages, roms_hip_set_avg, roms_hip_get_average, roms_hip_average_device_ptr, roms_hip_avg_phase
   PUBLIC :: roms_hip_set_diagnostics, roms_hip_set_diags, roms_hip_get_diagnostic, roms_hip_dia_index

@@ -47,7 +47,7 @@ DECLARED_SYMBOLS = (
      "roms_hip_step_floats", "roms_hip_set_tides", "roms_hip_tides", "roms_hip_set_diagnostics",
      "roms_hip_get_diagnostic", "roms_hip_dia_index", "roms_hip_set_data_record", "roms_hip_set_data_point",
      "roms_hip_set_data", "roms_hip_set_data_factors", "roms_hip_get_clima",
-     "roms_hip_set_kpp", "roms_hip_get_kpp", "roms_hip_set_biology"] + ["roms_hip_" + e for e in ENTRIES])
+     "roms_hip_set_kpp", "roms_hip_get_kpp", "roms_hip_set_biology", "roms_hip_set_ddmix"] + ["roms_hip_" + e for e in ENTRIES])
 
 
 _DP = C.POINTER(C.c_double)
@@ -115,6 +115,7 @@ def load():
     lib.roms_hip_set_kpp.argtypes = [C.c_int, C.c_void_p]
     lib.roms_hip_get_kpp.argtypes = [C.c_char_p, C.c_void_p, C.c_long]
     lib.roms_hip_set_biology.argtypes = [C.c_int, C.c_void_p, C.c_long]
+    lib.roms_hip_set_ddmix.argtypes = [C.c_int]
     if lib.roms_abi_sizeof(5) != C.sizeof(abi.BioPowell):
         raise RuntimeError(f"ABI struct size mismatch: roms_bio_powell_t python={C.sizeof(abi.BioPowell)} "
                            f"C={lib.roms_abi_sizeof(5)}")
@@ -287,13 +288,26 @@ class RomsHip:
         self.bkpp = bool(on)
 
     def get_kpp(self, name):
-        """"hbbl" (float64), "kbbl" or "ksbl" (int32) of the bottom boundary layer on the tile's rho points
-        (roms_hip_get_kpp)."""
-        if name not in KPP_ARRAYS:
-            raise ValueError(f"get_kpp: {name!r} is not one of {sorted(KPP_ARRAYS)}")
-        out = np.zeros((self.st.ni, self.st.nj), dtype=KPP_ARRAYS[name], order="F")
+        """"hbbl" (float64), "kbbl" or "ksbl" (int32) of the bottom boundary layer on the tile's rho points, or
+        "alfaobeta" (float64, W-levels 0:N) of LMD_DDMIX (roms_hip_get_kpp)."""
+        if name not in KPP_ARRAYS and name != "alfaobeta":
+            raise ValueError(f"get_kpp: {name!r} is not one of {sorted(KPP_ARRAYS) + ['alfaobeta']}")
+        if name == "alfaobeta":
+            out = np.zeros((self.st.ni, self.st.nj, self.st.b.N + 1), dtype=np.float64, order="F")
+        else:
+            out = np.zeros((self.st.ni, self.st.nj), dtype=KPP_ARRAYS[name], order="F")
         self._chk(self.l.roms_hip_get_kpp(name.encode(), out.ctypes.data, out.size), "get_kpp " + name)
         return out
+
+    def set_ddmix(self, lmd_ddmix=True):
+        """LMD_DDMIX, the double-diffusive mixing of KPP -> roms_hip_set_ddmix: rho_eos stores alfaobeta (library-owned,
+        get_kpp("alfaobeta")) and lmd_vmix adds nu_ddt / nu_dds to the interior Akt; False releases alfaobeta."""
+        if isinstance(lmd_ddmix, (bool, np.bool_)):
+            lmd_ddmix = int(lmd_ddmix)
+        if not isinstance(lmd_ddmix, (int, np.integer)) or lmd_ddmix not in (0, 1):
+            raise ValueError(f"set_ddmix: lmd_ddmix is False / True (0 / 1), not {lmd_ddmix!r}")
+        self._chk(self.l.roms_hip_set_ddmix(int(lmd_ddmix)), "set_ddmix")
+        self.ddmix = bool(lmd_ddmix)
 
     def set_biology(self, model="NPZD_POWELL", par=None):
         """BIOLOGY -> roms_hip_set_biology.  model: a name of abi.BIO_MODEL or its code, None / "NONE" drops the

@@ -50,7 +50,7 @@ def host_clock(tdays):
 
 class Main3D:
     def __init__(self, backend, ntstart=1, physics=False, diagnostics=False, ninfo=1, averages=None, floats=None, tides=None,
-                 diags=None, data=None, bkpp=False, hbbl=None, biology=None):
+                 diags=None, data=None, bkpp=False, hbbl=None, biology=None, ddmix=False):
         """physics=True also runs the per-step physics that is on the device:
         bulk_flux and lmd_vmix (BULK_FLUXES / LMD_MIXING applications, i.e. BENCHMARK) and set_vbc, in
         the reference's order;
@@ -77,6 +77,7 @@ class Main3D:
         (set_2dfld.F:139-141: a new record is due before the next step).  With None the sequence is unchanged.
         bkpp=True (LMD_BKPP applications): set_kpp is issued here, once, with hbbl (the depth of a restart file; None =
         zero, mod_mixing.F); the per-step call stays lmd_vmix, as the reference's lmd_vmix(ng, tile) is one call.
+        ddmix=True (LMD_DDMIX applications): set_ddmix is issued here, once; rho_eos and lmd_vmix then carry the option.
         biology: a bio.PowellPar (BIOLOGY applications with NPZD_POWELL): set_biology is issued here, once, and every step
         issues biology between gls_corstep and step3d_t (main3d.F:795-797).  With None the sequence is unchanged."""
         self.be = backend
@@ -99,6 +100,9 @@ class Main3D:
         self.bkpp = bool(bkpp)
         if bkpp:
             backend.set_kpp(True, hbbl)
+        self.ddmix = bool(ddmix)
+        if ddmix:
+            backend.set_ddmix(True)
         self.biology = biology
         if biology is not None:
             backend.set_biology(biology.model, biology)
