@@ -21,6 +21,7 @@
 // file against the oracle (tests/test_gpu_gls.py).
 #include "roms_dev.h"
 #include "gls.h"
+#include "kpp.h"                // spline_coef / spline_fwd / spline_back, nothing else
 
 namespace {
 
@@ -241,10 +242,10 @@ k_gls_shear(const RomsDev *__restrict__ c, int nstp, double *__restrict__ S, dou
     double CFm = 0.0, dUm = 0.0, dVm = 0.0;
     for (int k = 1; k <= N - 1; k++) {
       const long r = a2 + (long)(k - 1) * nij;
-      const double cff = 1.0 / (2.0 * Hz[r + nij] + Hz[r] * (2.0 - CFm));
-      const double CFk = cff * Hz[r + nij];
-      const double dUk = cff * (3.0 * (u[r + nij] - u[r] + u[r + nij + 1] - u[r + 1]) - Hz[r] * dUm);
-      const double dVk = cff * (3.0 * (v[r + nij] - v[r] + v[r + nij + ni] - v[r + ni]) - Hz[r] * dVm);
+      const SplineCoef sc = spline_coef(Hz[r], Hz[r + nij], CFm);                      // kpp.h: the splines of RI_SPLINES
+      const double CFk = sc.FC;
+      const double dUk = spline_fwd(sc.cff, 3.0 * (u[r + nij] - u[r] + u[r + nij + 1] - u[r + 1]), Hz[r], dUm);
+      const double dVk = spline_fwd(sc.cff, 3.0 * (v[r + nij] - v[r] + v[r + nij + ni] - v[r + ni]), Hz[r], dVm);
       CFs[a2 + (long)k * nij] = CFk; dUs[a2 + (long)k * nij] = dUk; dVs[a2 + (long)k * nij] = dVk;
       CFm = CFk; dUm = dUk; dVm = dVk;
     }
@@ -252,7 +253,7 @@ k_gls_shear(const RomsDev *__restrict__ c, int nstp, double *__restrict__ S, dou
     for (int k = N - 1; k >= 1; k--) {
       const long w = a2 + (long)k * nij;
       const double cf = CFs[w];
-      const double dUk = dUs[w] - cf * dUp, dVk = dVs[w] - cf * dVp;
+      const double dUk = spline_back(dUs[w], cf, dUp), dVk = spline_back(dVs[w], cf, dVp);
       S[w] = dUk * dUk + dVk * dVk;
       dUp = dUk; dVp = dVk;
     }

@@ -102,7 +102,7 @@ struct RomsDia {
 // DiaTwrk(:,:,:,itrc,idiag) of term `id` (device code; n3r = points of a rho-array)
 #define DIA_PLANE(c, id, itrc, n3r) ((gd_t)((c)->dia.wrk + ((long)(c)->dia.ix[id] * (c)->b.NT + ((itrc) - 1)) * (n3r)))
 
-// LMD_BKPP (roms_hip_set_kpp, k_physics.hip): the switch and the library-owned arrays of mod_mixing.F the bottom
+// LMD_BKPP (roms_hip_set_kpp, k_lmd.hip): the switch and the library-owned arrays of mod_mixing.F the bottom
 // boundary layer adds -- hbbl (double), kbbl and ksbl (int), all (LBi:UBi, LBj:UBj).  bkpp = 0: off, and no kernel reads
 // this block.
 struct RomsKpp {
@@ -118,7 +118,7 @@ struct RomsBio {
   roms_bio_powell_t powell;
 };
 
-// LMD_DDMIX (roms_hip_set_ddmix, k_physics.hip): alfaobeta (LBi:UBi, LBj:UBj, 0:N) of mod_mixing.F, library-owned, written
+// LMD_DDMIX (roms_hip_set_ddmix, k_lmd.hip): alfaobeta (LBi:UBi, LBj:UBj, 0:N) of mod_mixing.F, library-owned, written
 // by rho_eos on IstrT:IendT, JstrT:JendT and read by lmd_vmix at interior points.  nullptr: off, and no kernel reads this
 // block.  Last in RomsDev: the members before it keep their offsets.
 struct RomsDdmix {
@@ -459,9 +459,9 @@ void dia_release();                       // k_set_diags.hip: frees what roms_hi
 bool dia_on();                            // ... diagnostics are switched on (the DIA instantiations run)
 int dia_check(const char *where);         // ... and what they are not built with, refused by name (0 when off)
 int dia_rate(int nnew);                   // ... step3d_t.F:1598-1611 on IstrR:IendR, JstrR:JendR (k_dia_rate)
-void kpp_release();                       // k_physics.hip: frees what roms_hip_set_kpp allocated
+void kpp_release();                       // k_lmd.hip: frees what roms_hip_set_kpp allocated
 void bio_release();                       // k_biology.hip: drops the setting of roms_hip_set_biology
-void ddmix_release();                     // k_physics.hip: frees what roms_hip_set_ddmix allocated
+void ddmix_release();                     // k_lmd.hip: frees what roms_hip_set_ddmix allocated
 // lateral boundary conditions on the S/N edges (k_base.hip); s = the barotropic time indices (Chapman, Flather),
 // nstp = the time level the radiation condition compares with
 int bc_zeta(int kout, const roms_step_idx_t *s);

@@ -50,7 +50,7 @@ RUNGS = {
     # k_step3d_t_pipe: 16 / 32 / 64; in the unmasked k_step3d_t_pipe they also meet its rung 48)
     "a4_slopes": (16, 32, 64),
     "spline_w": (16, 32, 64),
-    "k_lmd_vmix": (32, 64),                          # k_physics.hip:867-868
+    "k_lmd_vmix": (32, 64),                          # k_lmd.hip, roms_hip_lmd_vmix: n32
     "k_uv_column_classic": (32, 64),                 # k_step3d_uv.hip:429-430
     "k_step3d_t_pipe:src": (64,),                    # k_step3d_t.hip:460-463: one instantiation for every N
     "k_step3d_t_pipe:classic": (64,),                # k_step3d_t.hip:447-449: one instantiation for every N
